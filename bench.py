@@ -23,7 +23,12 @@ over 31 daily snapshots generated and derived in HBM inside the timed region (2 
 particles per GPU (weak scaling, 1e8 on 8 GPUs), dt 60 s, 12 calendar-month pairs (Jan..Dec =
 365 days = 525 600 steps, daily records; ``--pairs k`` runs the first k months).
 
-Inputs (mesh, fields, seeds) are resident in HBM before the timed region.
+Inputs (mesh, fields, seeds) are resident in HBM before the timed region, and identical from run to run
+for the same arguments (fixed seeds, analytic fields).  A plain run sets up, warms up, times ``--steps``
+steps and prints the line; ``--dump-outputs DIR`` also writes the last timed step's results (a fixed
+particle sample, float64 .npy) so two builds can be compared output for output.  ``--full`` adds the
+line's companions, each a run of its own after the timed steps: the CPU baseline (``cpu_baseline``), the
+RK4 companion (``rk4_companion``) and config 3's host delivery (``host_delivery``).
 Rank 0 prints one JSON line (driver contract).
 """
 from __future__ import annotations
@@ -86,7 +91,7 @@ def parse(argv=None):
                         "0.5 s pair), the gather 11.5 GB per link (~75 ms).  'checkpoint' = only every particle's "
                         "final state (position, depth, death, id) / the pair's continuation points")
     p.add_argument("--deliver", choices=["host", "none"], default="host",
-                   help="config 3, N = 1: also time the chain with every pair's lines delivered to pinned host "
+                   help="--full, config 3, N = 1: also time the chain with every pair's lines delivered to pinned host "
                         "memory (chain.HostLineSink: a copy stream overlapped with the next pair), as the reference "
                         "returns them to its caller -> the line's host_delivery block (value stays device-resident)")
     p.add_argument("--topography", choices=["sigma", "zlevel"], default="sigma",
@@ -110,8 +115,17 @@ def parse(argv=None):
                         "(parts, overlapping the other parts' final waves) or all lines once every part is done")
     p.add_argument("--compact-priority", action="store_true",
                    help="run the compaction re-sorts on high-priority streams (experiment)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample length")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the companions of the line, each a run of its own: the CPU "
+                        "baseline (cpu_baseline; not with --no-cpu-baseline) and, for N = 1 Euler, the RK4 companion "
+                        "(rk4_companion) and config 3's host delivery (host_delivery, --deliver host).  Off by default: "
+                        "a plain run sets up, warms up, times --steps steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step returned to its caller as DIR/<name>.npy "
+                        "(float64; per-particle arrays as the rows of a fixed, seeded particle sample listed in "
+                        "sample_index.npy, at most 64 MB in all; ranks > 0 write <name>.rank<r>.npy)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    p.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: target CPU-baseline sample length")
     return p.parse_args(argv)
 
 
@@ -409,6 +423,46 @@ def algorithmic_bytes_per_pstep(nv: float, L: int, S: int = 1) -> float:
     return (4 + 4 * nv + 4 * nv + 24 * nv + 24 * (nv + 1) + S * (8 * nv * L + 2 * 24 * nv + 2 * 8 * nv) + 32)
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # the sampled rows of every array together (the 64 MB limit less headroom)
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_sample_index(n: int, row_bytes: int) -> np.ndarray:
+    """The particles whose rows --dump-outputs writes: all of them if they fit DUMP_BUDGET_BYTES, else a
+    sorted sample drawn without replacement from a fixed seed (the same for the same n and row size)."""
+    k = max(1, DUMP_BUDGET_BYTES // max(1, row_bytes))
+    if k >= n:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir: str, per_particle: dict, scalars: dict, rank: int = 0) -> dict:
+    """--dump-outputs: the last timed step's results as out_dir/<name>.npy in float64.  ``per_particle``:
+    device tensors with one row per particle in seed order (all of the same length), written as the rows
+    of dump_sample_index (itself written as sample_index.npy); ``scalars``: device scalars, written as
+    one-element arrays.  Returns {file name: bytes}."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    tail = ".npy" if rank == 0 else f".rank{rank}.npy"
+    n = int(next(iter(per_particle.values())).shape[0])
+    row_bytes = 8 * (1 + sum(int(t[0].numel()) for t in per_particle.values())) if n else 8
+    idx = dump_sample_index(n, row_bytes)
+    arrays = {"sample_index": idx.astype(np.float64)}
+    dev_idx = None
+    for name, t in per_particle.items():
+        if dev_idx is None:
+            dev_idx = torch.as_tensor(idx, device=t.device)
+        arrays[name] = t.index_select(0, dev_idx).to(torch.float64).cpu().numpy()
+    for name, t in scalars.items():
+        arrays[name] = np.asarray([float(t.item() if hasattr(t, "item") else t)], dtype=np.float64)
+    written = {}
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, name + tail)
+        np.save(path, np.ascontiguousarray(a, dtype=np.float64))
+        written[name + tail] = int(a.nbytes)
+    return written
+
+
 CONFIG3 = dict(mode="pathline", particles=10_000_000, dt=60, duration=86400, record=3600, method="euler")
 # (configs 3-5: `duration` is the daily snapshot spacing; config 5's snapshots are monthly -- each pair's
 # duration comes from its calendar month, chain_timestamps)
@@ -615,10 +669,13 @@ def main():
     death = ps.death.to(torch.int64)
     attempted = torch.where(death < 0, torch.full_like(death, n_steps), death + 1).sum().item()
     dead = int((death >= 0).sum().item())
-    # the north star's integrator on the same workload, timed after the Euler line (N = 1 only;
+    if args.dump_outputs:  # the last timed call's lines (seed order), before anything else runs
+        dump_outputs(args.dump_outputs, dict(lines_out[0], death_step=ps.original(ps.death)), {}, rank)
+    # the north star's integrator on the same workload, timed after the Euler line (--full, N = 1 only;
     # not part of `value`, which is the reference's default integrator, MPASOVisualizer.h:99)
     rk4 = None
-    if world == 1 and args.method == "euler" and not pathline and os.environ.get("MOPS_BENCH_NO_RK4") != "1":
+    if (args.full and world == 1 and args.method == "euler" and not pathline
+            and os.environ.get("MOPS_BENCH_NO_RK4") != "1"):
         cfg4 = TrajectoryConfig(deltaT=args.dt, simulationDuration=args.duration, recordT=args.record,
                                 depth=args.depth, method=0)
         ps4 = ParticleSet(dmesh, seeds, args.depth, cfg4, device=dev)
@@ -665,7 +722,7 @@ def main():
     finalize_avg = (sum(fms) / len(fms)) if fms else None
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         back_snap = (synth.make_snapshot(mesh, timestep=1, phase=0.35, topography=args.topography)
                      if pathline else None)
         cpu = cpu_baseline(mesh, snap, back_snap, seeds, seed_cells, args, n_steps)
@@ -875,8 +932,10 @@ def main_chain(args, mesh, dev, world, rank):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     attempted = 0
+    res = None
     for k in range(args.steps):
-        attempted += int(one_call(True)["attempted"].item())
+        res = one_call(True)  # (what the chain's caller receives: lastPoint, death_step, attempted)
+        attempted += int(res["attempted"].item())
         if rank == 0:
             print(f"[bench] timed chain {k + 1}/{args.steps} done at {time.perf_counter() - t0:.1f} s", file=sys.stderr,
                   flush=True)
@@ -884,6 +943,10 @@ def main_chain(args, mesh, dev, world, rank):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and res is not None:  # the last timed chain's results (seed order)
+        dump_outputs(args.dump_outputs, dict(lastPoint=res["lastPoint"], death_step=res["death_step"]),
+                     dict(attempted=res["attempted"]), rank)
+    res = None
     print_prof_counters()
     kms = [a.elapsed_time(b) for (a, b) in timing]
     avg_kernel_s = (sum(kms) / len(kms)) / 1e3
@@ -912,15 +975,16 @@ def main_chain(args, mesh, dev, world, rank):
                           avg_kernel_s, psteps_per_launch, B,
                           f"{mesh_class.lower()}_chain{args.config}_{args.method}_{args.particles}_{key_tail}")
     # the north star's integrator (and the reference caller's default, MOPSPathline.run(method="rk4"),
-    # tutorial/pyMOPSAPI.py:1396) on the same chain, timed after the Euler line (N = 1; not part of value)
+    # tutorial/pyMOPSAPI.py:1396) on the same chain, timed after the Euler line (--full, N = 1; not part of value)
     rk4 = deliver = None
-    companions = os.environ.get("MOPS_BENCH_NO_RK4") != "1" and os.environ.get("MOPS_BENCH_NO_COMPANIONS") != "1"
+    companions = (args.full and os.environ.get("MOPS_BENCH_NO_RK4") != "1"
+                  and os.environ.get("MOPS_BENCH_NO_COMPANIONS") != "1")
     if world == 1 and args.method == "euler" and args.config == 3 and companions:
         rk4 = chain_rk4_companion(args, chain, seeds_dev, compute, n, n_pad, gaps, B, mesh_class)
     if world == 1 and args.method == "euler" and args.config == 3 and companions and args.deliver == "host":
         deliver = chain_host_delivery(args, chain, seeds_dev, compute, n, n_pad, gaps, elapsed / args.steps)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         seed_cells = dmesh_locate_host(dmesh, seeds, dev)
         if snaps is None:  # configs 4/5: the first pair's snapshots, built on the host for the oracle
             snaps = [synth.make_snapshot(mesh, timestep=t, phase=0.35 * t) for t in range(2)]

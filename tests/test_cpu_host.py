@@ -317,6 +317,41 @@ def test_bench_gpus_n_starts_its_own_ranks(monkeypatch):
     b.check_world(2, 2)  # consistent: no error
 
 
+def test_bench_plain_run_is_lean_and_dumps_a_fixed_sample(tmp_path):
+    """A plain bench run leaves the companions (CPU baseline, RK4, host delivery) to --full, and
+    --dump-outputs writes float64 .npy files of a fixed, seeded particle sample within the 64 MB limit."""
+    import torch
+    b = _bench()
+    a = b.apply_config_defaults(b.parse(["--gpus", "1", "--steps", "4", "--warmup", "2"]))
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (4, 2)
+    a = b.apply_config_defaults(b.parse(["--full", "--dump-outputs", "d"]))
+    assert a.full is True and a.dump_outputs == "d"
+    # config 3's rows (lastPoint + death_step + index) at 1e7 particles: sampled, sorted, repeatable, under the limit
+    idx = b.dump_sample_index(10_000_000, 40)
+    assert np.array_equal(idx, b.dump_sample_index(10_000_000, 40))
+    assert len(idx) < 10_000_000 and len(idx) * 40 <= 64 * 10**6 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(b.dump_sample_index(1000, 40), np.arange(1000))  # everything, where it fits
+    n = 2000
+    last = torch.arange(3 * n, dtype=torch.float64).reshape(n, 3)
+    death = torch.arange(n, dtype=torch.int32) - 1
+    small = b.DUMP_BUDGET_BYTES
+    try:
+        b.DUMP_BUDGET_BYTES = 40 * 500  # force the sampling path on a small case
+        w = b.dump_outputs(str(tmp_path / "o"), dict(lastPoint=last, death_step=death),
+                           dict(attempted=torch.tensor(7, dtype=torch.int64)))
+        want = b.dump_sample_index(n, 40)
+    finally:
+        b.DUMP_BUDGET_BYTES = small
+    assert sorted(w) == ["attempted.npy", "death_step.npy", "lastPoint.npy", "sample_index.npy"]
+    got = {k: np.load(tmp_path / "o" / k) for k in w}
+    assert all(v.dtype == np.float64 for v in got.values())
+    i = got["sample_index.npy"].astype(np.int64)
+    assert len(i) == 500 and np.array_equal(i, want)
+    assert np.array_equal(got["lastPoint.npy"], last.numpy()[i])
+    assert np.array_equal(got["death_step.npy"], death.numpy()[i].astype(np.float64))
+    assert got["attempted.npy"].tolist() == [7.0]
+
+
 def test_build_id_is_stamped_and_checked(engine_lib, tmp_path):
     """libmops_traj.so carries the build id of the sources next to it (mops_build_id), the loader
     refuses a library stamped with another id, and the id tracks every engine source and header."""

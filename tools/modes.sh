@@ -8,6 +8,6 @@ for m in "se:" "sr:--method rk4" "pe:--mode pathline" "pr:--mode pathline --meth
   n=${m%%:*}; a=${m#*:}
   timeout -k 10 240 python3 bench.py --no-cpu-baseline $a > "$out/$n.json" 2> "$out/$n.err" || { echo "$n failed"; exit 1; }
 done
-timeout -k 10 400 python3 bench.py --config 4 --steps 1 --warmup 0 > "$out/c4.json" 2> "$out/c4.err" || { echo "c4 failed"; exit 1; }
-timeout -k 10 400 python3 bench.py --config 5 --steps 1 --warmup 0 > "$out/c5.json" 2> "$out/c5.err" || { echo "c5 failed"; exit 1; }
+timeout -k 10 400 python3 bench.py --full --config 4 --steps 1 --warmup 0 > "$out/c4.json" 2> "$out/c4.err" || { echo "c4 failed"; exit 1; }
+timeout -k 10 400 python3 bench.py --full --config 5 --steps 1 --warmup 0 > "$out/c5.json" 2> "$out/c5.err" || { echo "c5 failed"; exit 1; }
 echo modes ok

@@ -18,6 +18,6 @@ for c in "4:--pairs 2:orrs18to6_chain4_euler_10000000_seg720" "5:--pairs 1:orrs1
   python3 tools/make_traffic.py "$out/c$n" "$key" profiles/pmc_traffic.json || exit 1
 done
 cp profiles/pmc_traffic.json "$out/pmc_traffic.json"
-timeout -k 10 400 python3 bench.py --config 4 --steps 1 --warmup 0 > "$out/c4.json" 2> "$out/c4.err" || { echo "c4 failed"; exit 1; }
-timeout -k 10 400 python3 bench.py --config 5 --steps 1 --warmup 0 > "$out/c5.json" 2> "$out/c5.err" || { echo "c5 failed"; exit 1; }
+timeout -k 10 400 python3 bench.py --full --config 4 --steps 1 --warmup 0 > "$out/c4.json" 2> "$out/c4.err" || { echo "c4 failed"; exit 1; }
+timeout -k 10 400 python3 bench.py --full --config 5 --steps 1 --warmup 0 > "$out/c5.json" 2> "$out/c5.err" || { echo "c5 failed"; exit 1; }
 echo "pmc chain ok"

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 python3 -c "import bench; print(bench.bench_host())" > "$out/host.txt"
 # the counter passes must see only the measured workload's kernels (bench.py's RK4 companion off)
 export MOPS_BENCH_NO_RK4=1
-timeout -k 10 600 python3 bench.py ${BENCH_ARGS:-} > "$out/bench.json" 2> "$out/bench.err" || { echo "bench failed"; exit 1; }
+timeout -k 10 600 python3 bench.py --full ${BENCH_ARGS:-} > "$out/bench.json" 2> "$out/bench.err" || { echo "bench failed"; exit 1; }
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o p -- \
     python3 bench.py --no-cpu-baseline ${BENCH_ARGS:-} > "$out/stats.log" 2>&1 || { echo "stats failed"; exit 1; }
 timeout -k 5 300 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex traj_kernel --output-format csv -d "$out/fetch" -o p -- \
