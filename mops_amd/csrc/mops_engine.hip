@@ -69,48 +69,27 @@ constexpr int kBlock = 256;
 #endif
 constexpr int kTrajBlock = MOPS_TRAJ_BLOCK;
 constexpr int kPairRec = 10;  // doubles per level-pair record (see mops_field::d_pr)
-#ifndef MOPS_PAIR_TEST
-#define MOPS_PAIR_TEST 0  // the walk's pair test (dev::walk; superseded by dev::nbr_stay)
-#endif
-#ifndef MOPS_PAIR_TEST_P
-#define MOPS_PAIR_TEST_P 0  // ... in the pathline kernels
-#endif
-// Compact per-lane LDS (traj_kernel): edge normals for polygon slots 0-5 only (slot 6, used by
-// heptagons alone, is computed in the evaluation: same operands, same bits) and the pair-test
-// radius as a float rounded toward zero (a smaller ball: the test stays conservative) --
-// 11.5 KB per 64-lane block instead of 13 KB.  Fuller LDS measured slower even at the same
-// 12 blocks per CU.
-#ifndef MOPS_LDS_COMPACT
-#define MOPS_LDS_COMPACT 1
-#endif
+// Compact per-lane LDS (traj_kernel): edge normals for the first MOPS_NRM_SLOTS polygon slots only; a later
+// slot's normal is computed in the evaluation (same operands, same bits).  Fuller LDS measured slower even at
+// the same 12 blocks per CU; 7 keeps every slot of a MAXV 7 cell in LDS.
 #ifndef MOPS_NRM_SLOTS
-#define MOPS_NRM_SLOTS 5  // polygon slots whose normals live in LDS (MOPS_LDS_COMPACT; slots 5-6 computed per evaluation)
+#define MOPS_NRM_SLOTS 5  // polygon slots whose normals live in LDS (slots 5-6 computed per evaluation)
 #endif
-constexpr int kNrmSlots(int maxv) { return (MOPS_LDS_COMPACT && maxv > MOPS_NRM_SLOTS) ? MOPS_NRM_SLOTS : maxv; }
-// Level-pair record layout (mops_field::d_pr) in 16-B pieces: piece q (0..4) of the record of layer k1 = k-1
-// and vertex v.  MOPS_PR_PIECES = 1 (round 5): piece-major [L-1][5][V+1] -- piece q of consecutive vertices is
-// contiguous, and vertices are numbered in Morton order at mesh creation (MOPS_VPERM), so the lanes of one
-// gather instruction, which ask for piece q of the records of neighbouring cells' vertices, share 128-B lines:
-// the vector L1 / TD spends a cycle per distinct line of an instruction (tools/membench.hip mb_l1_scatter:
-// 8-16 lines 17 cycles, 32 lines 33, 64 lines 64).  The all-zero record is vertex V of every (layer, piece).
-// 0: record-major, level-major [L-1][V][5] (rounds 2-4) + one all-zero record after the last.
-#ifndef MOPS_PR_PIECES
-#define MOPS_PR_PIECES 0  // measured slower: record-major stays
-#endif
+constexpr int kNrmSlots(int maxv) { return maxv > MOPS_NRM_SLOTS ? MOPS_NRM_SLOTS : maxv; }
 #ifndef MOPS_VPERM
 #define MOPS_VPERM 1  // mesh vertices renumbered internally in the Morton order of their coordinates
 #endif
+// Level-pair record layout (mops_field::d_pr) in 16-B pieces: record-major and level-major, [L-1][V][5] -- the
+// five pieces of the record of layer k1 = k-1 and vertex v are contiguous -- plus one all-zero record after the
+// last.  (The piece-major layout measured slower: DESIGN.md section 3.6.)
 // (all in 16-B piece units; uint32 throughout: mops_mesh_create checks pr_pieces < 2^32)
 __host__ __device__ __forceinline__ uint32_t pr_base(uint32_t k1, uint32_t v, uint32_t V) {  // piece 0
-    return MOPS_PR_PIECES ? k1 * 5u * (V + 1u) + v : (k1 * V + v) * 5u;
+    return (k1 * V + v) * 5u;
 }
-__host__ __device__ __forceinline__ uint32_t pr_qstride(uint32_t V) { return MOPS_PR_PIECES ? V + 1u : 1u; }
 __host__ __device__ __forceinline__ uint32_t pr_zero(uint32_t V, uint32_t L) {  // the all-zero record's piece 0
-    return MOPS_PR_PIECES ? V : (L - 1u) * V * 5u;
+    return (L - 1u) * V * 5u;
 }
-inline uint64_t pr_pieces(int64_t V, int L) {
-    return MOPS_PR_PIECES ? (uint64_t)(L - 1) * 5u * (uint64_t)(V + 1) : ((uint64_t)(L - 1) * (uint64_t)V + 1u) * 5u;
-}
+inline uint64_t pr_pieces(int64_t V, int L) { return ((uint64_t)(L - 1) * (uint64_t)V + 1u) * 5u; }
 
 inline int rec_ints_for(int maxv) { return ((1 + 2 * maxv) + 3) / 4 * 4; }
 
@@ -121,9 +100,6 @@ inline int rec_ints_for(int maxv) { return ((1 + 2 * maxv) + 3) / 4 * 4; }
 // front layer, hinted back layer) loads each group's polygon and records ONCE -- one 16-B piece
 // per lane, the pieces of all groups spread over the wave -- into an LDS tile, and its lanes
 // read them from there (ds_read_b128).  Same doubles, same order: bit-identical results.
-#ifndef MOPS_FUSED_RECORDS
-#define MOPS_FUSED_RECORDS 1  // derivation: vertex values computed inside the record build (field_derive)
-#endif
 #ifndef MOPS_COOP_PE
 #define MOPS_COOP_PE 1
 #endif
@@ -168,22 +144,14 @@ constexpr int kCellNrm = 22;               // doubles per cell of mops_mesh::d_c
 constexpr int kCellNrmPieces = kCellNrm / 2;  // ... as 11 pieces
 constexpr int kTileNrm = (3 * kTileSlots + 1) / 2;  // the tile's normal pieces (7 slots: 11, 6 slots: 9)
 constexpr int kTileRec = (kPairRec / 2) * kTileSlots;  // the slots' level-pair records of one field
-#ifndef MOPS_TILE_E1
-#define MOPS_TILE_E1 0  // the tile also holds each slot's edge vector X_{i+1} - X_i (mops_mesh::d_cedge): the
-                        // Wachspress areas skip its 3 subtractions per slot (the same doubles, computed once per cell)
-#endif
-constexpr int kTileE1 = MOPS_TILE_E1 ? kTileNrm : 0;  // edge-vector pieces (laid out like the normals)
-constexpr int kTileOffNrm = kTilePoly, kTileOffE1 = kTilePoly + kTileNrm, kTileOffRec = kTileOffE1 + kTileE1;
-constexpr int kTilePieces = kTilePoly + kTileNrm + kTileE1 + 2 * kTileRec;  // 95 pieces = 1520 B per group (6 slots: 81)
+constexpr int kTileOffNrm = kTilePoly, kTileOffRec = kTilePoly + kTileNrm;
+constexpr int kTilePieces = kTilePoly + kTileNrm + 2 * kTileRec;  // 95 pieces = 1520 B per group (6 slots: 81)
 constexpr int kTileHdr = 20;               // ints per group header: cell, nv, pad x2, front / back record index x 8
 // Neighbour table (maxEdges <= 7 meshes, mops_mesh::d_nbr): per cell 112 B = 7 x 16 B -- the centre as three
 // doubles, the 7 neighbour offsets q_k - c as floats, then the bitmask of the neighbours the walk considers.
 // dev::nbr_stay answers the walk's "does c stay?" from it, exactly, in 7 VMEM instead of the walk's ~20.
 #ifndef MOPS_NBR_TEST
 #define MOPS_NBR_TEST 1
-#endif
-#ifndef MOPS_NBR_PAIR
-#define MOPS_NBR_PAIR 0  // dev::nbr_stay re-arms the pair test (with MOPS_PAIR_TEST / MOPS_PAIR_TEST_P)
 #endif
 #ifndef MOPS_NBR_RK4
 #define MOPS_NBR_RK4 0  // ... in the RK4 kernels too (measured: 6.64e9 vs 6.95e9 p-steps/s on the config-3 RK4 chain)
@@ -219,7 +187,6 @@ struct mops_mesh {
     // slot j = {poly[j-1] (poly[-1] = poly[nv-1]), B_j = area(poly[j-1], poly[j], poly[j+1])}, zeros past nv
     double4* d_cpoly = nullptr;
     double* d_cnrm = nullptr;    // [C][kCellNrm] IsInMesh edge normals of the rotated polygon slots (maxv 7 meshes)
-    double* d_cedge = nullptr;   // [C][kCellNrm] edge vectors X_{i+1} - X_i of the same slots (MOPS_TILE_E1)
     uint4* d_nbr = nullptr;      // [C][kNbrQ] neighbour table (cell_nbr_kernel, dev::nbr_stay; maxv 7 meshes)
     double* d_rloc2 = nullptr;       // [C] squared hinted-locate radius (locate_radius_kernel)
     double* d_ring = nullptr;        // [C] hinted-locate ring distance (locate_radius_kernel)
@@ -356,20 +323,15 @@ __device__ __forceinline__ double sqrt_core(double x) {
 #ifndef MOPS_FAST_SQRT
 #define MOPS_FAST_SQRT 1
 #endif
-#ifndef MOPS_SQRT_ONESIDED
-#define MOPS_SQRT_ONESIDED 1  // measured: streamline Euler segment 27.0 -> 26.0 ms, RK4 86.5 -> 85.2 ms
-#endif
 __device__ __forceinline__ double xsqrt(double x) {
-#if MOPS_FAST_SQRT && MOPS_SQRT_ONESIDED
+#if MOPS_FAST_SQRT
     // the core result always, the library's only for the rare out-of-range x: a one-sided branch
-    // (fewer exec-mask instructions than if/else)
+    // (fewer exec-mask instructions than if/else; measured: streamline Euler segment 27.0 -> 26.0 ms,
+    // RK4 86.5 -> 85.2 ms)
     double r = sqrt_core(x);
     if (__builtin_expect(!(x >= 0x1p-767 && x < __builtin_huge_val()), 0)) r = sqrt(x);
     return r;
 #else
-#if MOPS_FAST_SQRT
-    if (__builtin_expect(x >= 0x1p-767 && x < __builtin_huge_val(), 1)) return sqrt_core(x);
-#endif
     return sqrt(x);
 #endif
 }
@@ -392,17 +354,10 @@ __device__ __forceinline__ double kconst(unsigned hi, unsigned lo, unsigned salt
 // a * b + k with k an SGPR-pair constant (MOPS_K), as one VOP3 v_fma_f64: the compiler's own
 // choice is v_fmac_f64, whose tied accumulator needs k copied into a VGPR pair first (two
 // v_mov_b32 per Horner step).  Same operation, same rounding.
-#ifndef MOPS_SINCOS_VOP3
-#define MOPS_SINCOS_VOP3 1
-#endif
 __device__ __forceinline__ double fma_k(double a, double b, double k) {
-#if MOPS_SINCOS_VOP3
     double r;
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(k));
     return r;
-#else
-    return __builtin_fma(a, b, k);
-#endif
 }
 
 // sin and cos of |x| < 0.78, bit-identical to the device library's sin(x) / cos(x):
@@ -474,16 +429,9 @@ __device__ __forceinline__ double len3(double x, double y, double z) { return xs
 #endif
 __device__ __forceinline__ void xdiv_norm3(double a0, double a1, double a2, double b, double& q0, double& q1,
                                            double& q2) {
-#ifndef MOPS_DIV3_ONESIDED
-#define MOPS_DIV3_ONESIDED 0
-#endif
 #if MOPS_FAST_DIV3 && !defined(MOPS_ABL_DIV)
     const bool fast = b <= 0x1p300 && fabs(a0) >= 0x1p-700 && fabs(a1) >= 0x1p-700 && fabs(a2) >= 0x1p-700;
-#if MOPS_DIV3_ONESIDED
-    if (true) {  // the fast quotients always; `/` replaces them for the rare operands outside the range
-#else
     if (__builtin_expect(fast, 1)) {
-#endif
         double r = __builtin_amdgcn_rcp(b);
         double e = __builtin_fma(-b, r, 1.0);
         r = __builtin_fma(r, e, r);
@@ -495,9 +443,6 @@ __device__ __forceinline__ void xdiv_norm3(double a0, double a1, double a2, doub
         q1 = __builtin_fma(__builtin_fma(-b, q, a1), r, q);
         q = a2 * r;
         q2 = __builtin_fma(__builtin_fma(-b, q, a2), r, q);
-#if MOPS_DIV3_ONESIDED
-        if (__builtin_expect(!fast, 0)) { q0 = xdiv(a0, b); q1 = xdiv(a1, b); q2 = xdiv(a2, b); }
-#endif
         return;
     }
 #endif
@@ -522,16 +467,13 @@ __device__ __forceinline__ double tri_area(double ax, double ay, double az, doub
     return xsqrt(px * px + py * py + pz * pz) / 2.0;
 }
 
-// Wachspress without the two halvings (round 6, MOPS_WACH_X4): the reference's w_i = B_i / (A_i A_{i+1}) with
+// Wachspress without the two halvings (round 6): the reference's w_i = B_i / (A_i A_{i+1}) with
 // A = R / 2, R = sqrt(|cross|^2).  Halving is exact here, and so is scaling a product by 1/4 before rounding: with
 // mesh vertices at Earth radius (< 2^23 m) every edge difference is a multiple of 2^-30, every cross-product
 // component a multiple of 2^-60, so R is 0 or >= 2^-60 and R_i R_{i+1} is 0 or >= 2^-120 -- far from the
 // subnormal range, and far below overflow.  So fl(A_i A_{i+1}) = fl(R_i R_{i+1}) / 4 and fl(B_i / fl(A_i A_{i+1})) = fl(4 B_i / fl(R_i R_{i+1}))
 // with 4 B_i exact: the same double, inf (R = 0) and NaN included, from 4 B_i stored per cell (cell_poly_kernel,
 // load_cell) and R_i = tri_area_x2: 6 FP64 multiplies fewer per evaluation.
-#ifndef MOPS_WACH_X4
-#define MOPS_WACH_X4 1
-#endif
 __device__ __forceinline__ double tri_area_x2(double ax, double ay, double az, double bx, double by, double bz,
                                               double cx, double cy, double cz) {
     const double e1x = bx - ax, e1y = by - ay, e1z = bz - az;
@@ -541,17 +483,8 @@ __device__ __forceinline__ double tri_area_x2(double ax, double ay, double az, d
     const double pz = e1x * e2y - e1y * e2x;
     return xsqrt(px * px + py * py + pz * pz);
 }
-// ... with the edge vector e1 = b - a given (the same doubles: MOPS_TILE_E1 stores b - a per cell)
-__device__ __forceinline__ double tri_area_x2_e(double ax, double ay, double az, double e1x, double e1y, double e1z,
-                                                double cx, double cy, double cz) {
-    const double e2x = cx - ax, e2y = cy - ay, e2z = cz - az;
-    const double px = e1y * e2z - e1z * e2y;
-    const double py = e1z * e2x - e1x * e2z;
-    const double pz = e1x * e2y - e1y * e2x;
-    return xsqrt(px * px + py * py + pz * pz);
-}
-// the per-cell Wachspress numerator as the weights read it: B_i, or 4 B_i (exact) with MOPS_WACH_X4
-__device__ __forceinline__ double wach_numerator(double B) { return MOPS_WACH_X4 ? 4.0 * B : B; }
+// the per-cell Wachspress numerator as the weights read it: 4 B_i (exact)
+__device__ __forceinline__ double wach_numerator(double B) { return 4.0 * B; }
 
 // TBBKernel::CalcPositionAfterRotation (TBBKernel.h:177-206)
 __device__ __forceinline__ void rotate(unsigned salt, double px, double py, double pz, double ax, double ay, double az, double th,
@@ -563,17 +496,6 @@ __device__ __forceinline__ void rotate(unsigned salt, double px, double py, doub
 #ifndef MOPS_FAST_TRIG
 #define MOPS_FAST_TRIG 1
 #endif
-#ifndef MOPS_TRIG_ONESIDED
-#define MOPS_TRIG_ONESIDED 0
-#endif
-#if MOPS_TRIG_ONESIDED
-    sincos_small(th, s, c, salt);  // always; the library's values replace it for the rare |th| >= 0.78
-    if (!MOPS_FAST_TRIG || __builtin_expect(!(fabs(th) < 0.78), 0)) {
-        const double2 sc = sincos_lib(th);
-        s = sc.x;
-        c = sc.y;
-    }
-#else
     if (MOPS_FAST_TRIG && __builtin_expect(fabs(th) < 0.78, 1)) {
         sincos_small(th, s, c, salt);
     } else {
@@ -581,7 +503,6 @@ __device__ __forceinline__ void rotate(unsigned salt, double px, double py, doub
         s = sc.x;
         c = sc.y;
     }
-#endif
 #endif
     const double al = len3(ax, ay, az);
     if (al <= 1e-12) { rx = px; ry = py; rz = pz; return; }
@@ -624,11 +545,8 @@ __device__ __forceinline__ double dclamp(double v, double lo, double hi) { retur
 #ifndef MOPS_RC_PE_PLAIN
 #define MOPS_RC_PE_PLAIN 0
 #endif
-// modes without the register polygon: read a slot from the per-cell packed polygon (one 32-B
-// {x, y, z, B_j}, mops_mesh::d_cpoly) rather than the vertex array + B_j (1 = packed)
-#ifndef MOPS_CPOLY
-#define MOPS_CPOLY 1
-#endif
+// modes without the register polygon read a slot from the per-cell packed polygon (one 32-B
+// {x, y, z, B_j}, mops_mesh::d_cpoly) rather than the vertex array + B_j
 // ... and (MAXV 7) read it piece-major in the cells' Morton-rank order, mops_mesh::d_cpolyr [14][C]: the lanes of a
 // wave sit in consecutive-rank cells (the particles' locality order), so one polygon-piece gather touches a few
 // 128-B lines instead of one per cell (the TD spends a cycle per line)
@@ -645,7 +563,6 @@ struct Cell {
     double cx, cy, cz;  // "stay" anchor: the cell centre, or the position of the last walk that kept the cell
     double rs2;         // squared stay radius around the anchor (see dev::walk)
     int vid[MAXV];
-    int vlast;          // vid[nv-1]: slot 0 of the rotated polygon
     int V;              // vertex count (index of the all-zero level-pair record is V*(L-1))
     bool rc;            // compile-time constant per kernel (load_cell<MAXV, RC>): which members below are live
     // polygon positions in "rotated" order: x[0] = poly[nv-1], x[j] = poly[j-1] (1 <= j < nv), so
@@ -657,13 +574,9 @@ struct Cell {
     // lds_n: IsInMesh edge normals n_i = X_i x X_{i+1} (slot pairs as in dev::weights), computed
     // by load_cell into this lane's LDS column: component j of slot i at nrm[(3 * i + j) * kTrajBlock]
     double* nrm;
-    // pair test (dev::walk): the bisector of c and its nearest neighbour at the last anchor, valid
-    // in a second, larger ball around it -- {n.x, n.y, n.z, k, rb2} at pr2[j * kTrajBlock] (LDS);
-    // rb2 < 0 = none (load_cell)
-    double* pr2;
-    float* rb2;      // MOPS_LDS_COMPACT: the pair test's rb2 (else pr2[4 * kTrajBlock])
-    const double4* __restrict__ vxyz;   // rc == false: polygon re-read per evaluation (L1-resident)
-    const double4* __restrict__ cpoly;  // rc == false: per-cell rotated polygon + B_i [C][MAXV] (cell_poly_kernel)
+    // rc == false: the polygon is re-read per evaluation (L1-resident) from the per-cell rotated polygon + B_i
+    // [C][MAXV] (cell_poly_kernel)
+    const double4* __restrict__ cpoly;
     const double2* __restrict__ cpolyr;  // MOPS_CPOLY_RANK: the same, piece-major by cell rank [2 MAXV][C]
     const uint32_t* __restrict__ crank;  // mops_mesh::d_cell_rank
     uint32_t rank, C;                    // this cell's rank (load_cell), the cell count
@@ -671,7 +584,7 @@ struct Cell {
 
 // NRMC (the cooperative kernel): the lane's normals, when it keeps them (c.lds_n, a wave-uniform
 // runtime mode there), are copied from the per-cell array mops_mesh::d_cnrm -- the same products
-template <int MAXV, bool RC, bool NRM, bool PT, bool NRMC = false>
+template <int MAXV, bool RC, bool NRM, bool NRMC = false>
 __device__ __forceinline__ void load_cell(Cell<MAXV>& c, int cell, const int* __restrict__ cellrec,
                                           const double4* __restrict__ vxyz, const uint32_t* __restrict__ mono0,
                                           const uint32_t* __restrict__ mono1, const double4* __restrict__ cxyz,
@@ -681,10 +594,6 @@ __device__ __forceinline__ void load_cell(Cell<MAXV>& c, int cell, const int* __
     {
         const double4 q = cxyz[cell];
         c.cx = q.x; c.cy = q.y; c.cz = q.z; c.rs2 = q.w;
-    }
-    if constexpr (PT) {  // no pair test before a walk in c
-        if (MOPS_LDS_COMPACT) *c.rb2 = -1.0f;
-        else c.pr2[4 * kTrajBlock] = -1.0;
     }
     constexpr int REC = ((1 + 2 * MAXV) + 3) / 4 * 4;
     const int* r = cellrec + (int64_t)cell * REC;
@@ -700,12 +609,7 @@ __device__ __forceinline__ void load_cell(Cell<MAXV>& c, int cell, const int* __
     c.rc = RC;
 #pragma unroll
     for (int k = 0; k < MAXV; ++k) c.vid[k] = buf[1 + k];
-    c.vlast = 0;
-#pragma unroll
-    for (int k = 0; k < MAXV; ++k)
-        if (k == nv - 1) c.vlast = c.vid[k];
     if constexpr (!RC) {
-        c.vxyz = vxyz;
         c.cpoly = cpoly;
         if constexpr (MOPS_CPOLY_RANK && MAXV == 7) c.rank = c.crank[cell];
     }
@@ -772,14 +676,9 @@ __device__ __forceinline__ void load_cell(Cell<MAXV>& c, int cell, const int* __
 #ifndef MOPS_HEX
 #define MOPS_HEX 1  // NV = 6 instantiation for all-hexagon waves
 #endif
-// ... and for the level-pair sums: pathline yes (measured -2%, PE/PR); streamline no --
-// without the per-vertex branch its scheduler spills (register-cached polygon), 2.4x slower
-#ifndef MOPS_HEX_PAIRS
-#define MOPS_HEX_PAIRS 0
-#endif
-#ifndef MOPS_HEX_PAIRS_P
-#define MOPS_HEX_PAIRS_P 1
-#endif
+// ... and for the level-pair sums: pathline yes (measured -2%, PE/PR: eval_path passes NV on to layer_eval);
+// streamline no (eval_stream passes 0) -- without the per-vertex branch its scheduler spills (register-cached
+// polygon), 2.4x slower
 template <int NV, int MAXV>
 __device__ __forceinline__ int nverts(const Cell<MAXV>& c) { return NV > 0 ? NV : c.nv; }
 
@@ -800,7 +699,6 @@ __device__ __forceinline__ bool weights(const Cell<MAXV>& c, int L, int V, doubl
             X[j] = c.x[j]; Y[j] = c.y[j]; Z[j] = c.z[j]; BB[j] = c.B[j];
         } else {
             if (j < nv) {
-#if MOPS_CPOLY
                 // one 32-B slot {x, y, z, B_j} of the cell's packed polygon: 2 VMEM instead of 3; in a
                 // cooperative wave (coop, wave-uniform) the same slot from the wave's LDS tile
                 double4 q;
@@ -814,11 +712,6 @@ __device__ __forceinline__ bool weights(const Cell<MAXV>& c, int L, int V, doubl
                     q = c.cpoly[(int64_t)c.id * MAXV + j];
                 }
                 X[j] = q.x; Y[j] = q.y; Z[j] = q.z; BB[j] = q.w;
-#else
-                const double4 q = c.vxyz[j == 0 ? c.vlast : c.vid[(j + MAXV - 1) % MAXV]];
-                X[j] = q.x; Y[j] = q.y; Z[j] = q.z;
-                BB[j] = c.cpoly[(int64_t)c.id * MAXV + j].w;
-#endif
             } else {
                 X[j] = 0.0; Y[j] = 0.0; Z[j] = 0.0; BB[j] = 0.0;
             }
@@ -850,13 +743,7 @@ __device__ __forceinline__ bool weights(const Cell<MAXV>& c, int L, int V, doubl
                 nz = X[i] * by - Y[i] * bx;
             }
             inside = inside & !(nx * px + ny * py + nz * pz < 0.0);  // no short circuit: straight-line code
-            if constexpr (COOP && MOPS_TILE_E1 && MOPS_WACH_X4) {  // the tile's b - a of this slot
-                const double* te = reinterpret_cast<const double*>(tpoly) + 2 * kTileOffE1;
-                w[i] = tri_area_x2_e(X[i], Y[i], Z[i], te[3 * i], te[3 * i + 1], te[3 * i + 2], px, py, pz);
-            } else {
-                w[i] = MOPS_WACH_X4 ? tri_area_x2(X[i], Y[i], Z[i], bx, by, bz, px, py, pz)
-                                    : tri_area(X[i], Y[i], Z[i], bx, by, bz, px, py, pz);
-            }
+            w[i] = tri_area_x2(X[i], Y[i], Z[i], bx, by, bz, px, py, pz);
             if constexpr (NV > 0 && BAR) __builtin_amdgcn_sched_barrier(0);  // one slot at a time (register pressure)
         } else {
             w[i] = 0.0;
@@ -1112,19 +999,8 @@ __device__ __forceinline__ int bracket_mono(const Cell<MAXV>& c, const double* w
 // the same argument at p0 = c.  A walk that changes cell leaves the anchor of
 // the new cell's load_cell.
 //
-// Pair test (MOPS_PAIR_TEST).  Near an edge of c the stay ball is small (g is the gap to the
-// neighbour across that edge), so a particle drifting along the edge walked every few steps --
-// the walk's gathers and their dependent round trips cost ~14% of a config-2 step (measured by
-// running every walk twice).  The walk that keeps c therefore also records, for its anchor p0, the
-// gap g2 of the second-nearest distinct neighbour and the bisector of c and the nearest one, nb1:
-// f(p) = |p - c1|^2 - |p - c|^2 = n.p + k, n = 2 (c - c1), k = |c1|^2 - |c|^2.  Inside the ball
-// |p - p0| < (g2 - 0.01 m) / 2 every neighbour but nb1 stays farther than c by more than rounding
-// (same argument as above), so the reference's argmin is c or nb1; and there d_1 + d_c <= D =
-// 2 rb + d_c(p0) + d_1(p0), so f(p) > 0.01 D means d_1 - d_c > 0.01 m, far above the < 1e-7 m
-// error of a computed distance, i.e. c stays the unique minimum.  The computed f errs by < 1e-13
-// (|c|^2 + |c1|^2 + |p0|^2 + rb^2) (a few hundred ulps of the largest term, over-estimated by
-// ~50x), which is subtracted from k with the 0.01 D margin.  The caller then keeps c without
-// walking; any other outcome walks.  (MOPS_PAIR_TEST, defined with the other build switches.)
+// (Near an edge of c that ball is small; dev::nbr_stay keeps such a particle off the walk.  The pair test
+// that did so before it is described in DESIGN.md sections 4.7 and 4.11.)
 #if defined(MOPS_PROF)
 // Event counters for perf experiments (tools/build_variant.sh -DMOPS_PROF), read back with
 // mops_debug_prof: [0] lane-steps, [1] lane walks, [2] lane cell loads, [3] wave-steps,
@@ -1133,7 +1009,7 @@ __device__ __forceinline__ int bracket_mono(const Cell<MAXV>& c, const double* w
 __device__ unsigned long long g_prof[16];
 #endif
 
-template <int MAXV, bool PAIR>
+template <int MAXV>
 __device__ __forceinline__ int walk(Cell<MAXV>& c, int cell, double x, double y, double z,
                                     const int* __restrict__ cellrec, const double4* __restrict__ cxyz, int C) {
     MOPS_CNT(4, 1);
@@ -1178,42 +1054,16 @@ __device__ __forceinline__ int walk(Cell<MAXV>& c, int cell, double x, double y,
         }
     }
     // c attains the minimum and no neighbour ties it (so every finite s_k > s_c)
-    double s2 = inf;
-    int id1 = -1;  // the nearest neighbour (first of equals)
+    double s2 = inf;  // the nearest neighbour
 #pragma unroll
     for (int k = 0; k < MAXV; ++k)
-        if (ok[k] && s[k] < s2) { s2 = s[k]; id1 = id[k]; }
-    double rb2 = -1.0;
+        if (ok[k] && s[k] < s2) s2 = s[k];
     if (!(s2 < inf)) {
         c.rs2 = inf;  // no neighbour with a finite distance: the walk can only keep c
     } else {
         const double dc = sqrt(sc), d1 = sqrt(s2);
         const double ra = (d1 - dc - 0.01) * 0.5;
         c.rs2 = (ra > 0.0) ? ra * ra * (1.0 - 1e-9) : -1.0;
-        if constexpr (PAIR) {
-            double s3 = inf;  // the second-nearest distinct neighbour
-#pragma unroll
-            for (int k = 0; k < MAXV; ++k)
-                if (ok[k] && id[k] != id1 && s[k] < s3) s3 = s[k];
-            const double rb = (s3 < inf) ? (sqrt(s3) - dc - 0.01) * 0.5 : -1.0;
-            if (ra > 0.0 && rb > ra) {
-                const double4 q1 = cxyz[id1];
-                const double c2 = qc.x * qc.x + qc.y * qc.y + qc.z * qc.z;
-                const double c12 = q1.x * q1.x + q1.y * q1.y + q1.z * q1.z;
-                const double p2 = x * x + y * y + z * z;
-                const double D = 2.0 * rb + dc + d1;
-                const double err = 1e-13 * (c2 + c12 + p2 + rb * rb);
-                c.pr2[0 * kTrajBlock] = 2.0 * (qc.x - q1.x);
-                c.pr2[1 * kTrajBlock] = 2.0 * (qc.y - q1.y);
-                c.pr2[2 * kTrajBlock] = 2.0 * (qc.z - q1.z);
-                c.pr2[3 * kTrajBlock] = (c12 - c2) - 0.01 * D - err;
-                rb2 = rb * rb * (1.0 - 1e-9);
-            }
-        }
-    }
-    if constexpr (PAIR) {
-        if (MOPS_LDS_COMPACT) *c.rb2 = __double2float_rz(rb2);  // <= rb2: a conservative ball
-        else c.pr2[4 * kTrajBlock] = rb2;
     }
     c.cx = x; c.cy = y; c.cz = z;
     return cell;
@@ -1229,7 +1079,7 @@ __device__ __forceinline__ int walk(Cell<MAXV>& c, int cell, double x, double y,
 // r = min_k (g_k - M_k) / (2 |d_k|) of p keeps the same margin (f_k moves by <= 2 |d_k| |p' - p|), so the
 // test also re-centres the stay ball on p with that radius.  Any other outcome (a bisector within the
 // margin, a crossing, a non-finite p) returns false and the caller walks as before.
-template <int MAXV, bool PT>
+template <int MAXV>
 __device__ __forceinline__ bool nbr_stay(Cell<MAXV>& c, int cell, double x, double y, double z,
                                          const uint4* __restrict__ nbr) {
     const uint4* t = nbr + (int64_t)cell * kNbrQ;
@@ -1247,7 +1097,6 @@ __device__ __forceinline__ bool nbr_stay(Cell<MAXV>& c, int cell, double x, doub
     const uint32_t mask = w[27];
     bool ok = true;
     float r = __builtin_huge_valf();
-    float r2 = __builtin_huge_valf(), n1x = 0.0f, n1y = 0.0f, n1z = 0.0f, h1 = 0.0f;  // MOPS_NBR_PAIR
 #pragma unroll
     for (int k = 0; k < 7; ++k) {
         if ((mask >> k) & 1u) {
@@ -1258,11 +1107,6 @@ __device__ __forceinline__ bool nbr_stay(Cell<MAXV>& c, int cell, double x, doub
             const float M = 0x1p-17f * (h + e2);
             ok = ok & (g > M);  // (false for NaN / inf operands)
             const float rk = (g - M) * (0.5f * __builtin_amdgcn_rsqf(h));
-            if constexpr (PT && MOPS_NBR_PAIR) {  // the nearest bisector and the second-nearest distance
-                const bool nearer = rk < r;
-                r2 = nearer ? r : fminf(r2, rk);
-                n1x = nearer ? dx : n1x; n1y = nearer ? dy : n1y; n1z = nearer ? dz : n1z; h1 = nearer ? h : h1;
-            }
             r = fminf(r, rk);
         }
     }
@@ -1270,27 +1114,6 @@ __device__ __forceinline__ bool nbr_stay(Cell<MAXV>& c, int cell, double x, doub
     const double rr = (double)(r * (1.0f - 0x1p-16f));  // (rsq, the products: < 2^-20 relative)
     c.cx = x; c.cy = y; c.cz = z;
     c.rs2 = rr * rr * (1.0 - 1e-9);  // (inf when no neighbour is considered: the walk can only keep c)
-    if constexpr (PT) {
-        // The pair test's ball is centred on the anchor, which just moved.  MOPS_NBR_PAIR: re-arm it from the
-        // table -- inside the ball of the second-nearest bisector's radius r2 only the nearest one, k1, can be
-        // crossed, and f_k1(p') = h1 - 2 d1.(p' - c) = n.p' + k with n = -2 d1, k = h1 + 2 d1.c (DESIGN.md
-        // section 4.11; the float offsets' error over that ball is below M' / 32)
-        float rb2 = -1.0f;
-        if constexpr (MOPS_NBR_PAIR) {
-            if (r2 > r) {
-                const double rr2 = fmin((double)(r2 * (1.0f - 0x1p-16f)), sqrt((double)h1));
-                const double Mp = 0x1p-16 * ((double)h1 + 2.0 * (double)e2 * 1.01 + 2.0 * rr2 * rr2);
-                const double dx = n1x, dy = n1y, dz = n1z;
-                c.pr2[0 * kTrajBlock] = -2.0 * dx;
-                c.pr2[1 * kTrajBlock] = -2.0 * dy;
-                c.pr2[2 * kTrajBlock] = -2.0 * dz;
-                c.pr2[3 * kTrajBlock] = ((double)h1 + 2.0 * (dx * cx + dy * cy + dz * cz)) - Mp;
-                rb2 = __double2float_rz(rr2 * rr2 * (1.0 - 1e-9));
-            }
-        }
-        if (MOPS_LDS_COMPACT) *c.rb2 = rb2;
-        else c.pr2[4 * kTrajBlock] = rb2;
-    }
     return true;
 }
 
@@ -1357,9 +1180,6 @@ struct Pair {
 // +0.0 and only adds products is never -0.0 (x + -x = +0 under
 // round-to-nearest) and S + +0.0 == S otherwise (NaN, inf included), so
 // every sum keeps the bits of the reference's nv-term loop.
-#ifndef MOPS_PAIR_BARRIER
-#define MOPS_PAIR_BARRIER 1
-#endif
 #ifndef MOPS_SCHED_BAR_PR
 #define MOPS_SCHED_BAR_PR 1  // the tiled RK4 pathline evaluation keeps the per-slot / per-group scheduling barriers
 #endif
@@ -1373,7 +1193,7 @@ __device__ __forceinline__ void pair_sums(const Cell<MAXV>& c, const double* w, 
     S.zm = S.zk = S.wm = S.wk = 0.0;
     S.um0 = S.um1 = S.um2 = S.uk0 = S.uk1 = S.uk2 = 0.0;
     // 32-bit piece indices (mops_mesh_create: pr_pieces < 2^32)
-    const uint32_t zrec = pr_zero((uint32_t)c.V, (uint32_t)L), qs = pr_qstride((uint32_t)c.V);
+    const uint32_t zrec = pr_zero((uint32_t)c.V, (uint32_t)L);
     // tile reads (LDS latency) need fewer records in flight than gathers
     constexpr int GR_ = COOP ? MOPS_GR_COOP : GR;
 #pragma unroll
@@ -1393,11 +1213,11 @@ __device__ __forceinline__ void pair_sums(const Cell<MAXV>& c, const double* w, 
 #pragma unroll
                     for (int q = 0; q < kPairRec / 2; ++q) a[j][q] = trec[(kPairRec / 2) * v + q];
                 } else {
-                    // (a 64-bit base, then the pieces at q * qs: with record-major records (qs = 1) the five loads
-                    // share one address and take immediate offsets)
+                    // (a 64-bit base, then the record's contiguous pieces: the five loads share one address and
+                    // take immediate offsets)
                     const double2* r = reinterpret_cast<const double2*>(pr) + ri;
 #pragma unroll
-                    for (int q = 0; q < kPairRec / 2; ++q) a[j][q] = r[(size_t)q * qs];
+                    for (int q = 0; q < kPairRec / 2; ++q) a[j][q] = r[q];
                 }
             }
 #pragma unroll
@@ -1412,7 +1232,7 @@ __device__ __forceinline__ void pair_sums(const Cell<MAXV>& c, const double* w, 
             }
             // NV > 0 has no per-group branch: keep the groups apart, or the
             // scheduler puts every record in flight at once and spills
-            if constexpr ((NV > 0 || COOP) && MOPS_PAIR_BARRIER && BAR) __builtin_amdgcn_sched_barrier(0);
+            if constexpr ((NV > 0 || COOP) && BAR) __builtin_amdgcn_sched_barrier(0);
         }
     }
     MOPS_MARK(310 + NV);
@@ -1489,8 +1309,8 @@ __device__ __forceinline__ bool eval_stream(const Cell<MAXV>& c, int L, int V, c
     if (!weights<MAXV, NV>(c, L, V, px, py, pz, w)) return false;
     Pair S;
     MOPS_MARK(410 + NV);
-    const int layer = layer_eval<MAXV, false, GR, MOPS_HEX_PAIRS ? NV : 0>(c, w, fast_ok<MAXV, NV>(c, c.mono0, weights_finite<MAXV, NV>(c, w), w), f,
-                                                  L, d, hint, S);
+    const int layer = layer_eval<MAXV, false, GR, 0>(c, w, fast_ok<MAXV, NV>(c, c.mono0, weights_finite<MAXV, NV>(c, w), w), f,
+                                                     L, d, hint, S);
     MOPS_MARK(420 + NV);
     if (layer < 0) return false;
     const double zdn = S.zk, zup = S.zm;
@@ -1523,9 +1343,9 @@ __device__ __forceinline__ bool eval_path(const Cell<MAXV>& c, int L, int V, con
     if (!weights<MAXV, NV, COOP, kBar>(c, L, V, px, py, pz, w, reinterpret_cast<const double4*>(tile))) return false;
     const bool wfin = weights_finite<MAXV, NV>(c, w);
     Pair F, B;
-    const int lf = layer_eval<MAXV, true, GR, MOPS_HEX_PAIRS_P ? NV : 0, COOP, TCHK>(
+    const int lf = layer_eval<MAXV, true, GR, NV, COOP, TCHK>(
         c, w, fast_ok<MAXV, NV>(c, c.mono0, wfin, w), ff, L, d, hint0, F, tile + kTileOffRec, th0);
-    const int lb = layer_eval<MAXV, true, GR, MOPS_HEX_PAIRS_P ? NV : 0, COOP, TCHK>(
+    const int lb = layer_eval<MAXV, true, GR, NV, COOP, TCHK>(
         c, w, fast_ok<MAXV, NV>(c, c.mono1, wfin, w), fb, L, d, hint1, B, tile + kTileOffRec + kTileRec, th1);
     if (lf < 0 || lb < 0) return false;
     const double xf = dmax(F.zk, dmin(d, F.zm));
@@ -1604,7 +1424,8 @@ struct TrajArgs {
     const int* __restrict__ n_live;  // device count of leading live slots (compaction), NULL = all n
     const double4* __restrict__ cpoly;  // per-cell rotated polygon + Wachspress B_i (mops_mesh::d_cpoly)
     const double* __restrict__ cnrm;    // per-cell edge normals (mops_mesh::d_cnrm; NULL past maxEdges 7)
-    const double* __restrict__ cedge;   // per-cell edge vectors (mops_mesh::d_cedge; MOPS_TILE_E1 only)
+    const double* __restrict__ cedge;   // unused, always NULL: kept so that the kernel-argument offsets of the
+                                        // fields below, and with them the device code, stay as measured
     const uint4* __restrict__ nbr;      // per-cell neighbour table (mops_mesh::d_nbr; NULL past maxEdges 7)
     const double2* __restrict__ cpolyr;  // mops_mesh::d_cpolyr (NULL past maxEdges 7)
     const uint32_t* __restrict__ crank;  // mops_mesh::d_cell_rank
@@ -1629,8 +1450,7 @@ struct TrajArgs {
 // edge normals, the front field's records, the back field's -- from the group headers hdi into s_tile[i]
 template <int MAXV>
 __device__ __forceinline__ void tile_piece(int i, const uint32_t* hdi, const double2* cpoly2, const double2* cnrm2,
-                                           const double2* cedge2, const double2* pr0, const double2* pr1, uint32_t V,
-                                           double2* s_tile) {
+                                           const double2* pr0, const double2* pr1, double2* s_tile) {
     const int gg = i / kTilePieces, pc = i - gg * kTilePieces;
     const uint32_t cl = hdi[gg * kTileHdr];
     const bool isp = pc < kTileOffNrm, isn = pc < kTileOffRec;
@@ -1638,12 +1458,10 @@ __device__ __forceinline__ void tile_piece(int i, const uint32_t* hdi, const dou
     const int pp = isn ? 0 : pc - (f1 ? kTileOffRec + kTileRec : kTileOffRec);
     const int v = pp / (kPairRec / 2), q = pp - (kPairRec / 2) * v;
     const uint32_t ri = hdi[gg * kTileHdr + 4 + (f1 ? 8 : 0) + v];
-    const bool ise = MOPS_TILE_E1 && pc >= kTileOffE1;  // (with isn: an edge-vector piece)
-    const double2* base = isp ? cpoly2 : (isn ? (ise ? cedge2 : cnrm2) : (f1 ? pr1 : pr0));
+    const double2* base = isp ? cpoly2 : (isn ? cnrm2 : (f1 ? pr1 : pr0));
     const uint64_t idx = isp ? ((uint64_t)cl * MAXV + (uint32_t)(pc >> 1)) * 2 + (uint32_t)(pc & 1)
-                             : (isn ? (uint64_t)cl * kCellNrmPieces +
-                                          (uint32_t)(pc - (ise ? kTileOffE1 : kTileOffNrm))
-                                    : (uint64_t)(ri + (uint32_t)q * pr_qstride(V)));
+                             : (isn ? (uint64_t)cl * kCellNrmPieces + (uint32_t)(pc - kTileOffNrm)
+                                    : (uint64_t)(ri + (uint32_t)q));
     s_tile[i] = base[idx];
 }
 
@@ -1660,22 +1478,6 @@ __device__ __forceinline__ void tile_piece(int i, const uint32_t* hdi, const dou
 #endif
 #ifndef MOPS_W_PR
 #define MOPS_W_PR 2  // pathline RK4
-#endif
-#ifndef MOPS_RK4_LOOP
-#define MOPS_RK4_LOOP 0  // 1: RK4 stages as a loop around one inlined evaluation (4x less code, but 220-240 spilled
-                         // VGPRs: pathline RK4 5.34e9 vs 6.97e9, streamline RK4 3.5e9 vs 6.9e9 p-steps/s, measured)
-#endif
-#ifndef MOPS_RK4_ACC
-#define MOPS_RK4_ACC 1  // RK4 stage velocities accumulated as they come (see traj_kernel)
-#endif
-#ifndef MOPS_RK4_FENCE
-#define MOPS_RK4_FENCE 0  // a compiler memory barrier between RK4 stages: each stage re-reads the cell's polygon,
-                          // normals and tile records instead of keeping stage 1's loads live across the step
-#endif
-#if MOPS_RK4_FENCE
-#define MOPS_STAGE_FENCE() asm volatile("" ::: "memory")
-#else
-#define MOPS_STAGE_FENCE() do { } while (0)
 #endif
 #ifndef MOPS_GR_E
 #define MOPS_GR_E 1  // level-pair records in flight per round trip, Euler
@@ -1823,8 +1625,7 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
     // config 4, keeps the polygon in registers: 12 fewer VMEM per evaluation for a TD-bound launch)
     constexpr bool kRC = RCache<MAXV, PATH, EULER>::value || (MOPS_RC_PE_PLAIN && PATH && EULER && !COOP && MAXV <= 7),
                    kNrm = LdsNormals<MAXV, PATH, EULER>::value && (MOPS_NRM_PE_PLAIN || COOP || !PATH || !EULER);
-    constexpr bool kCoop = COOP && PATH && MAXV == 7 && !kRC && kNrm && MOPS_CPOLY &&
-                           (EULER ? MOPS_COOP_PE : MOPS_COOP_PR);
+    constexpr bool kCoop = COOP && PATH && MAXV == 7 && !kRC && kNrm && (EULER ? MOPS_COOP_PE : MOPS_COOP_PR);
     // the tile and its headers are per block, and the group/header hand-offs between lanes rely on one
     // wave's LDS operations running in order: one wave per block
     static_assert(!kCoop || kTrajBlock == 64, "the cooperative tile needs one wave per block");
@@ -1840,11 +1641,6 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
     __shared__ __attribute__((aligned(16))) double s_nrm[kNrm ? (kCoop && kTileD > kNrmD ? kTileD : kNrmD) : 1];
     c.nrm = s_nrm + threadIdx.x;
     c.lds_n = kNrm && !kCoop;  // (the cooperative kernel starts in tile mode)
-    constexpr bool kPairT = (kNrm || kCoop) && (PATH ? MOPS_PAIR_TEST_P : MOPS_PAIR_TEST);  // (load_cell resets it)
-    __shared__ double s_pr2[kPairT ? (MOPS_LDS_COMPACT ? 4 : 5) * kTrajBlock : 1];  // per-lane pair test (Cell::pr2, dev::walk)
-    __shared__ float s_rb2[kPairT && MOPS_LDS_COMPACT ? kTrajBlock : 1];
-    c.pr2 = s_pr2 + threadIdx.x;
-    c.rb2 = s_rb2 + (kPairT && MOPS_LDS_COMPACT ? threadIdx.x : 0);
     double2* s_tile = reinterpret_cast<double2*>(s_nrm);
     __shared__ uint4 s_hdr[kCoop ? kG * (kTileHdr / 4) : 1];
     const int C = a.C;
@@ -1864,7 +1660,7 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
         if constexpr (HAND) cell_in = cell;  // (the walk restarts from it at a hand-off)
         if (step == 0) {  // first_loop (:892-901)
             if (cell < 0 || cell >= C) { died = 0; break; }
-            dev::load_cell<MAXV, kRC, kNrm, kPairT, kCoop>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly, a.cnrm);
+            dev::load_cell<MAXV, kRC, kNrm, kCoop>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly, a.cnrm);
             double* r0 = a.rec;
             r0[0 * a.rec_stride + pid] = x;
             r0[1 * a.rec_stride + pid] = y;
@@ -1875,7 +1671,7 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
             rec0 = true;
         } else {  // one-hop nearest-centre walk (:902-922)
             if (cell < 0 || cell >= C) { died = (int)step; break; }
-            if (c.id != cell) dev::load_cell<MAXV, kRC, kNrm, kPairT, kCoop>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly, a.cnrm);
+            if (c.id != cell) dev::load_cell<MAXV, kRC, kNrm, kCoop>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly, a.cnrm);
             // Exact shortcut: inside the stay ball around the anchor every
             // neighbour is strictly farther than c by more than rounding, so
             // the reference's argmin (c listed last, strict <) keeps c (dev::walk).
@@ -1883,13 +1679,8 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
 #if defined(MOPS_PROF)
             const double e2p = ex * ex + ey * ey + ez * ez;
             bool stay_p = e2p < c.rs2;
-            if constexpr (kPairT) {
-                if (!stay_p && e2p < (MOPS_LDS_COMPACT ? (double)*c.rb2 : c.pr2[4 * kTrajBlock]))
-                    stay_p = c.pr2[0] * x + c.pr2[kTrajBlock] * y + c.pr2[2 * kTrajBlock] * z +
-                             c.pr2[3 * kTrajBlock] > 0.0;
-            }
             if constexpr (kNbrT) {
-                if (!stay_p && dev::nbr_stay<MAXV, kPairT>(c, cell, x, y, z, a.nbr)) {
+                if (!stay_p && dev::nbr_stay<MAXV>(c, cell, x, y, z, a.nbr)) {
                     stay_p = true;
                     atomicAdd(&dev::g_prof[13], 1ull);  // lane-steps the neighbour table kept in c
                 }
@@ -1897,9 +1688,9 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
             const bool walking = !stay_p;
             bool loading = false;
             if (walking) {
-                cell = dev::walk<MAXV, kPairT>(c, cell, x, y, z, a.cellrec, a.cxyz, C);
+                cell = dev::walk<MAXV>(c, cell, x, y, z, a.cellrec, a.cxyz, C);
                 loading = c.id != cell;
-                if (c.id != cell) dev::load_cell<MAXV, kRC, kNrm, kPairT, kCoop>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly, a.cnrm);
+                if (c.id != cell) dev::load_cell<MAXV, kRC, kNrm, kCoop>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly, a.cnrm);
             }
             {
                 const unsigned long long bw = __ballot(walking), bl = __ballot(loading), ba = __ballot(1);
@@ -1915,13 +1706,8 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
 #else
             const double e2 = ex * ex + ey * ey + ez * ez;
             bool stay = e2 < c.rs2;
-            if constexpr (kPairT) {
-                if (!stay && e2 < (MOPS_LDS_COMPACT ? (double)*c.rb2 : c.pr2[4 * kTrajBlock]))  // second ball: only nb1 competes (dev::walk)
-                    stay = c.pr2[0] * x + c.pr2[kTrajBlock] * y + c.pr2[2 * kTrajBlock] * z +
-                           c.pr2[3 * kTrajBlock] > 0.0;
-            }
             if constexpr (kNbrT) {
-                if (!stay) stay = dev::nbr_stay<MAXV, kPairT>(c, cell, x, y, z, a.nbr);  // exact: every bisector clear
+                if (!stay) stay = dev::nbr_stay<MAXV>(c, cell, x, y, z, a.nbr);  // exact: every bisector clear
             }
 #if defined(MOPS_ABL_NOWALK)  // ablation: never walk (wrong results; the walks' cost bound)
             if (false) {
@@ -1932,12 +1718,12 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
                 {
                     double xo = x;
                     asm volatile("" : "+v"(xo));
-                    cell = dev::walk<MAXV, kPairT>(c, cell, xo, y, z, a.cellrec, a.cxyz, C);
+                    cell = dev::walk<MAXV>(c, cell, xo, y, z, a.cellrec, a.cxyz, C);
                 }
 #endif
-                cell = dev::walk<MAXV, kPairT>(c, cell, x, y, z, a.cellrec, a.cxyz, C);
+                cell = dev::walk<MAXV>(c, cell, x, y, z, a.cellrec, a.cxyz, C);
                 if (c.id != cell) MOPS_CNT(5, 1);
-                if (c.id != cell) dev::load_cell<MAXV, kRC, kNrm, kPairT, kCoop>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly, a.cnrm);
+                if (c.id != cell) dev::load_cell<MAXV, kRC, kNrm, kCoop>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly, a.cnrm);
             }
 #endif
         }
@@ -2031,7 +1817,6 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
                     const uint32_t* hdi = reinterpret_cast<const uint32_t*>(s_hdr);
                     const double2* cpoly2 = reinterpret_cast<const double2*>(a.cpoly);
                     const double2* cnrm2 = reinterpret_cast<const double2*>(a.cnrm);
-                    const double2* cedge2 = reinterpret_cast<const double2*>(a.cedge);
                     const double2* pr0 = reinterpret_cast<const double2*>(a.f0.pr);
                     const double2* pr1 = reinterpret_cast<const double2*>(a.f1.pr);
                     // this lane's rank among the live lanes
@@ -2040,11 +1825,11 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
     #pragma unroll
                     for (int rr = 0; rr < kR; ++rr) {
                         const int i = rank + nact * rr;
-                        if (i < np) tile_piece<MAXV>(i, hdi, cpoly2, cnrm2, cedge2, pr0, pr1, (uint32_t)a.V, s_tile);
+                        if (i < np) tile_piece<MAXV>(i, hdi, cpoly2, cnrm2, pr0, pr1, s_tile);
                     }
                     if constexpr (kFillAll) {
                         for (int i = rank + nact * kR; i < np; i += nact)
-                            tile_piece<MAXV>(i, hdi, cpoly2, cnrm2, cedge2, pr0, pr1, (uint32_t)a.V, s_tile);
+                            tile_piece<MAXV>(i, hdi, cpoly2, cnrm2, pr0, pr1, s_tile);
                     }
                     dev::wave_lds_sync();
                     c.lds_n = false;  // (the tile overwrote the lane normals)
@@ -2098,35 +1883,10 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
             // the tile's layers per field (cooperative waves; see layer_eval)
             const int th0 = (tkey >> 16) - 1, th1 = ((tkey >> 8) & 0xff) - 1;
             constexpr int GR = PairGroup<PATH, EULER>::value;
-#if MOPS_RK4_LOOP
-            // The four stages as one loop around a single inlined evaluation (the unrolled form inlines
-            // four copies of every eval_path instantiation: ~90k instructions in the cooperative RK4
-            // kernel).  The sums keep the reference's association, ((s1 + 2 s2) + 2 s3) + s4 (:959-960).
-            const double a2 = PATH ? dev::dclamp(a1 + 0.5 * a.dalpha, 0.0, 1.0) : 0.0;
-            const double a4 = PATH ? dev::dclamp(a1 + a.dalpha, 0.0, 1.0) : 0.0;
-            double qx = x, qy = y, qz = z;
-            bool ok = true;
-#pragma nounroll
-            for (int stg = 0; stg < 4; ++stg) {
-                double sx, sy, sz, sw;
-                const double as = stg == 0 ? a1 : (stg == 3 ? a4 : a2);
-                ok = dev::eval_at<MAXV, PATH, GR, true, HAND>(hex, c, a.L, a.V, a.f0, a.f1, qx, qy, qz, d, as, hint0, hint1,
-                                                        sx, sy, sz, sw, coop, tile, th0, th1);
-                if (!ok) break;
-                if (stg == 0) {
-                    hx = sx; hy = sy; hz = sz; wv = sw;
-                } else if (stg == 3) {
-                    hx = hx + sx; hy = hy + sy; hz = hz + sz; wv = wv + sw;
-                } else {
-                    hx = hx + sx * 2.0; hy = hy + sy * 2.0; hz = hz + sz * 2.0; wv = wv + 2.0 * sw;
-                }
-                if (stg < 3) dev::advect((unsigned)step, x, y, z, sx, sy, sz, stg == 2 ? dt : dt * 0.5, qx, qy, qz);
-            }
-            if (!ok) { died = (int)step; break; }
-            hx = hx / 6.0; hy = hy / 6.0; hz = hz / 6.0; wv = wv / 6.0;
-#elif MOPS_RK4_ACC
-            // The stage velocities summed as they come, in the reference's association ((s1 + 2 s2) + 2 s3) + s4
-            // (:959-960): the same operations as the sum at the end, without s1..s3 live across the stages
+            // The four stages unrolled (one loop around a single inlined evaluation spilled 220-240 VGPRs, DESIGN.md
+            // section 3.6), the stage velocities summed as they come, in the reference's association
+            // ((s1 + 2 s2) + 2 s3) + s4 (:959-960): the same operations as a sum at the end, without s1..s3 live
+            // across the stages
             double sx, sy, sz, sw, qx, qy, qz;
             bool ok = dev::eval_at<MAXV, PATH, GR, true, HAND>(hex, c, a.L, a.V, a.f0, a.f1, x, y, z, d, a1, hint0, hint1,
                                                         sx, sy, sz, sw, coop, tile, th0, th1);
@@ -2134,50 +1894,21 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
             hx = sx; hy = sy; hz = sz; wv = sw;
             dev::advect((unsigned)step, x, y, z, sx, sy, sz, dt * 0.5, qx, qy, qz);
             const double a2 = PATH ? dev::dclamp(a1 + 0.5 * a.dalpha, 0.0, 1.0) : 0.0;
-            MOPS_STAGE_FENCE();
             ok = dev::eval_at<MAXV, PATH, GR, true, HAND>(hex, c, a.L, a.V, a.f0, a.f1, qx, qy, qz, d, a2, hint0, hint1, sx, sy,
                                                    sz, sw, coop, tile, th0, th1);
             if (!ok) { died = (int)step; break; }
             hx = hx + sx * 2.0; hy = hy + sy * 2.0; hz = hz + sz * 2.0; wv = wv + 2.0 * sw;
             dev::advect((unsigned)step, x, y, z, sx, sy, sz, dt * 0.5, qx, qy, qz);
-            MOPS_STAGE_FENCE();
             ok = dev::eval_at<MAXV, PATH, GR, true, HAND>(hex, c, a.L, a.V, a.f0, a.f1, qx, qy, qz, d, a2, hint0, hint1, sx, sy,
                                                    sz, sw, coop, tile, th0, th1);
             if (!ok) { died = (int)step; break; }
             hx = hx + sx * 2.0; hy = hy + sy * 2.0; hz = hz + sz * 2.0; wv = wv + 2.0 * sw;
             dev::advect((unsigned)step, x, y, z, sx, sy, sz, dt, qx, qy, qz);
             const double a4 = PATH ? dev::dclamp(a1 + a.dalpha, 0.0, 1.0) : 0.0;
-            MOPS_STAGE_FENCE();
             ok = dev::eval_at<MAXV, PATH, GR, true, HAND>(hex, c, a.L, a.V, a.f0, a.f1, qx, qy, qz, d, a4, hint0, hint1, sx, sy,
                                                    sz, sw, coop, tile, th0, th1);
             if (!ok) { died = (int)step; break; }
             hx = (hx + sx) / 6.0; hy = (hy + sy) / 6.0; hz = (hz + sz) / 6.0; wv = (wv + sw) / 6.0;
-#else
-            double s1x, s1y, s1z, s1w, s2x, s2y, s2z, s2w, s3x, s3y, s3z, s3w, s4x, s4y, s4z, s4w;
-            double qx, qy, qz;
-            bool ok = dev::eval_at<MAXV, PATH, GR, true, HAND>(hex, c, a.L, a.V, a.f0, a.f1, x, y, z, d, a1, hint0, hint1,
-                                                        s1x, s1y, s1z, s1w, coop, tile, th0, th1);
-            if (!ok) { died = (int)step; break; }
-            dev::advect((unsigned)step, x, y, z, s1x, s1y, s1z, dt * 0.5, qx, qy, qz);
-            const double a2 = PATH ? dev::dclamp(a1 + 0.5 * a.dalpha, 0.0, 1.0) : 0.0;
-            ok = dev::eval_at<MAXV, PATH, GR, true, HAND>(hex, c, a.L, a.V, a.f0, a.f1, qx, qy, qz, d, a2, hint0, hint1, s2x,
-                                                   s2y, s2z, s2w, coop, tile, th0, th1);
-            if (!ok) { died = (int)step; break; }
-            dev::advect((unsigned)step, x, y, z, s2x, s2y, s2z, dt * 0.5, qx, qy, qz);
-            ok = dev::eval_at<MAXV, PATH, GR, true, HAND>(hex, c, a.L, a.V, a.f0, a.f1, qx, qy, qz, d, a2, hint0, hint1, s3x,
-                                                   s3y, s3z, s3w, coop, tile, th0, th1);
-            if (!ok) { died = (int)step; break; }
-            dev::advect((unsigned)step, x, y, z, s3x, s3y, s3z, dt, qx, qy, qz);
-            const double a4 = PATH ? dev::dclamp(a1 + a.dalpha, 0.0, 1.0) : 0.0;
-            ok = dev::eval_at<MAXV, PATH, GR, true, HAND>(hex, c, a.L, a.V, a.f0, a.f1, qx, qy, qz, d, a4, hint0, hint1, s4x,
-                                                   s4y, s4z, s4w, coop, tile, th0, th1);
-            if (!ok) { died = (int)step; break; }
-            // (s1 + 2 s2 + 2 s3 + s4) / 6 -- cy::Vec3 operator order (:959-960)
-            hx = (((s1x + s2x * 2.0) + s3x * 2.0) + s4x) / 6.0;
-            hy = (((s1y + s2y * 2.0) + s3y * 2.0) + s4y) / 6.0;
-            hz = (((s1z + s2z * 2.0) + s3z * 2.0) + s4z) / 6.0;
-            wv = (s1w + 2.0 * s2w + 2.0 * s3w + s4w) / 6.0;
-#endif
             const double tx = x + hx * dt, ty = y + hy * dt, tz = z + hz * dt;
             const double tl = dev::len3(tx, ty, tz);
             if (tl > 1e-12) {
@@ -2252,9 +1983,9 @@ __global__ void selftest_walk_kernel(int64_t n, const double* __restrict__ pts, 
     dev::Cell<7> c;
     c.nv = cellrec[(int64_t)cell * (((1 + 2 * 7) + 3) / 4 * 4)];
     c.rs2 = 0.0;
-    const bool a = dev::nbr_stay<7, false>(c, cell, x, y, z, nbr);
+    const bool a = dev::nbr_stay<7>(c, cell, x, y, z, nbr);
     const double rad = a ? sqrt(c.rs2) : 0.0;
-    const bool b = dev::walk<7, false>(c, cell, x, y, z, cellrec, cxyz, C) == cell;
+    const bool b = dev::walk<7>(c, cell, x, y, z, cellrec, cxyz, C) == cell;
     const int rq = (int)fmin(rad, 4.0e6);  // (< 2^22)
     out[i] = (a ? 1 : 0) | (b ? 2 : 0) | (rq << 8);
 }
@@ -2413,19 +2144,12 @@ __global__ void __launch_bounds__(256) assemble_kernel(int64_t n, int64_t K, con
 // once, with consecutive threads on consecutive doubles of a line (whole 600-B point runs at K =
 // 24 instead of 192-B chunks), saving remove_nan_kernel's second, strided pass over the lines.
 constexpr int kAsmFull = 24;
-#ifndef MOPS_ASM_V2
 // 16-B record reads (even stride, full blocks) and streaming (non-temporal) line stores: config 3's per-pair
 // assembly 9.71 -> 8.46 ms, its 7-pair chain 3620 -> 3610 ms (3 interleaved rounds,
 // profiles/r05/ab/assembly_v2.txt)
-#define MOPS_ASM_V2 1
-#endif
 template <typename T>
 __device__ __forceinline__ void asm_store(T* p, T v) {
-#if MOPS_ASM_V2
     __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 }
 __global__ void __launch_bounds__(256) assemble_clean_kernel(int64_t n, int K, const double* __restrict__ seeds,
                                                              const double* __restrict__ rec, int64_t stride,
@@ -2441,7 +2165,6 @@ __global__ void __launch_bounds__(256) assemble_clean_kernel(int64_t n, int K, c
     const int64_t s0 = (int64_t)blockIdx.x * kAsmSlots;
     const int ns = (int)((n - s0) < kAsmSlots ? (n - s0) : kAsmSlots);
     const int P = K + 1;
-#if MOPS_ASM_V2
     // (block-uniform) 16-B pieces, 2 slots per load: needs an even stride and a 16-B aligned slab (a caller's
     // finalize_range passes records + 8 lo for any lo)
     if (ns == kAsmSlots && (stride & 1) == 0 && (reinterpret_cast<uintptr_t>(rec) & 15) == 0) {
@@ -2451,11 +2174,11 @@ __global__ void __launch_bounds__(256) assemble_clean_kernel(int64_t n, int K, c
             tile[kk][c][2 * i2] = v.x;
             tile[kk][c][2 * i2 + 1] = v.y;
         }
-    } else
-#endif
-    for (int e = t; e < K * 6 * kAsmSlots; e += blockDim.x) {
-        const int i = e % kAsmSlots, c = (e / kAsmSlots) % 6, kk = e / (kAsmSlots * 6);
-        if (i < ns) tile[kk][c][i] = rec[kk * 6 * stride + c * stride + s0 + i];
+    } else {
+        for (int e = t; e < K * 6 * kAsmSlots; e += blockDim.x) {
+            const int i = e % kAsmSlots, c = (e / kAsmSlots) % 6, kk = e / (kAsmSlots * 6);
+            if (i < ns) tile[kk][c][i] = rec[kk * 6 * stride + c * stride + s0 + i];
+        }
     }
     for (int e = t; e < 3 * kAsmSlots; e += blockDim.x)
         if (e / 3 < ns) seed[e / 3][e % 3] = seeds[3 * s0 + e];
@@ -3130,6 +2853,7 @@ __global__ void cell_poly_kernel(int64_t C, const int* cellrec, const double4* v
             o = make_double4(qx, qy, qz, dev::wach_numerator(dev::tri_area(qx, qy, qz, x[i], y[i], z[i], nx, ny, nz)));
         }
         cpoly[c * MAXV + i] = o;
+        // (cedge: no caller passes it -- the edge vectors X_{i+1} - X_i of the slots; kept with TrajArgs::cedge)
         if (cedge && 3 * i + 2 < kCellNrm) {  // b - a of the weights' tri_area for slot i (X_{i+1} = poly[i])
             double* e = cedge + c * kCellNrm + 3 * i;
             e[0] = i < nv ? x[i] - o.x : 0.0;
@@ -3151,49 +2875,12 @@ __global__ void cell_poly_kernel(int64_t C, const int* cellrec, const double4* v
     if (cedge) cedge[c * kCellNrm + kCellNrm - 1] = 0.0;
 }
 
-// Level-pair records (mops_field::d_pr), one 16-B chunk per thread so that a wave's
-// stores are contiguous: chunk q of record (v, k) is {z_{k-1}, z_k}, {w_{k-1}, w_k} or
-// two of the six doubles vel_{k-1}.xyz, vel_k.xyz.  IDX = uint32_t when the chunk count fits.
-template <typename IDX>
-__global__ void pair_record_kernel(int64_t V, int L, const double* __restrict__ zt, const double* __restrict__ vel,
-                                   const double* __restrict__ w, double* __restrict__ pr) {
-    const IDX j = (IDX)blockIdx.x * (IDX)blockDim.x + (IDX)threadIdx.x;
-    if ((int64_t)j >= V * (L - 1) * (kPairRec / 2)) return;
-    // (k-1, q, v) with v fastest (piece-major: contiguous stores), or (k-1, v, q) record-major
-    const IDX vv = (IDX)V;
-    IDX v;
-    int q, k;
-    if (MOPS_PR_PIECES) {
-        const IDX r = j / vv;
-        v = j - r * vv;
-        q = (int)(r % (IDX)(kPairRec / 2));
-        k = (int)(r / (IDX)(kPairRec / 2)) + 1;
-    } else {
-        const IDX rec = j / (IDX)(kPairRec / 2);
-        q = (int)(j - rec * (IDX)(kPairRec / 2));
-        const IDX kk = rec / vv;
-        v = rec - kk * vv;
-        k = (int)kk + 1;
-    }
-    double2 val;
-    if (q == 0) {
-        const double* z = zt + (int64_t)v * L;
-        val = make_double2(z[k - 1], z[k]);
-    } else if (q == 1) {
-        const double* ww = w + (int64_t)v * (L + 1);
-        val = make_double2(ww[k - 1], ww[k]);
-    } else {
-        const double* u = vel + ((int64_t)v * L + k - 1) * 3 + 2 * (q - 2);
-        val = make_double2(u[0], u[1]);
-    }
-    reinterpret_cast<double2*>(pr)[pr_base((uint32_t)(k - 1), (uint32_t)v, (uint32_t)V) +
-                                   (uint32_t)q * pr_qstride((uint32_t)V)] = val;
-}
-
+// Level-pair records (mops_field::d_pr): 16-B piece q of record (v, k) is {z_{k-1}, z_k}, {w_{k-1}, w_k} or
+// two of the six doubles vel_{k-1}.xyz, vel_k.xyz.
 // Level-major records ((k-1)*V + v) from the vertex-major zt/vel/w arrays: a block stages a
 // tile of kRecTV vertices x (kRecTK + 1) levels through LDS (reads run along each vertex's
 // column) and writes kRecTK rows of kRecTV consecutive records (contiguous 5 KB per row), so
-// both sides are coalesced.  Same values and chunk layout as pair_record_kernel.
+// both sides are coalesced.
 #ifndef MOPS_REC_TV
 #define MOPS_REC_TV 32  // 32 x 16 tiles: 16.4 vs 17.6 ms per oRRS18to6 snapshot (64 x 16), profiles/r03
 #endif
@@ -3201,9 +2888,6 @@ __global__ void pair_record_kernel(int64_t V, int L, const double* __restrict__ 
 #define MOPS_REC_TK 16
 #endif
 constexpr int kRecTV = MOPS_REC_TV, kRecTK = MOPS_REC_TK;
-#ifndef MOPS_REC_TILED
-#define MOPS_REC_TILED 1  // records built by pair_record_tiled_kernel (0: one 16-B piece per thread, pair_record_kernel)
-#endif
 __global__ void __launch_bounds__(256) pair_record_tiled_kernel(int64_t V, int L, const double* __restrict__ zt,
                                                                 const double* __restrict__ vel,
                                                                 const double* __restrict__ w,
@@ -3227,17 +2911,11 @@ __global__ void __launch_bounds__(256) pair_record_tiled_kernel(int64_t V, int L
         if (vl < nv && kl <= nk) su[vl][kl][r - kl * 3] = vel[((v0 + vl) * L + k0) * 3 + r];
     }
     __syncthreads();
+    // (pair_record_fused_kernel ends in the same write-out loop: as one shared inline function it changed that
+    // kernel's instruction schedule, so it stays written out in both)
     for (int i = t; i < nk * kRecTV * (kPairRec / 2); i += blockDim.x) {
-        // piece-major: consecutive threads on consecutive vertices of one (level, piece) row
-        int q, kl, vl;
-        if (MOPS_PR_PIECES) {
-            vl = i % kRecTV;
-            const int r = i / kRecTV;
-            q = r % (kPairRec / 2); kl = r / (kPairRec / 2);
-        } else {
-            const int rl = i / (kPairRec / 2);
-            q = i - rl * (kPairRec / 2); kl = rl / kRecTV; vl = rl - kl * kRecTV;
-        }
+        const int rl = i / (kPairRec / 2);
+        const int q = i - rl * (kPairRec / 2), kl = rl / kRecTV, vl = rl - kl * kRecTV;
         if (vl >= nv) continue;
         double2 val;
         if (q == 0) val = make_double2(sz[vl][kl], sz[vl][kl + 1]);
@@ -3245,8 +2923,7 @@ __global__ void __launch_bounds__(256) pair_record_tiled_kernel(int64_t V, int L
         else if (q == 2) val = make_double2(su[vl][kl][0], su[vl][kl][1]);
         else if (q == 3) val = make_double2(su[vl][kl][2], su[vl][kl + 1][0]);
         else val = make_double2(su[vl][kl + 1][1], su[vl][kl + 1][2]);
-        reinterpret_cast<double2*>(pr)[pr_base((uint32_t)(k0 + kl), (uint32_t)(v0 + vl), (uint32_t)V) +
-                                       (uint32_t)q * pr_qstride((uint32_t)V)] = val;
+        reinterpret_cast<double2*>(pr)[pr_base((uint32_t)(k0 + kl), (uint32_t)(v0 + vl), (uint32_t)V) + (uint32_t)q] = val;
     }
 }
 
@@ -3300,17 +2977,10 @@ __global__ void __launch_bounds__(256) pair_record_fused_kernel(int64_t V, int L
         }
     }
     __syncthreads();
+    // (pair_record_tiled_kernel's write-out loop)
     for (int i = t; i < nk * kRecTV * (kPairRec / 2); i += blockDim.x) {
-        // piece-major: consecutive threads on consecutive vertices of one (level, piece) row
-        int q, kl, vl;
-        if (MOPS_PR_PIECES) {
-            vl = i % kRecTV;
-            const int r = i / kRecTV;
-            q = r % (kPairRec / 2); kl = r / (kPairRec / 2);
-        } else {
-            const int rl = i / (kPairRec / 2);
-            q = i - rl * (kPairRec / 2); kl = rl / kRecTV; vl = rl - kl * kRecTV;
-        }
+        const int rl = i / (kPairRec / 2);
+        const int q = i - rl * (kPairRec / 2), kl = rl / kRecTV, vl = rl - kl * kRecTV;
         if (vl >= nv) continue;
         double2 val;
         if (q == 0) val = make_double2(sz[vl][kl], sz[vl][kl + 1]);
@@ -3318,8 +2988,7 @@ __global__ void __launch_bounds__(256) pair_record_fused_kernel(int64_t V, int L
         else if (q == 2) val = make_double2(su[vl][kl][0], su[vl][kl][1]);
         else if (q == 3) val = make_double2(su[vl][kl][2], su[vl][kl + 1][0]);
         else val = make_double2(su[vl][kl + 1][1], su[vl][kl + 1][2]);
-        reinterpret_cast<double2*>(pr)[pr_base((uint32_t)(k0 + kl), (uint32_t)(v0 + vl), (uint32_t)V) +
-                                       (uint32_t)q * pr_qstride((uint32_t)V)] = val;
+        reinterpret_cast<double2*>(pr)[pr_base((uint32_t)(k0 + kl), (uint32_t)(v0 + vl), (uint32_t)V) + (uint32_t)q] = val;
     }
 }
 
@@ -3333,11 +3002,11 @@ __global__ void records_to_vertex_kernel(int64_t V, int L, const double* __restr
     const int j = (int)(idx - v * L);
     const bool hi = j == L - 1;  // the second half of record L-2
     const double2* p2 = reinterpret_cast<const double2*>(pr);
-    const uint32_t b = pr_base((uint32_t)(hi ? j - 1 : j), (uint32_t)v, (uint32_t)V), qs = pr_qstride((uint32_t)V);
+    const uint32_t b = pr_base((uint32_t)(hi ? j - 1 : j), (uint32_t)v, (uint32_t)V);
     double r[kPairRec];  // the record's 10 doubles in their order
 #pragma unroll
     for (int q = 0; q < kPairRec / 2; ++q) {
-        const double2 x = p2[b + (uint32_t)q * qs];
+        const double2 x = p2[b + (uint32_t)q];
         r[2 * q] = x.x; r[2 * q + 1] = x.y;
     }
     w[v * (L + 1) + j] = hi ? r[3] : r[2];
@@ -3502,7 +3171,7 @@ void free_mesh(mops_mesh* m) {
     if (!m) return;
     (void)hipFree(m->d_cellrec); (void)hipFree(m->d_cxyz); (void)hipFree(m->d_vxyz); (void)hipFree(m->d_cov);
     (void)hipFree(m->d_bary);
-    (void)hipFree(m->d_bkeys); (void)hipFree(m->d_bcells); (void)hipFree(m->d_hkeys); (void)hipFree(m->d_hval); (void)hipFree(m->d_cell_rank); (void)hipFree(m->d_rank_cell); (void)hipFree(m->d_cpolyr); (void)hipFree(m->d_cpoly); (void)hipFree(m->d_cnrm); (void)hipFree(m->d_cedge); (void)hipFree(m->d_nbr); (void)hipFree(m->d_rloc2); (void)hipFree(m->d_ring);
+    (void)hipFree(m->d_bkeys); (void)hipFree(m->d_bcells); (void)hipFree(m->d_hkeys); (void)hipFree(m->d_hval); (void)hipFree(m->d_cell_rank); (void)hipFree(m->d_rank_cell); (void)hipFree(m->d_cpolyr); (void)hipFree(m->d_cpoly); (void)hipFree(m->d_cnrm); (void)hipFree(m->d_nbr); (void)hipFree(m->d_rloc2); (void)hipFree(m->d_ring);
     (void)hipFree(m->d_scratch);
     (void)hipFree(m->d_eoc); (void)hipFree(m->d_coe); (void)hipFree(m->d_exyz); (void)hipFree(m->d_rbf_coef);
     (void)hipFree(m->d_rbf_slot);
@@ -3896,15 +3565,11 @@ mops_status mops_mesh_create(const mops_mesh_desc* desc, void* stream, mops_mesh
                                                         m->d_rloc2, m->d_ring);
     if ((st = dmalloc(&m->d_cpoly, (size_t)(C * m->maxv), &acc)) != MOPS_OK) { free_mesh(m); return st; }
     if (m->maxv == 7 && (st = dmalloc(&m->d_cnrm, (size_t)(C * kCellNrm), &acc)) != MOPS_OK) { free_mesh(m); return st; }
-    if (MOPS_TILE_E1 && m->maxv == 7 && (st = dmalloc(&m->d_cedge, (size_t)(C * kCellNrm), &acc)) != MOPS_OK) {
-        free_mesh(m);
-        return st;
-    }
     if (m->maxv == 7 && (st = dmalloc(&m->d_nbr, (size_t)(C * kNbrQ), &acc)) != MOPS_OK) { free_mesh(m); return st; }
     if (m->maxv == 7) cell_nbr_kernel<<<grid_for(C), kBlock, 0, s>>>(C, m->d_cellrec, m->d_cxyz, m->d_nbr);
     switch (m->maxv) {
         case 7:
-            cell_poly_kernel<7><<<grid_for(C), kBlock, 0, s>>>(C, m->d_cellrec, m->d_vxyz, m->d_cpoly, m->d_cnrm, m->d_cedge);
+            cell_poly_kernel<7><<<grid_for(C), kBlock, 0, s>>>(C, m->d_cellrec, m->d_vxyz, m->d_cpoly, m->d_cnrm);
             if (MOPS_CPOLY_RANK) {
                 if ((st = dmalloc(&m->d_cpolyr, (size_t)(C * 14), &acc)) != MOPS_OK) { free_mesh(m); return st; }
                 cpoly_rank_kernel<<<grid_for(C * 14), kBlock, 0, s>>>(C, m->d_rank_cell, m->d_cpoly, m->d_cpolyr);
@@ -3995,21 +3660,17 @@ mops_status mops_cell_center_velocity_rbf(const mops_mesh* m, const double* d_no
     return MOPS_OK;
 }
 
-// the all-zero record's pieces (pair_sums reads it for slots v >= nv): vertex V of every (layer, piece) row
-// (piece-major) or the record after the last (record-major); the builders never write them
+// the all-zero record's pieces (pair_sums reads it for slots v >= nv): the record after the last; the builders
+// never write them
 __global__ void pr_zero_kernel(int64_t V, int L, double2* __restrict__ pr) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (MOPS_PR_PIECES) {
-        if (i < (int64_t)(L - 1) * (kPairRec / 2)) pr[(uint64_t)i * (uint64_t)(V + 1) + (uint64_t)V] = make_double2(0.0, 0.0);
-    } else if (i < kPairRec / 2) {
-        pr[pr_zero((uint32_t)V, (uint32_t)L) + (uint32_t)i] = make_double2(0.0, 0.0);
-    }
+    if (i < kPairRec / 2) pr[pr_zero((uint32_t)V, (uint32_t)L) + (uint32_t)i] = make_double2(0.0, 0.0);
 }
 
 static mops_status alloc_records(const mops_mesh* mesh, mops_field* f, hipStream_t s) {
     if (mesh->L < 2) return MOPS_OK;
     if (!f->d_pr) MOPS_TRY(dmalloc(&f->d_pr, (size_t)(pr_pieces(mesh->V, mesh->L) * 2), &f->bytes));
-    pr_zero_kernel<<<grid_for((int64_t)(mesh->L - 1) * (kPairRec / 2)), kBlock, 0, s>>>(
+    pr_zero_kernel<<<grid_for(kPairRec / 2), kBlock, 0, s>>>(
         mesh->V, mesh->L, reinterpret_cast<double2*>(f->d_pr));
     HIP_TRY(hipGetLastError());
     return MOPS_OK;
@@ -4021,23 +3682,10 @@ static mops_status compute_flags(const mops_mesh* mesh, mops_field* f, hipStream
 static mops_status compute_mono(const mops_mesh* mesh, mops_field* f, hipStream_t s) {
     const int64_t npr = mesh->V * (int64_t)std::max(mesh->L - 1, 0);
     MOPS_TRY(alloc_records(mesh, f, s));
-#if MOPS_REC_TILED
     if (npr > 0) {
         const dim3 grid((unsigned)((mesh->V + kRecTV - 1) / kRecTV), (unsigned)((mesh->L - 1 + kRecTK - 1) / kRecTK));
         pair_record_tiled_kernel<<<grid, 256, 0, s>>>(mesh->V, mesh->L, f->d_zt, f->d_vel, f->d_w, f->d_pr);
     }
-#else
-    if (npr > 0)
-    {
-        const int64_t chunks = npr * (kPairRec / 2);
-        if (chunks < ((int64_t)1 << 32) - kBlock)
-            pair_record_kernel<uint32_t><<<grid_for(chunks), kBlock, 0, s>>>(mesh->V, mesh->L, f->d_zt, f->d_vel,
-                                                                           f->d_w, f->d_pr);
-        else
-            pair_record_kernel<uint64_t><<<grid_for(chunks), kBlock, 0, s>>>(mesh->V, mesh->L, f->d_zt, f->d_vel,
-                                                                           f->d_w, f->d_pr);
-    }
-#endif
     return compute_flags(mesh, f, s);
 }
 
@@ -4147,7 +3795,6 @@ static mops_status field_derive(const mops_mesh* mesh, mops_field* f, const mops
     } else {  // edge normals only: the RBF reconstruction (MPASOSolution::calcCellCenterVelocity)
         MOPS_TRY(mops_cell_center_velocity_rbf(mesh, d->h_normal_velocity, velc, s));
     }
-#if MOPS_FUSED_RECORDS
     if (L >= 2) {
         // CalcCellVertexZtop / CalcCellVertexVelocity / CalcCellVertexVertVelocity fused into the
         // level-pair record build (pair_record_fused_kernel)
@@ -4164,7 +3811,7 @@ static mops_status field_derive(const mops_mesh* mesh, mops_field* f, const mops
         HIP_TRY(hipGetLastError());
         return MOPS_OK;
     }
-#endif
+    // L < 2 (no level pair, no record): the vertex arrays alone
     cell_to_vertex_bary_kernel<1><<<grid_for(V * L), kBlock, 0, s>>>(V, L, mesh->d_cov, mesh->d_bary, ztc, f->d_zt, 0);
     cell_to_vertex_bary_kernel<3><<<grid_for(V * L), kBlock, 0, s>>>(V, L, mesh->d_cov, mesh->d_bary, velc, f->d_vel, 0);
     if (d->h_vert_velocity_top) {
@@ -4464,7 +4111,7 @@ mops_status mops_traj_advance(const mops_mesh* mesh, const mops_field* front, co
     a.n_live = p->d_n_live;
     a.cpoly = mesh->d_cpoly;
     a.cnrm = mesh->d_cnrm;
-    a.cedge = mesh->d_cedge;
+    a.cedge = nullptr;
     a.nbr = mesh->d_nbr;
     a.cpolyr = mesh->d_cpolyr;
     a.crank = mesh->d_cell_rank;

@@ -722,7 +722,7 @@ def test_zlevel_topography_partial_bottom(gpu, engine_lib, oracle_lib, method):
 def test_heptagon_cells_all_modes(gpu, engine_lib, oracle_lib):
     """maxEdges 7 with heptagons (diagonal flips): the MAXV 7 kernels keep the IsInMesh
     normals of polygon slots 0-4 in LDS and compute slots 5-6 per evaluation
-    (MOPS_LDS_COMPACT / MOPS_NRM_SLOTS), so seeds are placed in and around the
+    (MOPS_NRM_SLOTS), so seeds are placed in and around the
     heptagon (and pentagon) cells; every mode bit-exact against the oracle."""
     from mops_amd import synth
     from mops_amd.engine import DeviceField, DeviceMesh, TrajectoryConfig, run_trajectories
