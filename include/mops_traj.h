@@ -276,7 +276,10 @@ int64_t mops_traj_num_steps(const mops_traj_cfg* cfg);
  * the mesh (the cooperative-tile selection), freed with the mesh.  Use
  * long-lived streams (torch's pool, or streams created once): a stream
  * destroyed while its launches still run, whose handle a new stream then
- * reuses, would share that flag with the old launches. */
+ * reuses, would share that flag with the old launches.
+ * Ranges: the number of steps, the number of records and the record period
+ * in steps must each be below 2^31 (MOPS_ERR_INVALID otherwise, decided from
+ * cfg alone): the kernel counts them in 32 bits. */
 mops_status mops_traj_advance(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
                               const mops_traj_cfg* cfg, const mops_particles* particles,
                               int64_t step_begin, int64_t step_end, double* d_records,

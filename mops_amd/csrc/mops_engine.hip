@@ -1424,8 +1424,8 @@ struct TrajArgs {
     const int* __restrict__ n_live;  // device count of leading live slots (compaction), NULL = all n
     const double4* __restrict__ cpoly;  // per-cell rotated polygon + Wachspress B_i (mops_mesh::d_cpoly)
     const double* __restrict__ cnrm;    // per-cell edge normals (mops_mesh::d_cnrm; NULL past maxEdges 7)
-    const double* __restrict__ cedge;   // unused, always NULL: kept so that the kernel-argument offsets of the
-                                        // fields below, and with them the device code, stay as measured
+    const double* __restrict__ unused0; // unused, always NULL: kept so that the kernel-argument offsets of the
+                                        // fields below stay where the measured builds have them
     const uint4* __restrict__ nbr;      // per-cell neighbour table (mops_mesh::d_nbr; NULL past maxEdges 7)
     const double2* __restrict__ cpolyr;  // mops_mesh::d_cpolyr (NULL past maxEdges 7)
     const uint32_t* __restrict__ crank;  // mops_mesh::d_cell_rank
@@ -1597,7 +1597,14 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
     // kernel is sensitive to the form of this prologue and of the epilogue: 128 instead of 70 spilled VGPRs.)
     const bool resumed = COOP && !HAND && !EULER && a.handoff;
     if (resumed && a.death[pid] > -2) return;
-    const int64_t sb = resumed ? (int64_t)__builtin_amdgcn_readfirstlane(-2 - a.death[pid]) : a.step_begin;
+    // Steps, the record period, the next record step and the record index are 32-bit in here (mops_traj_advance
+    // checks n_steps, K and the record period against 2^31 once per launch).  What the compiler makes of it:
+    // step, step_end and the period are SGPRs and the loop exit is s_cmp; rec_next and rec_k are per-lane VGPRs
+    // (lanes leave the loop at different steps and rec_k is read after it), so the record test is a v_cmp_eq_u32
+    // -- and in the tile Euler and RK4 hand-off kernels rec_next is spilled: one 4-byte scratch reload per step
+    // 
+    const int sb = resumed ? (int)__builtin_amdgcn_readfirstlane(-2 - a.death[pid]) : (int)a.step_begin;
+    const int step_end = (int)a.step_end;
     // Records need no initialisation: the launches from step 0 on write every record of every
     // particle -- its samples while alive, then (at its death) the zeros the reference's
     // preallocated trajectory holds (dev::clear_records)
@@ -1646,16 +1653,19 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
     const int C = a.C;
     // next recording step (the smallest j >= step_begin with (j+1) % rec_period == 0) and its
     // record index, advanced by counting instead of a 64-bit modulo per step
-    int64_t rec_next = -1, rec_k = 0;
+    // (rec_next is unsigned: at most sb + rec_period - 1 < 2^32 here, and advanced only from a step it equals)
+    const int rec_period = (int)a.rec_period;
+    uint32_t rec_next = ~(uint32_t)0;
+    int rec_k = 0;
     bool rec0 = sb > 0;  // record 0's step-0 part (seed position, zero velocity) written
-    if (a.rec_period > 0) {
-        rec_k = sb / a.rec_period;
-        rec_next = (rec_k + 1) * a.rec_period - 1;
+    if (rec_period > 0) {
+        rec_k = sb / rec_period;
+        rec_next = (uint32_t)(rec_k + 1) * (uint32_t)rec_period - 1u;
     }
     [[maybe_unused]] int cell_in = 0;       // HAND: the cell this step's walk started from
     int tcell = -1, tkey = 0;               // cooperative tile: this lane's (cell, hints) at the last fill + group
     bool have_tile = false, coop_prev = false;  // (wave-uniform)
-    for (int64_t step = sb; step < a.step_end; ++step) {
+    for (int step = sb; step < step_end; ++step) {
         MOPS_MARK(100);
         if constexpr (HAND) cell_in = cell;  // (the walk restarts from it at a hand-off)
         if (step == 0) {  // first_loop (:892-901)
@@ -1867,7 +1877,8 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
         }
         double hx = 0, hy = 0, hz = 0, wv = 0;
         double nx, ny, nz;
-        const double alpha = PATH ? (double)step / (double)a.n_steps : 0.0;
+        double alpha = 0.0;
+        if constexpr (PATH) alpha = (double)step / (double)a.n_steps;
         if (EULER) {
             bool ok = dev::eval_at<MAXV, PATH, PairGroup<PATH, EULER>::value>(hex, c, a.L, a.V, a.f0, a.f1, x, y, z, d, alpha, hint0, hint1, hx, hy, hz, wv,
                                                                               coop, tile);
@@ -1936,13 +1947,13 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
             a.rec[5 * a.rec_stride + pid] = hz;
         }
         x = nx; y = ny; z = nz;
-        if (step == rec_next) {  // (step + 1) % rec_period == 0, record k = (step + 1) / rec_period - 1
-            const int64_t k = rec_k;
-            rec_next += a.rec_period;
+        if ((uint32_t)step == rec_next) {  // (step + 1) % rec_period == 0, record k = (step + 1) / rec_period - 1
+            const int k = rec_k;
+            rec_next += (uint32_t)rec_period;
             ++rec_k;
             MOPS_MARK(150);
-            if (k < a.K) {
-                double* rk = a.rec + k * 6 * a.rec_stride;
+            if (k < (int)a.K) {
+                double* rk = a.rec + (int64_t)k * 6 * a.rec_stride;
                 rk[0 * a.rec_stride + pid] = x;
                 rk[1 * a.rec_stride + pid] = y;
                 rk[2 * a.rec_stride + pid] = z;
@@ -1951,6 +1962,7 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
                 rk[5 * a.rec_stride + pid] = hz;
             }
         }
+        MOPS_MARK(160);
     }
     a.px[pid] = x; a.py[pid] = y; a.pz[pid] = z;
     a.depth[pid] = dep;
@@ -1963,10 +1975,10 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
     // slots never sampled: after a death, and past the last record step of a run whose
     // record period does not fill all K slots (streamline recordT % deltaT != 0)
     if constexpr (HAND) {
-        if (died >= 0 || (a.step_end == a.n_steps && died == -1))
+        if (died >= 0 || (step_end == (int)a.n_steps && died == -1))
             dev::clear_records(a.rec, a.rec_stride, pid, (rec_k == 0 && rec0) ? 1 : rec_k, a.K);
     } else {
-        if (died >= 0 || a.step_end == a.n_steps) dev::clear_records(a.rec, a.rec_stride, pid, (rec_k == 0 && rec0) ? 1 : rec_k, a.K);
+        if (died >= 0 || step_end == (int)a.n_steps) dev::clear_records(a.rec, a.rec_stride, pid, (rec_k == 0 && rec0) ? 1 : rec_k, a.K);
     }
 }
 
@@ -2823,7 +2835,7 @@ __global__ void cpoly_rank_kernel(int64_t C, const int* __restrict__ rank_cell, 
 // cooperative waves' tile takes them from here
 template <int MAXV>
 __global__ void cell_poly_kernel(int64_t C, const int* cellrec, const double4* vxyz, double4* cpoly,
-                                 double* cnrm = nullptr, double* cedge = nullptr) {
+                                 double* cnrm = nullptr) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     constexpr int REC = ((1 + 2 * MAXV) + 3) / 4 * 4;
@@ -2853,13 +2865,6 @@ __global__ void cell_poly_kernel(int64_t C, const int* cellrec, const double4* v
             o = make_double4(qx, qy, qz, dev::wach_numerator(dev::tri_area(qx, qy, qz, x[i], y[i], z[i], nx, ny, nz)));
         }
         cpoly[c * MAXV + i] = o;
-        // (cedge: no caller passes it -- the edge vectors X_{i+1} - X_i of the slots; kept with TrajArgs::cedge)
-        if (cedge && 3 * i + 2 < kCellNrm) {  // b - a of the weights' tri_area for slot i (X_{i+1} = poly[i])
-            double* e = cedge + c * kCellNrm + 3 * i;
-            e[0] = i < nv ? x[i] - o.x : 0.0;
-            e[1] = i < nv ? y[i] - o.y : 0.0;
-            e[2] = i < nv ? z[i] - o.z : 0.0;
-        }
         if (cnrm && 3 * i + 2 < kCellNrm) {
             double* n = cnrm + c * kCellNrm + 3 * i;
             if (i < nv) {  // X_i = (qx, qy, qz), X_{i+1} = poly[i] = (x[i], y[i], z[i])
@@ -2872,7 +2877,6 @@ __global__ void cell_poly_kernel(int64_t C, const int* cellrec, const double4* v
         }
     }
     if (cnrm) cnrm[c * kCellNrm + kCellNrm - 1] = 0.0;
-    if (cedge) cedge[c * kCellNrm + kCellNrm - 1] = 0.0;
 }
 
 // Level-pair records (mops_field::d_pr): 16-B piece q of record (v, k) is {z_{k-1}, z_k}, {w_{k-1}, w_k} or
@@ -4091,6 +4095,13 @@ mops_status mops_traj_advance(const mops_mesh* mesh, const mops_field* front, co
         return fail(MOPS_ERR_INVALID, "invalid trajectory settings");  // :666-669
     const int64_t K = mops_traj_num_records(cfg), n_steps = mops_traj_num_steps(cfg);
     if (K <= 0 || n_steps <= 0) return fail(MOPS_ERR_INVALID, "invalid integration steps");  // :709-712
+    // the kernel counts steps, records and the record period in 32 bits (settings only: checked before any handle
+    // is read)
+    const int64_t rec_period = back ? cfg->record_t / cfg->delta_t                          // record_interval (:1470)
+                                    : cfg->record_t / gcd64(cfg->record_t, cfg->delta_t);  // run_time % recordT == 0 (:994)
+    if (n_steps > INT32_MAX || K > INT32_MAX || rec_period > INT32_MAX)
+        return fail(MOPS_ERR_INVALID, "mops_traj_advance: the number of steps, the number of records and the record "
+                                      "period in steps must each be below 2^31");
     if (front->mesh != mesh || (back && back->mesh != mesh)) return fail(MOPS_ERR_INVALID, "field/mesh mismatch");
     if (p->n < 0 || record_stride < p->n) return fail(MOPS_ERR_INVALID, "record_stride < n");
     if (p->n == 0) return MOPS_OK;
@@ -4111,7 +4122,7 @@ mops_status mops_traj_advance(const mops_mesh* mesh, const mops_field* front, co
     a.n_live = p->d_n_live;
     a.cpoly = mesh->d_cpoly;
     a.cnrm = mesh->d_cnrm;
-    a.cedge = nullptr;
+    a.unused0 = nullptr;
     a.nbr = mesh->d_nbr;
     a.cpolyr = mesh->d_cpolyr;
     a.crank = mesh->d_cell_rank;
@@ -4121,11 +4132,7 @@ mops_status mops_traj_advance(const mops_mesh* mesh, const mops_field* front, co
     const int dt_sign = (cfg->direction == MOPS_FORWARD) ? 1 : -1;
     a.delta_t = dt_sign * (int)cfg->delta_t;
     a.dalpha = (double)a.delta_t / (double)cfg->simulation_duration;
-    if (back) {
-        a.rec_period = cfg->record_t / cfg->delta_t;  // record_interval (:1470)
-    } else {
-        a.rec_period = cfg->record_t / gcd64(cfg->record_t, cfg->delta_t);  // run_time % recordT == 0 (:994)
-    }
+    a.rec_period = rec_period;
     a.K = K;
     a.rec = d_records;
     a.rec_stride = record_stride;

@@ -41,9 +41,31 @@ def classify(ins):
     return "other"
 
 
+def overhead(ins):
+    """The VALU classes that carry no arithmetic of the result (--overhead)."""
+    op = ins.split()[0]
+    if op.startswith(("v_readlane", "v_writelane")):
+        return "lane_rd" if op.startswith("v_readlane") else "lane_wr"
+    if op.startswith(("v_mov", "v_accvgpr")):
+        return "v_mov"
+    if op.startswith("v_cvt"):
+        return "cvt"
+    if op.startswith(("v_div_", "v_rcp_", "v_rsq_", "v_sqrt_")):
+        return "div_sqrt"
+    if op.startswith("v_") and re.search(r"_[iub]64|u64_u32|i64_i32", op) and "f64" not in op:
+        return "int64"
+    if op.startswith("scratch_"):
+        return "scratch"
+    return None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("asm")
+    ap.add_argument("--overhead", action="store_true",
+                    help="per region: v_readlane / v_writelane (SGPR spill restores / saves, but for the regroup's "
+                         "three readlanes), v_mov, conversions, division/sqrt seeds and fix-ups, 64-bit integer VALU, "
+                         "scratch accesses")
     ap.add_argument("--kernel", default="_Z11traj_kernelILi7ELb0ELb1EEv8TrajArgs")
     ap.add_argument("--dump", default=None, help="FROM:TO marker ids: print that region")
     a = ap.parse_args()
@@ -73,6 +95,17 @@ def main():
         c = collections.Counter(classify(x) for x in real)
         nl = sum(1 for x in ins if x.startswith("LABEL"))
         print("%-8s %6d " % (rid, len(real)) + " ".join("%8d" % c.get(k, 0) for k in keys) + "  %d" % nl)
+    if a.overhead:
+        okeys = ["lane_rd", "lane_wr", "v_mov", "cvt", "div_sqrt", "int64", "scratch"]
+        print("\n%-8s %6s " % ("from", "valu") + " ".join("%10s" % k for k in okeys))
+        tot = collections.Counter()
+        for rid, ins in regions:
+            real = [x for x in ins if not x.startswith("LABEL")]
+            c = collections.Counter(overhead(x) for x in real)
+            c["valu"] = sum(1 for x in real if x.startswith("v_"))
+            tot.update(c)
+            print("%-8s %6d " % (rid, c["valu"]) + " ".join("%10d" % c.get(k, 0) for k in okeys))
+        print("%-8s %6d " % ("kernel", tot["valu"]) + " ".join("%10d" % tot.get(k, 0) for k in okeys))
     if a.dump:
         f, t = a.dump.split(":")
         on = False
