@@ -1,8 +1,8 @@
 // MOPS.h -- C++ operator API of the MI355X trajectory engine.
 //
 // Source-compatible mirror of the reference's public API for the trajectory
-// path (YosefQiu/MOPS include/api/MOPS.h:20-148, settings structs
-// src/Core/MPASOVisualizer.h:44-103, data model setters
+// path and the fixed-depth image remapping (YosefQiu/MOPS include/api/MOPS.h:20-148,
+// settings structs src/Core/MPASOVisualizer.h:20-103, data model setters
 // src/Core/MPASOGrid.cpp:82-188, src/Core/MPASOSolution.cpp:1145-1210):
 // same names, argument meaning and error behaviour, implemented on the C ABI
 // (include/mops_traj.h) -- the GPU engine is the only backend.
@@ -12,8 +12,6 @@
 //     p.x() into p.x with a macro (BackendCompat.hpp:188-191) -- define
 //     MOPS_COMPAT_ACCESSOR_MACROS before including this header to get the
 //     same macros;
-//   * MOPS_RunRemapping / regridding (image remapping) are out of scope and
-//     return an empty result with an error message;
 //   * derived fields are computed on the GPU and kept in HBM; nothing is
 //     cached on disk (the reference's cache is keyed only by timestep, Q11).
 #pragma once
@@ -44,6 +42,12 @@ namespace MOPS {
 
 enum class CalcDirection : int { kForward, kBackward, kCount };
 enum class CalcMethodType : int { kRK4, kEuler, kCount };
+enum class CalcPositionType : int { kCenter, kVertx, kPoint, kCount };
+enum class CalcAttributeType : int { kZonalMerimoal, kVelocity, kZTop, kTemperature, kSalinity, kAll, kCount };
+enum class VisualizeType : int { kFixedLayer, kFixedDepth };
+enum class SaveType : int { kVTI, kPNG, kNone, kCount };
+// Extension: the layer rule of the fixed-depth remapping (mops_traj.h MOPS_LAYER_*)
+enum class LayerRule : int { kReference = MOPS_LAYER_REFERENCE, kBracket = MOPS_LAYER_BRACKET };
 enum class GridAttributeType : int {
     kCellSize, kEdgeSize, kVertexSize, kMaxEdgesSize, kVertLevels, kVertLevelsP1, kVertexCoord, kCellCoord,
     kEdgeCoord, kVertexLatLon, kVerticesOnCell, kVerticesOnEdge, kCellsOnVertex, kCellsOnCell,
@@ -70,6 +74,60 @@ struct TrajectoryLine {
     double duration;
     double timestamp;
     double depth;
+};
+
+// ImageBuffer (src/Common/ImageBuffer.hpp:10-64): the members a caller reads.  Row-major
+// [height][width][4] (x, y, z, alpha); a written pixel has alpha 1.
+template <typename T>
+class ImageBuffer {
+  public:
+    ImageBuffer() = default;
+    ImageBuffer(int w, int h) : mWidth(w), mHeight(h) { mPixels.resize((size_t)mWidth * mHeight * 4, (T)0); }
+    int getIndex(const int i, const int j) const {
+        if (i < 0 || i >= mHeight || j < 0 || j >= mWidth) return -1;
+        return (i * mWidth + j) * 4;
+    }
+    vec3 getPixel(const int i, const int j) const {
+        const int index = getIndex(i, j);
+        if (index == -1) return vec3{-1, -1, -1};
+        return vec3{(double)mPixels[index + 0], (double)mPixels[index + 1], (double)mPixels[index + 2]};
+    }
+    std::vector<T> getChannel(int channel) const {
+        std::vector<T> out;
+        if (channel < 0 || channel > 3) return out;
+        out.reserve((size_t)mWidth * mHeight);
+        for (size_t k = 0; k < (size_t)mWidth * mHeight; ++k) out.push_back(mPixels[4 * k + channel]);
+        return out;
+    }
+    int getWidth() const { return mWidth; }
+    int getHeight() const { return mHeight; }
+
+    std::vector<T> mPixels;
+
+  protected:
+    int mWidth = 0;
+    int mHeight = 0;
+};
+
+// VisualizationSettings (src/Core/MPASOVisualizer.h:20-42); layerRule is this engine's one extension
+struct VisualizationSettings {
+    vec2 imageSize;  // x = width, y = height
+    vec2 LonRange;
+    vec2 LatRange;
+    vec2 DepthRange;
+    double FixedLatitude;
+    union {
+        double FixedDepth;
+        double FixedLayer;
+    };
+    int tile_index;
+    CalcAttributeType CalcType = CalcAttributeType::kZonalMerimoal;
+    CalcPositionType PositionType = CalcPositionType::kPoint;
+    VisualizeType VisType = VisualizeType::kFixedDepth;
+    SaveType saveType = SaveType::kNone;
+    double TimeStep;
+    LayerRule layerRule = LayerRule::kReference;
+    VisualizationSettings() = default;
 };
 
 struct TrajectorySettings {
@@ -166,6 +224,9 @@ void MOPS_End();
 void MOPS_ActiveAttribute(int t1, std::optional<int> t2 = std::nullopt);
 std::vector<TrajectoryLine> MOPS_RunStreamLine(TrajectorySettings* config, std::vector<CartesianCoord>& sample_points);
 std::vector<TrajectoryLine> MOPS_RunPathLine(TrajectorySettings* config, std::vector<CartesianCoord>& sample_points);
+// MOPSApp::runRemapping (MOPSApp.cpp:171-196): the fixed-depth images of the active front solution --
+// image 0 the ENU velocity, image 1 the first two double attributes when there are at least two
+std::vector<ImageBuffer<double>> MOPS_RunRemapping(VisualizationSettings* config);
 void MOPS_GenerateSamplePoints(SamplingSettings* config, std::vector<CartesianCoord>& sample_points);
 // Extension (the reference has no teardown): releases the mesh and fields held in HBM by the
 // global app.  Call it before the HIP runtime shuts down; nothing is freed from a static

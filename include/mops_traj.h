@@ -323,6 +323,69 @@ mops_status mops_remove_nan_lines(int64_t n, int64_t P, double* d_points, double
 mops_status mops_remove_nan_ragged(int64_t n, const int64_t* d_offsets, double* d_points, double* d_velocity,
                                    double* d_temperature, double* d_salinity, double* d_last_point, void* stream);
 
+/* ---- image remapping ---------------------------------------------------- */
+
+/* Layer rule of mops_remap_fixed_depth.  MOPS_LAYER_REFERENCE is the
+ * reference: MPASOVisualizerKernels.cpp:392-394 set local_layer = 0 whenever
+ * the depth lies at or below the column's top, so every wet pixel is the mean
+ * of the two top levels.  MOPS_LAYER_BRACKET (no
+ * reference counterpart) leaves those three lines out: the layer is the one
+ * the search found. */
+enum { MOPS_LAYER_REFERENCE = 0, MOPS_LAYER_BRACKET = 1 };
+
+/* VisualizationSettings (src/Core/MPASOVisualizer.h:20-42) as the two
+ * remapping kernels read it; degrees and metres. */
+typedef struct {
+    int32_t width, height;               /* imageSize.x, imageSize.y */
+    double min_lat, max_lat;             /* LatRange (fixed depth only) */
+    double min_lon, max_lon;             /* LonRange */
+    double fixed_depth;                  /* FixedDepth, positive down (negated, :251) */
+    double fixed_latitude;               /* FixedLatitude (fixed latitude only) */
+    double min_depth, max_depth;         /* fixed latitude rows: cellRefBottomDepth_vec.front() / .back() (:496-497) */
+    int32_t layer_rule;                  /* MOPS_LAYER_REFERENCE / MOPS_LAYER_BRACKET (fixed depth only) */
+} mops_remap_cfg;
+
+/* Images MOPSApp::runRemapping returns for a solution with n_attr double
+ * attributes (MOPSApp.cpp:176-185): 1 + ceil(n_attr / 3), or 1 without any. */
+int32_t mops_remap_num_images(int32_t n_attr);
+
+/* The host cos / sin tables the pixel positions are formed from (host only,
+ * no device work): fixed_latitude == 0 -- GeoConverter::
+ * convertPixelToLatLonToRadians (GeoConverter.hpp:28-32) per row [height] and
+ * per column [width]; != 0 -- VisualizeFixedLatitude's one row [1] at
+ * FixedLatitude and columns lon = minLon + j * j_step
+ * (MPASOVisualizerKernels.cpp:513-523).  libm cos / sin, as the reference's
+ * convertRadianLatLonToXYZ (GeoConverter.hpp:118-124). */
+mops_status mops_remap_tables(const mops_remap_cfg* cfg, int32_t fixed_latitude, double* h_row_cos,
+                              double* h_row_sin, double* h_col_cos, double* h_col_sin);
+
+/* MOPSApp::runRemapping -> Kernel::VisualizeFixedDepth (MOPSApp.cpp:171-196,
+ * MPASOVisualizerKernels.cpp:238-471), bit for bit: TBBKernel::SearchKDTree
+ * becomes mops_locate_cells on positions formed on the device from
+ * mops_remap_tables.  d_images receives mops_remap_num_images(n_attr) images
+ * [height][width][4] doubles: image 0 = {u_east, v_north, speed, 1}; image 1
+ * is written only when n_attr > 1, {d_attr0, d_attr1, 0, 1} (vertex arrays
+ * [V*L] in the caller's vertex order from mops_cell_to_vertex_attr, in
+ * std::map name order: mDoubleAttributes_CtoV), and stays zero otherwise, as
+ * every later image.  d_cells [height*width] (optional) receives the cell of
+ * each pixel.  h_stage_ms (optional, host, 3 floats) receives the HIP-event
+ * times of the positions, locate and evaluation stages.  Synchronises
+ * `stream`.  MOPS_ERR_INVALID (nothing written) where the reference answers
+ * Error() and returns, and for a bad image size, rule or attribute count. */
+mops_status mops_remap_fixed_depth(const mops_mesh* mesh, const mops_field* field, const mops_remap_cfg* cfg,
+                                   int32_t n_attr, const double* d_attr0, const double* d_attr1, double* d_images,
+                                   int32_t* d_cells, float* h_stage_ms, void* stream);
+
+/* MOPSApp::runReGrid -> Kernel::VisualizeFixedLatitude (MOPSApp.cpp:198-210,
+ * MPASOVisualizerKernels.cpp:473-651), bit for bit: rows are depths from
+ * min_depth to max_depth, columns longitudes at fixed_latitude; the inside
+ * test is MPASOField::isOnOcean (MPASOField.cpp:36-81).  d_image
+ * [height][width][4] = {zonal, meridional, 0, 1}.  A column's position and
+ * cell do not depend on the row, so only `width` points are located; d_cells
+ * [width] (optional) receives them.  Synchronises `stream`. */
+mops_status mops_remap_fixed_latitude(const mops_mesh* mesh, const mops_field* field, const mops_remap_cfg* cfg,
+                                      double* d_image, int32_t* d_cells, void* stream);
+
 /* Identity of the engine build: a hash of the engine's sources, headers,
  * compiler flags and ROCm version, stamped at compile time (no reference
  * counterpart).  The Python loader refuses a library whose id differs from

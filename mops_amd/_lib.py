@@ -22,6 +22,7 @@ EXPORTED = (
     "mops_order_particles_live", "mops_permute_arrays", "mops_records_clear_dead",
     "mops_traj_num_records", "mops_traj_num_steps", "mops_traj_advance", "mops_traj_finalize", "mops_traj_last_points",
     "mops_remove_nan_lines", "mops_remove_nan_ragged", "mops_run_trajectories", "mops_build_id",
+    "mops_remap_num_images", "mops_remap_tables", "mops_remap_fixed_depth", "mops_remap_fixed_latitude",
     # include/mops_io.h
     "mops_lines_geo", "mops_write_lines_vtp", "mops_write_lines_txt", "mops_write_pathline_binary",
     # include/mops_netcdf.h
@@ -32,6 +33,7 @@ EXPORTED = (
 MOPS_OK, MOPS_ERR_INVALID, MOPS_ERR_HIP, MOPS_ERR_UNSUPPORTED = 0, -1, -2, -3
 MOPS_FORWARD, MOPS_BACKWARD = 0, 1
 MOPS_RK4, MOPS_EULER = 0, 1
+MOPS_LAYER_REFERENCE, MOPS_LAYER_BRACKET = 0, 1
 
 
 class MeshDesc(C.Structure):
@@ -62,6 +64,13 @@ class Particles(C.Structure):
 class PermArray(C.Structure):
     _fields_ = [("d_src", C.c_void_p), ("d_dst", C.c_void_p), ("elem_bytes", C.c_int64), ("rows", C.c_int64),
                 ("row_stride", C.c_int64)]
+
+
+class RemapCfg(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("min_lat", C.c_double), ("max_lat", C.c_double),
+                ("min_lon", C.c_double), ("max_lon", C.c_double), ("fixed_depth", C.c_double),
+                ("fixed_latitude", C.c_double), ("min_depth", C.c_double), ("max_depth", C.c_double),
+                ("layer_rule", C.c_int32)]
 
 
 class MopsError(RuntimeError):
@@ -154,6 +163,10 @@ def load(path: str | None = None):
     lib.mops_records_clear_dead.restype = st
     lib.mops_run_trajectories.argtypes = [P, P, P, P, I64, P, P, C.c_float, P, P, P, P, P, P, P, P, P, P]
     lib.mops_run_trajectories.restype = st
+    lib.mops_remap_num_images.argtypes = [I32]; lib.mops_remap_num_images.restype = I32
+    lib.mops_remap_tables.argtypes = [P, I32, P, P, P, P]; lib.mops_remap_tables.restype = st
+    lib.mops_remap_fixed_depth.argtypes = [P, P, P, I32, P, P, P, P, P, P]; lib.mops_remap_fixed_depth.restype = st
+    lib.mops_remap_fixed_latitude.argtypes = [P, P, P, P, P, P]; lib.mops_remap_fixed_latitude.restype = st
     _lib = lib
     return lib
 

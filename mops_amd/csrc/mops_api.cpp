@@ -2,7 +2,7 @@
 // of the C ABI.  Mirrors the reference's MOPS.cpp / MOPSApp.cpp state machine
 // (src/Core/MOPS.cpp:10-71, src/Core/MOPSApp.cpp:34-337): one global app,
 // Init -> Begin -> AddGridMesh -> AddAttribute* -> End -> ActiveAttribute ->
-// RunStreamLine / RunPathLine.  Every trajectory computation goes to the HIP
+// RunStreamLine / RunPathLine / RunRemapping.  Every computation goes to the HIP
 // engine; this file only marshals host containers.
 #include "mops/MOPS.h"
 
@@ -61,6 +61,7 @@ struct App {
     std::map<int, mops_field*> fields;
     mops_field* front = nullptr;
     mops_field* back = nullptr;
+    int front_id = 0;  // the solution behind `front` (its attributes feed the remapping)
 
     void release() {
         for (auto& kv : fields) mops_field_destroy(kv.second);
@@ -316,7 +317,10 @@ void MOPS_End() {
                                   reinterpret_cast<const double*>(g.edgeCoord_vec.data()), nullptr),
               "mops_mesh_set_edges");
     for (auto& kv : g_app.sols) g_app.fields[kv.first] = make_field(*kv.second);
-    if (!g_app.fields.empty()) g_app.front = g_app.fields.begin()->second;  // addField: first map entry
+    if (!g_app.fields.empty()) {  // addField: first map entry
+        g_app.front = g_app.fields.begin()->second;
+        g_app.front_id = g_app.fields.begin()->first;
+    }
 }
 
 void MOPS_ActiveAttribute(int t1, std::optional<int> t2) {  // MOPSApp.cpp:145-169
@@ -335,6 +339,7 @@ void MOPS_ActiveAttribute(int t1, std::optional<int> t2) {  // MOPSApp.cpp:145-1
         g_app.back = it2->second;
     }
     g_app.front = it->second;
+    g_app.front_id = t1;
 }
 
 std::vector<TrajectoryLine> MOPS_RunStreamLine(TrajectorySettings* config, std::vector<CartesianCoord>& sample_points) {
@@ -352,6 +357,65 @@ std::vector<TrajectoryLine> MOPS_RunPathLine(TrajectorySettings* config, std::ve
     for (size_t i = 0; i < sample_points.size() && i < lines.size(); ++i)  // :287-290
         sample_points[i] = lines[i].lastPoint;
     return lines;
+}
+
+std::vector<ImageBuffer<double>> MOPS_RunRemapping(VisualizationSettings* config) {
+    ScopedTimer t("GPUKernel::Remapping", "GPUKernel");
+    if (config == nullptr || g_app.mesh == nullptr || g_app.front == nullptr) {  // MPASOVisualizerKernels.cpp:240-243
+        Error("[MI355X::VisualizeFixedDepth] invalid inputs");
+        return {};
+    }
+    const auto sit = g_app.sols.find(g_app.front_id);
+    static const std::map<std::string, std::vector<double>> none;
+    const auto& attrs = (sit == g_app.sols.end() || !sit->second) ? none : sit->second->mDoubleAttributes;
+    const int n_attr = (int)attrs.size();
+    const int W = (int)config->imageSize.x, H = (int)config->imageSize.y;
+    const int n_img = mops_remap_num_images(n_attr);
+    std::vector<ImageBuffer<double>> img_vec;  // MOPSApp.cpp:173-185
+    for (int k = 0; k < n_img; ++k) img_vec.emplace_back(W > 0 ? W : 0, H > 0 ? H : 0);
+    if (W <= 0 || H <= 0) {
+        Error("[MI355X::VisualizeFixedDepth] invalid image size");
+        return img_vec;
+    }
+    mops_remap_cfg cfg{};
+    cfg.width = W; cfg.height = H;
+    cfg.min_lat = config->LatRange.x; cfg.max_lat = config->LatRange.y;
+    cfg.min_lon = config->LonRange.x; cfg.max_lon = config->LonRange.y;
+    cfg.fixed_depth = config->FixedDepth;
+    cfg.layer_rule = (int32_t)config->layerRule;
+    const size_t px = (size_t)W * H * 4, VL = (size_t)g_app.grid->mVertexSize * g_app.grid->mVertLevels,
+                 CL = (size_t)g_app.grid->mCellsSize * g_app.grid->mVertLevels;
+    const bool two = n_attr > 1;
+    // one allocation: images | two vertex attribute arrays | one cell attribute staging array
+    struct DevBuf {
+        void* p = nullptr;
+        ~DevBuf() { (void)hipFree(p); }
+    } buf;
+    auto hip = [](hipError_t e, const char* what) {
+        if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+    };
+    hip(hipMalloc(&buf.p, (px * n_img + (two ? 2 * VL + CL : 0)) * sizeof(double)), "MOPS_RunRemapping: hipMalloc");
+    double* d_img = static_cast<double*>(buf.p);
+    double* d_attr[2] = {nullptr, nullptr};
+    if (two) {  // mDoubleAttributes_CtoV: the first two attributes in std::map name order
+        double* d_cell = d_img + px * n_img + 2 * VL;
+        auto it = attrs.begin();
+        for (int k = 0; k < 2; ++k, ++it) {
+            if (it->second.size() != CL)
+                throw std::runtime_error("MOPS_RunRemapping: attribute " + it->first + " is not [nCells*nVertLevels]");
+            d_attr[k] = d_img + px * n_img + (size_t)k * VL;
+            hip(hipMemcpy(d_cell, it->second.data(), CL * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy attribute");
+            check(mops_cell_to_vertex_attr(g_app.mesh, d_cell, d_attr[k], nullptr), "mops_cell_to_vertex_attr");
+            hip(hipDeviceSynchronize(), "mops_cell_to_vertex_attr");
+        }
+    }
+    check(mops_remap_fixed_depth(g_app.mesh, g_app.front, &cfg, n_attr, d_attr[0], d_attr[1], d_img, nullptr, nullptr,
+                                 nullptr),
+          "mops_remap_fixed_depth");
+    for (int k = 0; k < n_img; ++k)
+        hip(hipMemcpy(img_vec[(size_t)k].mPixels.data(), d_img + px * k, px * sizeof(double), hipMemcpyDeviceToHost),
+            "hipMemcpy image");
+    return img_vec;
 }
 
 void MOPS_GenerateSamplePoints(SamplingSettings* config, std::vector<CartesianCoord>& points) {

@@ -4332,3 +4332,518 @@ mops_status mops_run_trajectories(const mops_mesh* mesh, const mops_field* front
 }
 
 }  // extern "C"
+
+// ===========================================================================
+// image remapping: fixed depth (Kernel::VisualizeFixedDepth,
+// MPASOVisualizerKernels.cpp:238-471) and fixed latitude (VisualizeFixedLatitude,
+// :473-651).  One lane per pixel; the plain reference forms throughout (the
+// trajectory path's cached / rescaled stencils are not used here), so every
+// element sees the reference's operations in the reference's order.
+// ===========================================================================
+namespace {
+
+constexpr double kRemapRadius = 6371010.0;  // GeoConverter.hpp:107 (6371010.0f is exact in float)
+
+// GeoConverter::convertRadianLatLonToXYZ (GeoConverter.hpp:118-124) from the host's libm tables: the latitude
+// depends on the row only, the longitude on the column only
+__global__ void __launch_bounds__(256) remap_positions_kernel(int64_t n, int W, const double* __restrict__ row_cos,
+                                                              const double* __restrict__ row_sin,
+                                                              const double* __restrict__ col_cos,
+                                                              const double* __restrict__ col_sin,
+                                                              double* __restrict__ pts) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    const int64_t i = g / W;
+    const int j = (int)(g - i * W);
+    const double r = kRemapRadius;
+    const double costheta = row_cos[i], sintheta = row_sin[i], cosphi = col_cos[j], sinphi = col_sin[j];
+    pts[3 * g + 0] = r * costheta * cosphi;
+    pts[3 * g + 1] = r * costheta * sinphi;
+    pts[3 * g + 2] = r * sintheta;
+}
+
+struct RemapArgs {
+    int64_t n;                 // pixels
+    int W;
+    int64_t C, V;
+    int L, rec_ints;
+    const int* cellrec;
+    const double4* vxyz;
+    const double* zt;          // [V][L] internal vertex order
+    const double* pr;          // level-pair records (L >= 2), else NULL
+    const double* vel;         // [V][L][3] (read only when pr is NULL)
+    const int* vold;           // internal vertex -> the caller's vertex (attribute arrays), NULL = identity
+    const double* attr0;       // [V][L] in the caller's vertex order, or NULL
+    const double* attr1;
+    const double* pts;         // fixed depth: [n][3]; fixed latitude: [W][3]
+    const int* cells;          // fixed depth: [n]; fixed latitude: [W]
+    double depth;              // fixed depth: DEPTH = -FixedDepth
+    double min_depth, i_step;  // fixed latitude rows
+    int bracket;               // layer rule
+    double* img0;
+    double* img1;              // written only with two or more attributes
+};
+
+template <int MAXV>
+struct RemapStencil {
+    int nv;
+    int vid[MAXV];
+    double w[MAXV];
+};
+
+__device__ __forceinline__ void remap_set_pixel(double* img, int64_t g, double x, double y, double z) {
+    // SetPixel (ImageBuffer.hpp:68-77): alpha 1.0 for every written pixel, NaN ones included
+    img[4 * g + 0] = x;
+    img[4 * g + 1] = y;
+    img[4 * g + 2] = z;
+    img[4 * g + 3] = 1.0;
+}
+
+// The cell's vertices, the inside test and the Wachspress weights.  OCEAN false: TBBKernel::IsInMesh
+// (TBBKernel.h:21-54); true: MPASOField::isOnOcean (MPASOField.cpp:36-81), a sign-consistency test on (p - A).
+// Then Interpolator::CalcPolygonWachspress (Interpolation.hpp:137-165).  false = the pixel is NaN.
+template <int MAXV, bool OCEAN>
+__device__ __forceinline__ bool remap_stencil(const RemapArgs& a, int cell, double px, double py, double pz,
+                                              RemapStencil<MAXV>& s) {
+    const int* r = a.cellrec + (int64_t)cell * a.rec_ints;
+    const int nv = r[0];
+    s.nv = nv;
+    if (nv <= 0 || nv > MAXV) return false;
+    if (!OCEAN && !(isfinite(px) && isfinite(py) && isfinite(pz))) return false;
+    double x[MAXV], y[MAXV], z[MAXV];
+#pragma unroll
+    for (int k = 0; k < MAXV; ++k) {
+        s.vid[k] = 0; s.w[k] = 0.0;
+        x[k] = 0.0; y[k] = 0.0; z[k] = 0.0;
+        if (k < nv) {
+            const int v = r[1 + k];
+            if (v < 0 || v >= a.V) return false;
+            s.vid[k] = v;
+            const double4 q = a.vxyz[v];
+            x[k] = q.x; y[k] = q.y; z[k] = q.z;
+        }
+    }
+    double lx = 0.0, ly = 0.0, lz = 0.0;  // poly[nv-1]
+#pragma unroll
+    for (int k = 0; k < MAXV; ++k)
+        if (k == nv - 1) { lx = x[k]; ly = y[k]; lz = z[k]; }
+    bool first_pos = false, ok = true;
+#pragma unroll
+    for (int k = 0; k < MAXV; ++k) {
+        if (k < nv) {
+            const bool wrap = (k + 1 >= nv);
+            const double bx = wrap ? x[0] : x[(k + 1) % MAXV];
+            const double by = wrap ? y[0] : y[(k + 1) % MAXV];
+            const double bz = wrap ? z[0] : z[(k + 1) % MAXV];
+            if (!OCEAN) {
+                const double nx = y[k] * bz - z[k] * by;
+                const double ny = z[k] * bx - x[k] * bz;
+                const double nz = x[k] * by - y[k] * bx;
+                const double direction = nx * px + ny * py + nz * pz;
+                if (direction < 0.0) ok = false;
+            } else {
+                const double aox = 0.0 - x[k], aoy = 0.0 - y[k], aoz = 0.0 - z[k];
+                const double box = 0.0 - bx, boy = 0.0 - by, boz = 0.0 - bz;
+                const double apx = px - x[k], apy = py - y[k], apz = pz - z[k];
+                const double nx = aoy * boz - aoz * boy;
+                const double ny = aoz * box - aox * boz;
+                const double nz = aox * boy - aoy * box;
+                const double direction = nx * apx + ny * apy + nz * apz;
+                const bool pos = direction > 0;
+                if (k == 0) first_pos = pos;
+                if (pos != first_pos) ok = false;  // is_land
+            }
+        }
+    }
+    if (!ok) return false;
+    double sumweights = 0.0;
+    double A_iplus1 = dev::tri_area(lx, ly, lz, x[0], y[0], z[0], px, py, pz);
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        if (i < nv) {
+            const bool wrap = (i + 1 >= nv);
+            const double nx = wrap ? x[0] : x[(i + 1) % MAXV];
+            const double ny = wrap ? y[0] : y[(i + 1) % MAXV];
+            const double nz = wrap ? z[0] : z[(i + 1) % MAXV];
+            const double qx = (i == 0) ? lx : x[(i + MAXV - 1) % MAXV];
+            const double qy = (i == 0) ? ly : y[(i + MAXV - 1) % MAXV];
+            const double qz = (i == 0) ? lz : z[(i + MAXV - 1) % MAXV];
+            const double A_i = A_iplus1;
+            A_iplus1 = dev::tri_area(x[i], y[i], z[i], nx, ny, nz, px, py, pz);
+            const double B = dev::tri_area(qx, qy, qz, x[i], y[i], z[i], nx, ny, nz);
+            s.w[i] = B / (A_i * A_iplus1);
+            sumweights += s.w[i];
+        }
+    }
+    const double recp = 1.0 / sumweights;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i)
+        if (i < nv) s.w[i] *= recp;
+    return true;
+}
+
+// One pass over the clamped zTop column (MPASOVisualizerKernels.cpp:346-360 / :573-587) without storing it:
+// z[0], the last clamped value, and the first level k whose (z[k-1], z[k]) satisfies the layer search
+// predicate (:379-391 with tol 1e-8 / :597-607 with 1e-6), with that pair.  Returns that k or -1.
+template <int MAXV>
+__device__ __forceinline__ int remap_column(const RemapArgs& a, const RemapStencil<MAXV>& s, double D, double tol,
+                                            double& z0, double& zlast, double& ztop, double& zbot) {
+    int found = -1;
+    double prev = 0.0;
+    ztop = 0.0; zbot = 0.0;
+    for (int k = 0; k < a.L; ++k) {
+        double acc = 0.0;
+#pragma unroll
+        for (int v = 0; v < MAXV; ++v)
+            if (v < s.nv) acc += s.w[v] * a.zt[(int64_t)s.vid[v] * a.L + k];
+        if (k == 0) {
+            z0 = acc;
+        } else {
+            if (acc > prev) acc = prev - 1e-9;
+            double topI = prev, botI = acc;
+            if (topI < botI) { const double t = topI; topI = botI; botI = t; }
+            if (found < 0 && D <= topI + tol && D >= botI - tol) { found = k; ztop = prev; zbot = acc; }
+        }
+        prev = acc;
+    }
+    zlast = prev;
+    return found;
+}
+
+// TBBKernel::CalcVelocity (TBBKernel.h:128-147) at one level: the vertex velocities are read from the
+// level-pair records (level j < L-1 from record j, level L-1 from the second half of record L-2; the same
+// doubles as cellVertexVelocity_vec), or from the vertex array of a one-level field
+template <int MAXV>
+__device__ __forceinline__ void remap_velocity(const RemapArgs& a, const RemapStencil<MAXV>& s, int level,
+                                               double& vx, double& vy, double& vz) {
+    vx = 0.0; vy = 0.0; vz = 0.0;
+    const bool hi = a.pr && level == a.L - 1;
+#pragma unroll
+    for (int v = 0; v < MAXV; ++v) {
+        if (v < s.nv) {
+            const double* p;
+            if (a.pr)
+                p = a.pr + (size_t)pr_base((uint32_t)(hi ? level - 1 : level), (uint32_t)s.vid[v], (uint32_t)a.V) * 2u +
+                    (hi ? 7 : 4);
+            else
+                p = a.vel + ((int64_t)s.vid[v] * a.L + level) * 3;
+            vx += s.w[v] * p[0];
+            vy += s.w[v] * p[1];
+            vz += s.w[v] * p[2];
+        }
+    }
+}
+
+// TBBKernel::CalcAttribute (TBBKernel.h:149-166); the attribute arrays are in the caller's vertex order
+template <int MAXV>
+__device__ __forceinline__ double remap_attribute(const RemapArgs& a, const RemapStencil<MAXV>& s, int level,
+                                                  const double* __restrict__ attr) {
+    double r = 0.0;
+#pragma unroll
+    for (int v = 0; v < MAXV; ++v) {
+        if (v < s.nv) {
+            const int64_t vid = a.vold ? a.vold[s.vid[v]] : s.vid[v];
+            r += s.w[v] * attr[vid * a.L + level];
+        }
+    }
+    return r;
+}
+
+// GeoConverter::convertXYZVelocityToENU (GeoConverter.hpp:200-223)
+__device__ __forceinline__ void remap_enu(double px, double py, double pz, double vx, double vy, double vz,
+                                          double& Uzon, double& Umer) {
+    if (px == 0.0 && py == 0.0) { Uzon = 0.0; Umer = 0.0; return; }
+    const double Rxy = sqrt(px * px + py * py);
+    const double Rxyz = sqrt(px * px + py * py + pz * pz);
+    const double slon = py / Rxy;
+    const double clon = px / Rxy;
+    const double slat = pz / Rxyz;
+    const double clat = Rxy / Rxyz;
+    Uzon = -slon * vx + clon * vy;
+    Umer = -slat * (clon * vx + slon * vy) + clat * vz;
+}
+
+template <int MAXV>
+__global__ void __launch_bounds__(256) remap_fixed_depth_kernel(RemapArgs a) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= a.n) return;
+    const double nan = __builtin_nan("");
+    const int cell = a.cells[g];
+    const double px = a.pts[3 * g], py = a.pts[3 * g + 1], pz = a.pts[3 * g + 2];
+    RemapStencil<MAXV> s;
+    bool ok = cell >= 0 && cell < a.C;                               // :299
+    if (ok) ok = remap_stencil<MAXV, false>(a, cell, px, py, pz, s);  // :312-335
+    if (ok) ok = a.L > 0 && a.L <= kMaxLevels;                       // :338
+    const double DEPTH = a.depth;
+    int local_layer = -1;
+    double z0 = 0.0, zlast = 0.0, ftop = 0.0, fbot = 0.0;
+    if (ok) {
+        local_layer = remap_column<MAXV>(a, s, DEPTH, 1e-8, z0, zlast, ftop, fbot);
+        double z_surf = z0, z_bot = zlast;
+        if (z_surf < z_bot) { const double t = z_surf; z_surf = z_bot; z_bot = t; }
+        const double epsd = dev::dmax(1e-6, 1e-8 * fabs(z_surf - z_bot));
+        if (!(DEPTH <= z_surf + epsd && DEPTH >= z_bot - epsd)) ok = false;  // :370
+    }
+    if (ok) {
+        if (!a.bracket && DEPTH <= z0) local_layer = 0;  // :392-394, the layer override (reference rule only)
+        if (local_layer < 0) ok = false;                 // :395
+    }
+    if (!ok) {
+        remap_set_pixel(a.img0, g, nan, nan, nan);
+        if (a.img1) remap_set_pixel(a.img1, g, nan, nan, nan);
+        return;
+    }
+    double topI = local_layer == 0 ? z0 : ftop;  // z[max(0, local_layer - 1)]
+    double botI = local_layer == 0 ? z0 : fbot;  // z[local_layer]
+    if (topI < botI) { const double t = topI; topI = botI; botI = t; }
+    const double denom = topI - botI;
+    const double tparam = (denom > 1e-12) ? (DEPTH - botI) / denom : 0.5;
+    const int vel_levels = a.L;
+    int j = local_layer - 1;
+    j = j < 0 ? 0 : (j > vel_levels - 1 ? vel_levels - 1 : j);
+    const int j_bot = (j + 1 < vel_levels - 1) ? j + 1 : vel_levels - 1;
+    const int j_top = j;
+    double tx, ty, tz, bx, by, bz;
+    remap_velocity<MAXV>(a, s, j_top, tx, ty, tz);
+    remap_velocity<MAXV>(a, s, j_bot, bx, by, bz);
+    const double mtop = sqrt(tx * tx + ty * ty + tz * tz), mbot = sqrt(bx * bx + by * by + bz * bz);
+    double fx, fy, fz;
+    if (mtop < 1e-12 && mbot < 1e-12) {
+        fx = 0.0; fy = 0.0; fz = 0.0;
+    } else if (mtop < 1e-12) {
+        fx = bx; fy = by; fz = bz;
+    } else if (mbot < 1e-12) {
+        fx = tx; fy = ty; fz = tz;
+    } else {
+        const double c = 1.0 - tparam;
+        fx = c * bx + tparam * tx;
+        fy = c * by + tparam * ty;
+        fz = c * bz + tparam * tz;
+    }
+    double u_east, v_north;
+    remap_enu(px, py, pz, fx, fy, fz, u_east, v_north);
+    const double spd = sqrt(u_east * u_east + v_north * v_north);
+    remap_set_pixel(a.img0, g, u_east, v_north, spd);
+    if (a.img1) {  // :443-469: x = the first attribute, y = the second, both at level clamp(local_layer - 1)
+        const double a0 = remap_attribute<MAXV>(a, s, j, a.attr0);
+        const double a1 = remap_attribute<MAXV>(a, s, j, a.attr1);
+        remap_set_pixel(a.img1, g, a0, a1, 0.0);
+    }
+}
+
+template <int MAXV>
+__global__ void __launch_bounds__(256) remap_fixed_latitude_kernel(RemapArgs a) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= a.n) return;
+    const double nan = __builtin_nan("");
+    const int ih = (int)(g / a.W);
+    const int jw = (int)(g - (int64_t)ih * a.W);
+    const double depth_plot = a.min_depth + ih * a.i_step;  // :536
+    const double DEPTH = -fabs(depth_plot);
+    const int cell = a.cells[jw];
+    const double px = a.pts[3 * jw], py = a.pts[3 * jw + 1], pz = a.pts[3 * jw + 2];
+    RemapStencil<MAXV> s;
+    bool ok = cell >= 0 && cell < a.C;                              // :545
+    if (ok) ok = remap_stencil<MAXV, true>(a, cell, px, py, pz, s);  // :551-570
+    int layer = -1;
+    double z0 = 0.0, zlast = 0.0, up = 0.0, dn = 0.0;
+    if (ok) {
+        const double EPSILON = 1e-6;
+        layer = remap_column<MAXV>(a, s, DEPTH, EPSILON, z0, zlast, up, dn);
+        if (DEPTH > z0 + EPSILON || DEPTH < zlast - EPSILON) ok = false;  // :592
+        if (layer == -1) ok = false;                                      // :609
+    }
+    double denom = 0.0;
+    if (ok) {
+        if (up < dn) { const double t = up; up = dn; dn = t; }
+        denom = up - dn;
+        if (fabs(denom) < 1e-30) ok = false;  // :621
+    }
+    if (!ok) {
+        remap_set_pixel(a.img0, g, nan, nan, nan);
+        return;
+    }
+    const double t = (DEPTH - dn) / denom;
+    double ux, uy, uz, dx, dy, dz;
+    remap_velocity<MAXV>(a, s, layer - 1, ux, uy, uz);
+    remap_velocity<MAXV>(a, s, layer, dx, dy, dz);
+    const double c = 1.0 - t;
+    const double fx = c * dx + t * ux, fy = c * dy + t * uy, fz = c * dz + t * uz;
+    double zonal, meridional;
+    remap_enu(px, py, pz, fx, fy, fz, zonal, meridional);
+    remap_set_pixel(a.img0, g, zonal, meridional, 0.0);
+}
+
+// GeoConverter::convertPixelToLatLonToRadians (GeoConverter.hpp:28-32) per row / per column, then the
+// libm cos / sin of convertRadianLatLonToXYZ (:120-121)
+void remap_depth_tables(const mops_remap_cfg* c, double* row_cos, double* row_sin, double* col_cos, double* col_sin) {
+    const int width = c->width, height = c->height;
+    for (int i = 0; i < height; ++i) {
+        double lat = c->max_lat - (static_cast<double>(i) / static_cast<double>(height) * (c->max_lat - c->min_lat));
+        lat = lat * (M_PI / 180.0);
+        row_cos[i] = std::cos(lat); row_sin[i] = std::sin(lat);
+    }
+    for (int j = 0; j < width; ++j) {
+        double lon = (static_cast<double>(j) / static_cast<double>(width) * (c->max_lon - c->min_lon)) + c->min_lon;
+        lon = lon * (M_PI / 180.0);
+        col_cos[j] = std::cos(lon); col_sin[j] = std::sin(lon);
+    }
+}
+
+// VisualizeFixedLatitude's positions (MPASOVisualizerKernels.cpp:513-523): one row at FixedLatitude,
+// lon = minLon + jw * j_step
+void remap_latitude_tables(const mops_remap_cfg* c, double* row_cos, double* row_sin, double* col_cos,
+                           double* col_sin) {
+    const int width = c->width;
+    const double j_step = (width > 1) ? (c->max_lon - c->min_lon) / (width - 1) : 0.0;
+    const double lat = c->fixed_latitude * (M_PI / 180.0);
+    row_cos[0] = std::cos(lat); row_sin[0] = std::sin(lat);
+    for (int jw = 0; jw < width; ++jw) {
+        const double lon = c->min_lon + jw * j_step;
+        const double phi = lon * (M_PI / 180.0);
+        col_cos[jw] = std::cos(phi); col_sin[jw] = std::sin(phi);
+    }
+}
+
+mops_status remap_check(const char* what, const mops_mesh* mesh, const mops_field* field, const mops_remap_cfg* cfg,
+                        const void* d_out) {
+    if (!mesh || !field || !cfg || !d_out) return fail(MOPS_ERR_INVALID, std::string(what) + ": invalid inputs");
+    if (cfg->width <= 0 || cfg->height <= 0 || (int64_t)cfg->width * cfg->height > 0x7fffffffLL)
+        return fail(MOPS_ERR_INVALID, std::string(what) + ": invalid image size");
+    if (cfg->layer_rule != MOPS_LAYER_REFERENCE && cfg->layer_rule != MOPS_LAYER_BRACKET)
+        return fail(MOPS_ERR_INVALID, std::string(what) + ": invalid layer rule");
+    if (field->mesh != mesh) return fail(MOPS_ERR_INVALID, std::string(what) + ": the field belongs to another mesh");
+    return MOPS_OK;
+}
+
+RemapArgs remap_args(const mops_mesh* mesh, const mops_field* f, const mops_remap_cfg* cfg) {
+    RemapArgs a{};
+    a.W = cfg->width;
+    a.C = mesh->C; a.V = mesh->V; a.L = mesh->L; a.rec_ints = mesh->rec_ints;
+    a.cellrec = mesh->d_cellrec; a.vxyz = mesh->d_vxyz;
+    a.zt = f->d_zt; a.pr = mesh->L >= 2 ? f->d_pr : nullptr; a.vel = f->d_vel;
+    a.vold = mesh->d_vold;
+    a.bracket = cfg->layer_rule == MOPS_LAYER_BRACKET;
+    return a;
+}
+
+void launch_remap_depth(int maxv, const RemapArgs& a, hipStream_t s) {
+    const unsigned grid = grid_for(a.n);
+    if (maxv <= 7) remap_fixed_depth_kernel<7><<<grid, 256, 0, s>>>(a);
+    else if (maxv <= 12) remap_fixed_depth_kernel<12><<<grid, 256, 0, s>>>(a);
+    else remap_fixed_depth_kernel<20><<<grid, 256, 0, s>>>(a);
+}
+
+void launch_remap_latitude(int maxv, const RemapArgs& a, hipStream_t s) {
+    const unsigned grid = grid_for(a.n);
+    if (maxv <= 7) remap_fixed_latitude_kernel<7><<<grid, 256, 0, s>>>(a);
+    else if (maxv <= 12) remap_fixed_latitude_kernel<12><<<grid, 256, 0, s>>>(a);
+    else remap_fixed_latitude_kernel<20><<<grid, 256, 0, s>>>(a);
+}
+
+// positions -> locate -> `eval` on one scratch allocation: tables [2 rows + 2 W] | points [np][3] | cells [np]
+template <typename Eval>
+mops_status remap_run(const mops_mesh* mesh, int rows, int W, const std::vector<double>& tables, int32_t* d_cells,
+                      float* h_stage_ms, hipStream_t s, Eval eval) {
+    const int64_t np = (int64_t)rows * W;
+    const size_t ntab = tables.size();
+    double* scratch = nullptr;
+    int32_t* own_cells = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    mops_status st = MOPS_OK;
+    do {
+        if ((st = dmalloc(&scratch, ntab + (size_t)np * 3, nullptr)) != MOPS_OK) break;
+        if (!d_cells) {
+            if ((st = dmalloc(&own_cells, (size_t)np, nullptr)) != MOPS_OK) break;
+            d_cells = own_cells;
+        }
+        hipError_t e = hipMemcpyAsync(scratch, tables.data(), ntab * sizeof(double), hipMemcpyHostToDevice, s);
+        for (int k = 0; k < 4 && e == hipSuccess && h_stage_ms; ++k) e = hipEventCreate(&ev[k]);
+        if (e != hipSuccess) { st = fail(MOPS_ERR_HIP, std::string("remap: ") + hipGetErrorString(e)); break; }
+        double* pts = scratch + ntab;
+        if (h_stage_ms) (void)hipEventRecord(ev[0], s);
+        remap_positions_kernel<<<grid_for(np), 256, 0, s>>>(np, W, scratch, scratch + rows, scratch + 2 * rows,
+                                                           scratch + 2 * rows + W, pts);
+        if (h_stage_ms) (void)hipEventRecord(ev[1], s);
+        if ((st = mops_locate_cells(mesh, np, pts, d_cells, s)) != MOPS_OK) break;
+        if (h_stage_ms) (void)hipEventRecord(ev[2], s);
+        eval(pts, d_cells);
+        if (h_stage_ms) (void)hipEventRecord(ev[3], s);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { st = fail(MOPS_ERR_HIP, std::string("remap: ") + hipGetErrorString(e)); break; }
+        for (int k = 0; k < 3 && h_stage_ms; ++k) (void)hipEventElapsedTime(&h_stage_ms[k], ev[k], ev[k + 1]);
+    } while (0);
+    for (int k = 0; k < 4; ++k)
+        if (ev[k]) (void)hipEventDestroy(ev[k]);
+    (void)hipFree(scratch);
+    (void)hipFree(own_cells);
+    return st;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t mops_remap_num_images(int32_t n_attr) { return n_attr > 0 ? 1 + (n_attr + 2) / 3 : 1; }
+
+mops_status mops_remap_tables(const mops_remap_cfg* cfg, int32_t fixed_latitude, double* h_row_cos, double* h_row_sin,
+                              double* h_col_cos, double* h_col_sin) {
+    if (!cfg || !h_row_cos || !h_row_sin || !h_col_cos || !h_col_sin || cfg->width <= 0 || cfg->height <= 0)
+        return fail(MOPS_ERR_INVALID, "mops_remap_tables: invalid argument");
+    if (fixed_latitude) remap_latitude_tables(cfg, h_row_cos, h_row_sin, h_col_cos, h_col_sin);
+    else remap_depth_tables(cfg, h_row_cos, h_row_sin, h_col_cos, h_col_sin);
+    return MOPS_OK;
+}
+
+mops_status mops_remap_fixed_depth(const mops_mesh* mesh, const mops_field* field, const mops_remap_cfg* cfg,
+                                   int32_t n_attr, const double* d_attr0, const double* d_attr1, double* d_images,
+                                   int32_t* d_cells, float* h_stage_ms, void* stream) {
+    MOPS_TRY(remap_check("mops_remap_fixed_depth", mesh, field, cfg, d_images));
+    if (n_attr < 0 || (n_attr >= 2 && (!d_attr0 || !d_attr1)))
+        return fail(MOPS_ERR_INVALID, "mops_remap_fixed_depth: invalid attribute arrays");
+    hipStream_t s = (hipStream_t)stream;
+    const int W = cfg->width, H = cfg->height;
+    const int64_t n = (int64_t)W * H;
+    const int n_img = mops_remap_num_images(n_attr);
+    const bool two = n_attr > 1;  // bDoubleAttributes (:261): image 1 is written only then
+    // ImageBuffer's zero fill (ImageBuffer.hpp:15) for the images the kernel never writes
+    if (n_img > (two ? 2 : 1))
+        HIP_TRY(hipMemsetAsync(d_images + (size_t)(two ? 2 : 1) * n * 4, 0,
+                               (size_t)(n_img - (two ? 2 : 1)) * n * 4 * sizeof(double), s));
+    std::vector<double> tables(2 * (size_t)H + 2 * (size_t)W);
+    remap_depth_tables(cfg, tables.data(), tables.data() + H, tables.data() + 2 * H, tables.data() + 2 * H + W);
+    RemapArgs a = remap_args(mesh, field, cfg);
+    a.n = n;
+    a.depth = -cfg->fixed_depth;  // :251
+    a.img0 = d_images;
+    a.img1 = two ? d_images + n * 4 : nullptr;
+    a.attr0 = two ? d_attr0 : nullptr;
+    a.attr1 = two ? d_attr1 : nullptr;
+    const int maxv = mesh->maxv;
+    return remap_run(mesh, H, W, tables, d_cells, h_stage_ms, s, [&](const double* pts, const int32_t* cells) {
+        a.pts = pts; a.cells = cells;
+        launch_remap_depth(maxv, a, s);
+    });
+}
+
+mops_status mops_remap_fixed_latitude(const mops_mesh* mesh, const mops_field* field, const mops_remap_cfg* cfg,
+                                      double* d_image, int32_t* d_cells, void* stream) {
+    MOPS_TRY(remap_check("mops_remap_fixed_latitude", mesh, field, cfg, d_image));
+    hipStream_t s = (hipStream_t)stream;
+    const int W = cfg->width, H = cfg->height;
+    std::vector<double> tables(2 + 2 * (size_t)W);
+    remap_latitude_tables(cfg, tables.data(), tables.data() + 1, tables.data() + 2, tables.data() + 2 + W);
+    RemapArgs a = remap_args(mesh, field, cfg);
+    a.n = (int64_t)W * H;
+    a.min_depth = cfg->min_depth;
+    a.i_step = (H > 1) ? (cfg->max_depth - cfg->min_depth) / (H - 1) : 0.0;  // :513
+    a.img0 = d_image;
+    const int maxv = mesh->maxv;
+    return remap_run(mesh, 1, W, tables, d_cells, nullptr, s, [&](const double* pts, const int32_t* cells) {
+        a.pts = pts; a.cells = cells;
+        launch_remap_latitude(maxv, a, s);
+    });
+}
+
+}  // extern "C"

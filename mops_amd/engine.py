@@ -633,3 +633,105 @@ class ParticleSet:
                 e1.record(ts)
                 timing.append((e0, e1))
         return dict(points=pts, velocity=vel, temperature=tmp, salinity=sal, lastPoint=last)
+
+
+LAYER_RULES = {"reference": L.MOPS_LAYER_REFERENCE, "bracket": L.MOPS_LAYER_BRACKET}
+
+
+def _remap_cfg(width, height, lat_range=(0.0, 0.0), lon_range=(0.0, 0.0), depth=0.0, latitude=0.0,
+               depth_range=(0.0, 0.0), layer_rule="reference") -> L.RemapCfg:
+    if layer_rule not in LAYER_RULES:
+        raise ValueError(f"layer_rule must be one of {sorted(LAYER_RULES)}, not {layer_rule!r}")
+    width, height = int(width), int(height)
+    if width <= 0 or height <= 0 or width * height > 0x7fffffff:
+        raise ValueError(f"invalid image size {width} x {height}")
+    return L.RemapCfg(width, height, float(lat_range[0]), float(lat_range[1]), float(lon_range[0]),
+                      float(lon_range[1]), float(depth), float(latitude), float(depth_range[0]),
+                      float(depth_range[1]), LAYER_RULES[layer_rule])
+
+
+def remap_tables(width, height, lat_range=(0.0, 0.0), lon_range=(0.0, 0.0), latitude=None):
+    """The host cos / sin tables the remapping kernels form pixel positions from (mops_remap_tables; no
+    device work): (row_cos, row_sin, col_cos, col_sin).  ``latitude`` None: the fixed-depth image's rows
+    and columns; else the fixed-latitude image's one row and its columns."""
+    cfg = _remap_cfg(width, height, lat_range, lon_range, latitude=0.0 if latitude is None else latitude)
+    rows = int(height) if latitude is None else 1
+    rc, rs = np.empty(rows), np.empty(rows)
+    cc, cs = np.empty(int(width)), np.empty(int(width))
+    L.check(L.load().mops_remap_tables(C.byref(cfg), 0 if latitude is None else 1, _ptr(rc), _ptr(rs), _ptr(cc),
+                                       _ptr(cs)), "mops_remap_tables")
+    return rc, rs, cc, cs
+
+
+def cell_to_vertex_attr(mesh: DeviceMesh, cell_attr):
+    """CalcCellCenterToVertex for one double attribute (mops_cell_to_vertex_attr): a [C*L] array (numpy or
+    CUDA tensor) -> a [V, L] float64 CUDA tensor in the caller's vertex order, on torch's current stream."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if not isinstance(cell_attr, torch.Tensor):
+        cell_attr = torch.as_tensor(np.ascontiguousarray(cell_attr, dtype=np.float64).reshape(-1))
+    src = cell_attr.to(device=dev, dtype=torch.float64).contiguous()
+    if src.numel() != mesh.nCells * mesh.nVertLevels:
+        raise ValueError("attribute is not [nCells * nVertLevels]")
+    out = torch.empty((mesh.nVertices, mesh.nVertLevels), dtype=torch.float64, device=dev)
+    L.check(L.load().mops_cell_to_vertex_attr(mesh.handle, C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()),
+                                              _stream_handle(torch.cuda.current_stream(dev).cuda_stream)),
+            "mops_cell_to_vertex_attr")
+    return out
+
+
+def _vertex_attr_ptr(mesh: DeviceMesh, t, name: str):
+    if not (t.is_cuda and t.dtype.is_floating_point and t.element_size() == 8 and t.is_contiguous()
+            and t.numel() == mesh.nVertices * mesh.nVertLevels):
+        raise ValueError(f"{name}: expected a contiguous float64 CUDA tensor [nVertices, nVertLevels]")
+    return C.c_void_p(t.data_ptr())
+
+
+def remap_fixed_depth(mesh: DeviceMesh, field: DeviceField, width: int, height: int, lat_range, lon_range,
+                      depth: float, n_attr: int = 0, vertex_attrs=(), layer_rule: str = "reference",
+                      return_cells: bool = False, stage_ms: list | None = None, stream=None):
+    """MOPSApp::runRemapping (mops_remap_fixed_depth): the fixed-depth images as one float64 CUDA tensor
+    [n_images, height, width, 4], n_images = 1 + ceil(n_attr / 3) (1 without attributes).
+
+    ``n_attr``: the solution's double-attribute count; with two or more, ``vertex_attrs`` holds the vertex
+    arrays (``cell_to_vertex_attr``) of the first two in name order.  ``layer_rule``: "reference" (every wet
+    pixel is layer 0, quirk Q13) or "bracket".  ``return_cells``: also the int32 [height, width] cell map.
+    ``stage_ms``: a list that receives the positions / locate / evaluation times (HIP events, ms)."""
+    import torch
+    cfg = _remap_cfg(width, height, lat_range, lon_range, depth=depth, layer_rule=layer_rule)
+    n_attr = int(n_attr)
+    if n_attr < 0 or (n_attr > 1 and len(vertex_attrs) < 2):
+        raise ValueError("n_attr > 1 needs the first two attributes' vertex arrays")
+    lib = L.load()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    a = [_vertex_attr_ptr(mesh, vertex_attrs[k], f"vertex_attrs[{k}]") if n_attr > 1 else None for k in range(2)]
+    images = torch.empty((int(lib.mops_remap_num_images(n_attr)), cfg.height, cfg.width, 4), dtype=torch.float64,
+                         device=dev)
+    cells = torch.empty((cfg.height, cfg.width), dtype=torch.int32, device=dev) if return_cells else None
+    ms = (C.c_float * 3)() if stage_ms is not None else None
+    h = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    L.check(lib.mops_remap_fixed_depth(mesh.handle, field.handle, C.byref(cfg), n_attr, a[0], a[1],
+                                       C.c_void_p(images.data_ptr()),
+                                       None if cells is None else C.c_void_p(cells.data_ptr()), ms,
+                                       _stream_handle(h)), "mops_remap_fixed_depth")
+    if stage_ms is not None:
+        stage_ms[:] = [float(x) for x in ms]
+    return (images, cells) if return_cells else images
+
+
+def remap_fixed_latitude(mesh: DeviceMesh, field: DeviceField, width: int, height: int, lon_range,
+                         latitude: float, depth_range, return_cells: bool = False, stream=None):
+    """MOPSApp::runReGrid (mops_remap_fixed_latitude): one float64 CUDA tensor [height, width, 4]; rows are
+    depths from depth_range[0] to depth_range[1] (the grid's refBottomDepth front / back), columns
+    longitudes at ``latitude``.  ``return_cells``: also the int32 [width] cell of each column."""
+    import torch
+    cfg = _remap_cfg(width, height, lon_range=lon_range, latitude=latitude, depth_range=depth_range)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    image = torch.empty((cfg.height, cfg.width, 4), dtype=torch.float64, device=dev)
+    cells = torch.empty((cfg.width,), dtype=torch.int32, device=dev) if return_cells else None
+    h = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    L.check(L.load().mops_remap_fixed_latitude(mesh.handle, field.handle, C.byref(cfg),
+                                               C.c_void_p(image.data_ptr()),
+                                               None if cells is None else C.c_void_p(cells.data_ptr()),
+                                               _stream_handle(h)), "mops_remap_fixed_latitude")
+    return (image, cells) if return_cells else image

@@ -1,12 +1,14 @@
 """pyMOPS-compatible Python API for the MI355X trajectory engine.
 
-Mirrors the trajectory surface of the reference's pybind module
-(tools/pyMOPS/bindings.cpp:23-455): the same enum, class and function names,
-the same argument meaning and the same return layout, so a pyMOPS script's
-trajectory part runs unchanged with ``from mops_amd import pyMOPS``:
+Mirrors the trajectory and image-remapping surface of the reference's pybind
+module (tools/pyMOPS/bindings.cpp:23-455): the same enum, class and function
+names, the same argument meaning and the same return layout, so a pyMOPS
+script runs unchanged with ``from mops_amd import pyMOPS``:
 
     MOPS_Init / MOPS_Begin / MOPS_AddGridMesh / MOPS_AddAttribute / MOPS_End /
     MOPS_ActiveAttribute                       (bindings.cpp:281-286)
+    MOPS_RunRemapping(VisualizationSettings)   -> [ (H, W, 4) float64 ]   (:287-299)
+    MOPS_RunReGrid(VisualizationSettings)      -> (H, W, 4) float64       (:301-309)
     MOPS_GenerateSeedsPoints(SeedsSettings)    -> (N, 3) float64   (:311-327)
     MOPS_RunStreamLine(cfg, (N, 3))            -> [ {lineID, points, velocity} ]           (:328-381)
     MOPS_RunPathLine(cfg, (N, 3))              -> [ {lineID, points, velocity, temperature,
@@ -14,11 +16,13 @@ trajectory part runs unchanged with ``from mops_amd import pyMOPS``:
     MOPS_ResetTiming / MOPS_PrintTimingSummary / MOPS_PrintTimingDetailed /
     MOPS_GetCategoryTime / MOPS_GetTotalTime   (:457-475)
 
-Every trajectory goes through the HIP engine (``engine.run_trajectories`` on
-the C ABI); there is no CPU path.  ``MPASOReader`` / ``init_from_reader``
-load MPAS netCDF classic files (mops_amd/mpas.py).  Out of scope:
-image remapping (``MOPS_RunRemapping`` / ``MOPS_RunReGrid``) raises
-``NotImplementedError``.
+Every trajectory and every image goes through the HIP engine
+(``engine.run_trajectories`` / ``engine.remap_fixed_depth`` /
+``engine.remap_fixed_latitude`` on the C ABI); there is no CPU path.
+``MPASOReader`` / ``init_from_reader`` load MPAS netCDF classic files
+(mops_amd/mpas.py).  ``VisualizationSettings.layerRule`` is the one extension:
+"reference" (default) keeps the reference's layer override, "bracket" drops it
+(DESIGN.md quirk Q13).
 """
 from __future__ import annotations
 
@@ -43,6 +47,32 @@ class CalcDirection(enum.IntEnum):
 class CalcMethodType(enum.IntEnum):
     kRK4 = 0
     kEuler = 1
+
+
+class CalcPositionType(enum.IntEnum):
+    kCenter = 0
+    kVertx = 1
+    kPoint = 2
+
+
+class CalcAttributeType(enum.IntEnum):
+    kZonalMerimoal = 0
+    kVelocity = 1
+    kZTop = 2
+    kTemperature = 3
+    kSalinity = 4
+    kAll = 5
+
+
+class VisualizeType(enum.IntEnum):
+    kFixedLayer = 0
+    kFixedDepth = 1
+
+
+class SaveType(enum.IntEnum):
+    kVTI = 0
+    kPNG = 1
+    kNone = 2
 
 
 class GridAttributeType(enum.IntEnum):
@@ -93,10 +123,12 @@ class MPASOGrid:
         self.mVertLevels = self.mVertLevelsP1 = 0
         self.vec3 = {}
         self.ints = {}
+        self.cellRefBottomDepth_vec = np.empty(0)   # [L] (MPASOGrid.h:79), the fixed-latitude image's rows
 
     def init_from_reader(self, reader):
         """MPASOGrid::initGrid(MPASOReader*) (MPASOGrid.cpp:190-230)."""
         G = GridAttributeType
+        self.cellRefBottomDepth_vec = np.asarray(getattr(reader, "cellRefBottomDepth_vec", np.empty(0)), dtype=np.float64)
         self.mCellsSize, self.mEdgesSize = reader.mCellsSize, reader.mEdgesSize
         self.mMaxEdgesSize, self.mVertexSize = reader.mMaxEdgesSize, reader.mVertexSize
         self.mVertLevels, self.mVertLevelsP1 = reader.mVertLevels, reader.mVertLevelsP1
@@ -238,6 +270,32 @@ class TrajectorySettings:
         return len(self.particle_depths) > 0
 
 
+class VisualizationSettings:
+    """VisualizationSettings as bound by pyMOPS (bindings.cpp:174-218; src/Core/MPASOVisualizer.h:20-42).
+    ``layerRule`` ("reference" / "bracket") is this engine's extension."""
+
+    def __init__(self):
+        self.imageSize = (0.0, 0.0)         # (width, height)
+        self.LatRange = (0.0, 0.0)
+        self.LonRange = (0.0, 0.0)
+        self.DepthRange = (0.0, 0.0)
+        self.FixedLatitude = 0.0
+        self.FixedDepth = 0.0
+        self.TimeStep = 0.0
+        self.CalcType = CalcAttributeType.kZonalMerimoal
+        self.VisType = VisualizeType.kFixedDepth
+        self.PositionType = CalcPositionType.kPoint
+        self.SaveType = SaveType.kNone
+        self.layerRule = "reference"
+
+    def __setattr__(self, name, value):
+        if name in ("imageSize", "LatRange", "LonRange", "DepthRange"):
+            if len(value) != 2:
+                raise RuntimeError(f"{name} must be a tuple of size 2")
+            value = (float(value[0]), float(value[1]))
+        object.__setattr__(self, name, value)
+
+
 class SeedsSettings:
     """SamplingSettings as bound by pyMOPS (bindings.cpp:225-241)."""
 
@@ -319,6 +377,8 @@ class _App:
         self.fields: dict[int, _E.DeviceField] = {}
         self.front = None
         self.back = None
+        self.front_id = None
+        self.vertex_attrs = {}  # solID -> the first two attributes' vertex arrays (device), built on first use
 
 
 _app = _App()
@@ -387,7 +447,8 @@ def MOPS_End():
             _app.fields[sid] = _E.DeviceField.from_snapshot(_app.mesh, snap,
                                                             velocity="rbf" if rbf[sid] else "zonal")
         if _app.fields:
-            _app.front = _app.fields[min(_app.fields)]
+            _app.front_id = min(_app.fields)
+            _app.front = _app.fields[_app.front_id]
 
 
 def MOPS_ActiveAttribute(t1: int, t2: int | None = None):
@@ -396,6 +457,7 @@ def MOPS_ActiveAttribute(t1: int, t2: int | None = None):
         _error(f"[MOPSApp]::activeAttribute: solID {t1 if t1 not in _app.fields else t2} not found")
         return
     _app.front = _app.fields[t1]
+    _app.front_id = t1
     _app.back = None if t2 is None else _app.fields[t2]
 
 
@@ -476,9 +538,46 @@ def MOPS_RunPathLine(config: TrajectorySettings, sample_points_np):
                  "depth": float(eff[i])} for i in range(len(seeds))]
 
 
-def MOPS_RunRemapping(config):
-    raise NotImplementedError("image remapping is out of scope for the trajectory engine (DESIGN.md)")
+def _front_vertex_attrs():
+    """The active front solution's attribute count and, with two or more, the vertex arrays of the first two
+    in name order (the reference's std::map order: mDoubleAttributes_CtoV), built on the device once per
+    solution (CalcCellCenterToVertex, MOPSApp.cpp:121-127)."""
+    sol = _app.sols.get(_app.front_id)
+    names = sorted(sol.mDoubleAttributes) if sol is not None else []
+    if len(names) < 2:
+        return len(names), ()
+    if _app.front_id not in _app.vertex_attrs:
+        _app.vertex_attrs[_app.front_id] = tuple(_E.cell_to_vertex_attr(_app.mesh, sol.mDoubleAttributes[k])
+                                                 for k in names[:2])
+    return len(names), _app.vertex_attrs[_app.front_id]
 
 
-def MOPS_RunReGrid(config):
-    raise NotImplementedError("regridding is out of scope for the trajectory engine (DESIGN.md)")
+def MOPS_RunRemapping(config: VisualizationSettings):
+    """MOPSApp::runRemapping (MOPSApp.cpp:171-196) -> a list of [H, W, 4] float64 arrays (bindings.cpp:287-299)."""
+    with _Timer("GPUKernel::Remapping", "GPUKernel"):
+        if config is None or _app.mesh is None or _app.front is None:  # MPASOVisualizerKernels.cpp:240-243
+            _error("[MI355X::VisualizeFixedDepth] invalid inputs")
+            return []
+        w, h = int(config.imageSize[0]), int(config.imageSize[1])
+        n_attr, vattrs = _front_vertex_attrs()
+        images = _E.remap_fixed_depth(_app.mesh, _app.front, w, h, config.LatRange, config.LonRange,
+                                      float(config.FixedDepth), n_attr=n_attr, vertex_attrs=vattrs,
+                                      layer_rule=getattr(config, "layerRule", "reference"))
+        host = images.cpu().numpy()
+        return [host[k] for k in range(host.shape[0])]
+
+
+def MOPS_RunReGrid(config: VisualizationSettings):
+    """MOPSApp::runReGrid (MOPSApp.cpp:198-210) -> one [H, W, 4] float64 array (bindings.cpp:301-309)."""
+    with _Timer("GPUKernel::ReGrid", "GPUKernel"):
+        w, h = int(config.imageSize[0]), int(config.imageSize[1])
+        if _app.mesh is None or _app.front is None or w <= 0 or h <= 0:  # MPASOVisualizerKernels.cpp:475-485
+            _error("[MI355X::VisualizeFixedLatitude] invalid inputs")
+            return np.zeros((max(h, 0), max(w, 0), 4))
+        ref = np.asarray(_app.grid.cellRefBottomDepth_vec, dtype=np.float64).reshape(-1)
+        if ref.size == 0:  # :491-494
+            _error("[MI355X::VisualizeFixedLatitude] refBottomDepth is empty")
+            return np.zeros((h, w, 4))
+        image = _E.remap_fixed_latitude(_app.mesh, _app.front, w, h, config.LonRange, float(config.FixedLatitude),
+                                        (float(ref[0]), float(ref[-1])))
+        return image.cpu().numpy()
