@@ -108,8 +108,21 @@ int32_t mops_abi_version(void);
  * sqrt()} pairs, op 1 writes {fast sin, sin(), fast cos, cos()} (|x| < 0.78
  * only; other x copy the library values) into d_out (2n or 4n doubles); op 2
  * reads n 3-vectors (3n doubles) and writes {fast a_j / |a| (j = 0..2), a_j / |a|}
- * (6n doubles; zeros where |a| <= 1e-12). */
+ * (6n doubles; zeros where |a| <= 1e-12).  Op 3 reads d_x[0] = a number of
+ * steps N and writes the pathline time fractions (double)i / (double)N, i < n,
+ * divided on the device (n doubles).  Op 4 reads n pairs (a, b) and writes {a / b
+ * by the no-scale division where both lie in its window (else `/`), a / b, 1.0
+ * where the no-scale division ran} (3n doubles).  Op 5 reads n hexagons as {6
+ * Wachspress numerators 4 B_i, 6 doubled triangle areas R_i} (12n doubles) and
+ * writes {6 weights by the evaluation's guarded quotient block, 6 by the plain
+ * block, 1.0 where the guard passed} (13n doubles). */
 mops_status mops_selftest_math(int64_t n, const double* d_x, double* d_out, int32_t op, void* stream);
+
+/* The pathline kernels' per-run table of time fractions, as built on the host:
+ * h_out[s] = (double)s / (double)n_steps for s < n_steps (nothing is written for
+ * n_steps <= 0, past the cap or h_out NULL).  Returns the cap: the largest
+ * n_steps a run gets a table for; a longer run divides per step.  No device. */
+int64_t mops_traj_alpha_table(int64_t n_steps, double* h_out);
 
 /* Self-test of the trajectory kernel's exact neighbour-table shortcut (not a
  * reference entry point; maxEdges <= 7 meshes): for n points d_pts [n][3] in

@@ -21,6 +21,7 @@ EXPORTED = (
     "mops_locate_cells", "mops_locate_cells_hinted", "mops_order_particles", "mops_order_scratch_bytes",
     "mops_order_particles_live", "mops_permute_arrays", "mops_records_clear_dead",
     "mops_traj_num_records", "mops_traj_num_steps", "mops_traj_advance", "mops_traj_finalize", "mops_traj_last_points",
+    "mops_traj_alpha_table",
     "mops_remove_nan_lines", "mops_remove_nan_ragged", "mops_run_trajectories", "mops_build_id",
     "mops_remap_num_images", "mops_remap_tables", "mops_remap_fixed_depth", "mops_remap_fixed_latitude",
     # include/mops_io.h
@@ -115,6 +116,8 @@ def load(path: str | None = None):
     lib.mops_build_id.restype = C.c_char_p
     if hasattr(lib, "mops_selftest_math"):  # (older engine builds timed as variants lack the self-test)
         lib.mops_selftest_math.argtypes = [I64, P, P, I32, P]; lib.mops_selftest_math.restype = st
+    if hasattr(lib, "mops_traj_alpha_table"):  # (likewise)
+        lib.mops_traj_alpha_table.argtypes = [I64, P]; lib.mops_traj_alpha_table.restype = I64
     if hasattr(lib, "mops_selftest_walk"):
         lib.mops_selftest_walk.argtypes = [P, I64, P, P, P, P]; lib.mops_selftest_walk.restype = st
     lib.mops_mesh_create.argtypes = [P, P, P]; lib.mops_mesh_create.restype = st

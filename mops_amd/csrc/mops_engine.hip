@@ -213,6 +213,9 @@ struct mops_mesh {
     // trajectory kernel still reads; allocated once per stream (no per-launch allocation)
     mutable std::mutex coop_mu;
     mutable std::vector<std::pair<hipStream_t, int*>> coop_flags;
+    // the pathline launches' time-fraction tables (alpha_table), one per distinct number of steps: a run's
+    // n_steps comes from its settings, so a mesh sees one or a few; built on the first launch that needs it
+    mutable std::vector<std::pair<int64_t, double*>> alpha_tabs;
 };
 
 struct mops_field {
@@ -225,7 +228,8 @@ struct mops_field {
     // [C] fast-path word (mono_kernel, read by dev::fast_ok): bit 31 = eligible, bits 20..26 = km,
     // the cell's decreasing prefix (every non-zero vertex column drops by >= 1e-6 m per level over
     // levels 0..km), bits 0..19 = which polygon slots are identically-zero columns (boundary
-    // vertices, quirk Q10)
+    // vertices, quirk Q10); bits 29-30 (a property of the mesh cell, kept here because the evaluation has
+    // this word in a register): set unless the cell's Wachspress numerators all qualify for dev::wach_fast
     uint32_t* d_mono = nullptr;
     int32_t* d_vmono = nullptr;  // [V] first level that breaks the vertex column's decrease (L = none)
     uint8_t* d_vzero = nullptr;  // [V] 1 = every level of the vertex column is 0 (boundary vertex)
@@ -447,6 +451,78 @@ __device__ __forceinline__ void xdiv_norm3(double a0, double a1, double a2, doub
     }
 #endif
     q0 = xdiv(a0, b); q1 = xdiv(a1, b); q2 = xdiv(a2, b);
+}
+
+// q = a / b for operands inside the "no scale" window, bit-identical to `/`: xdiv_norm3's sequence for one
+// quotient.  The window, from the definitions of v_div_scale_f64 / v_div_fmas_f64 / v_div_fixup_f64: div_scale
+// returns its operand unscaled and leaves VCC clear when a and b are non-zero and normal, exponent(a) -
+// exponent(b) < 768, 1 / b and a / b are normal and the biased exponent of a is above 53 (|a| >= 2^-969);
+// div_fmas with VCC clear is a plain fma; div_fixup passes a finite non-zero quotient of finite non-zero
+// normal operands through (with the sign the fma already gave it).  Both magnitudes in [2^-300, 2^300) meet all
+// of it with room to spare (|a / b| in (2^-600, 2^600), 1 / |b| in (2^-300, 2^300]).  8 instructions instead of
+// 11.  The caller tests the window (ns_window, or wach_fast's test of six denominators at once); zero,
+// subnormals, inf and NaN are outside it.  Checked bitwise against `/` (mops_selftest_math op 4).
+constexpr uint32_t kNsLo = (1023u - 300u) << 20, kNsHi = (1023u + 300u) << 20;  // high words of 2^-300, 2^300
+__device__ __forceinline__ bool ns_window(double v) {
+    return ((uint32_t)__double2hiint(v) & 0x7fffffffu) - kNsLo < kNsHi - kNsLo;
+}
+__device__ __forceinline__ double xdiv_ns(double a, double b) {
+    double r = __builtin_amdgcn_rcp(b);
+    double e = __builtin_fma(-b, r, 1.0);
+    r = __builtin_fma(r, e, r);
+    e = __builtin_fma(-b, r, 1.0);
+    r = __builtin_fma(r, e, r);
+    const double q = a * r;
+    return __builtin_fma(__builtin_fma(-b, q, a), r, q);
+}
+
+// The Wachspress quotients w_i = N_i / D_i / sum_j (N_j / D_j) of a polygon with a compile-time vertex count
+// through xdiv_ns, all seven divisions under one test (MOPS_WACH_NS).  w[] holds the denominators D_i = R_i
+// R_{i+1} on entry: products of square roots, so +0 or above, or NaN -- as bit patterns their high words order
+// like unsigned integers, and a sign bit (a negative NaN, -0) reads as a huge one.  One unsigned min/max chain
+// over the six high words tests them all against [2^-190, 2^190); zero, subnormals, inf and NaN fail it.  The
+// numerators N_i = 4 B_i are per-cell constants, qualified once per cell: `cell_bad` is kWachCellBad (above the
+// window's upper bound) unless all of them lie in [2^-100, 2^100) (wach_cell_bad), and rides in the max chain.
+// Inside the test every q_i = N_i / D_i is finite, in (2^-290, 2^290), and so is their sum (in the same order
+// as the plain block): sum >= q_i > 0 since rounding is monotone, sum < 6 * 2^290 -- inside xdiv_ns's window
+// with the numerator 1, no second test.  And w_i = fl(q_i fl(1 / sum)) <= fl((q_i / sum) (1 + 2^-53)) <=
+// 1 + 2^-52 is finite: weights_finite is true without looking.  Returns false, w[] untouched, when the test
+// fails (a particle on a vertex or an edge: an area of exactly 0): the caller runs the plain block.
+// Checked bitwise against the plain block (mops_selftest_math op 5).
+#ifndef MOPS_WACH_NS
+#define MOPS_WACH_NS 1
+#endif
+constexpr uint32_t kWachDenLo = (1023u - 190u) << 20, kWachDenHi = (1023u + 190u) << 20;
+constexpr uint32_t kWachNumLo = (1023u - 100u) << 20, kWachNumHi = (1023u + 100u) << 20;
+constexpr uint32_t kWachCellBad = 0x60000000u;  // two spare bits of the cell's fast-path word (mops_field::d_mono)
+static_assert(kWachCellBad >= kWachDenHi, "an unqualified cell must fail the denominator test");
+// the per-cell half of the test: nv numerators, read with stride `stride` doubles
+__device__ __forceinline__ uint32_t wach_cell_bad(const double* num, int nv, int stride) {
+    bool ok = true;
+    for (int j = 0; j < nv; ++j)
+        ok = ok && ((uint32_t)__double2hiint(num[(int64_t)j * stride]) - kWachNumLo < kWachNumHi - kWachNumLo);
+    return ok ? 0u : kWachCellBad;
+}
+template <int N>
+__device__ __forceinline__ bool wach_fast(const double* num, double* w, uint32_t cell_bad) {
+    uint32_t mn = (uint32_t)__double2hiint(w[0]), mx = cell_bad;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const uint32_t h = (uint32_t)__double2hiint(w[i]);
+        mn = h < mn ? h : mn;
+        mx = h > mx ? h : mx;
+    }
+    if (!(mn >= kWachDenLo && mx < kWachDenHi)) return false;
+    double sum = 0.0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        w[i] = xdiv_ns(num[i], w[i]);
+        sum += w[i];
+    }
+    const double recp = xdiv_ns(1.0, sum);
+#pragma unroll
+    for (int i = 0; i < N; ++i) w[i] *= recp;
+    return true;
 }
 
 // The reference's `length(v) < 1e-12` tests (MPASOVisualizerKernels.cpp:841-852)
@@ -682,11 +758,21 @@ __device__ __forceinline__ void load_cell(Cell<MAXV>& c, int cell, const int* __
 template <int NV, int MAXV>
 __device__ __forceinline__ int nverts(const Cell<MAXV>& c) { return NV > 0 ? NV : c.nv; }
 
+template <int MAXV, int NV>
+__device__ __forceinline__ bool weights_finite(const Cell<MAXV>& c, const double* w) {
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i)
+        if (i < nverts<NV>(c)) ok = ok & isfinite(w[i]);
+    return ok;
+}
+
 // guards + TBBKernel::IsInMesh + Interpolator::CalcPolygonWachspress
 // (MPASOVisualizerKernels.cpp:744-770, TBBKernel.h:21-54, Interpolation.hpp:137-165)
+// wfin: every weight is finite (weights_finite, or implied by the fast quotient block, dev::wach_fast)
 template <int MAXV, int NV, bool COOP = false, bool BAR = true>
 __device__ __forceinline__ bool weights(const Cell<MAXV>& c, int L, int V, double px, double py, double pz,
-                                        double* w, const double4* tpoly = nullptr) {
+                                        double* w, bool& wfin, const double4* tpoly = nullptr) {
     if (c.id < 0 || L <= 1 || L > kMaxLevels) return false;
     const int nv = nverts<NV>(c);
     if (nv <= 0 || nv > kMaxVertex) return false;
@@ -754,13 +840,30 @@ __device__ __forceinline__ bool weights(const Cell<MAXV>& c, int L, int V, doubl
     // (the reference also range-checks the vertex ids in its zTop loop, :776-779; mops_mesh_create
     // rejects a mesh with an out-of-range active verticesOnCell entry, so that test always passes)
     // w_i = B_i / (A_i * A_{i+1}), A_nv = A_0, summed in vertex order
+    // the denominators first, in place (w[i + 1] is still A_{i+1} when slot i reads it)
     const double A0 = w[0];
-    double sum = 0.0;
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
         if (i < nv) {
             const double An = (i + 1 >= nv) ? A0 : w[(i + 1) % MAXV];
-            w[i] = xdiv(BB[i], (w[i] * An));
+            w[i] = w[i] * An;
+        }
+    }
+    // a wave of hexagons (NV = 6): the seven divisions without scaling and fix-up steps where one test of
+    // the six denominators and the cell's flag (two spare bits of its fast-path word) allows it; any other
+    // operands -- an area of exactly 0 on a vertex or an edge, inf, NaN -- take the plain block below
+    if constexpr (MOPS_WACH_NS && NV > 0) {
+        if (__builtin_expect(wach_fast<NV>(BB, w, c.mono0 & kWachCellBad), 1)) {
+            wfin = true;
+            MOPS_MARK(220 + NV);
+            return true;
+        }
+    }
+    double sum = 0.0;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        if (i < nv) {
+            w[i] = xdiv(BB[i], w[i]);
             sum += w[i];
         }
     }
@@ -768,6 +871,7 @@ __device__ __forceinline__ bool weights(const Cell<MAXV>& c, int L, int V, doubl
 #pragma unroll
     for (int i = 0; i < MAXV; ++i)
         if (i < nv) w[i] *= recp;
+    wfin = weights_finite<MAXV, NV>(c, w);
     MOPS_MARK(220 + NV);
     return true;
 }
@@ -1117,15 +1221,6 @@ __device__ __forceinline__ bool nbr_stay(Cell<MAXV>& c, int cell, double x, doub
     return true;
 }
 
-template <int MAXV, int NV>
-__device__ __forceinline__ bool weights_finite(const Cell<MAXV>& c, const double* w) {
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i)
-        if (i < nverts<NV>(c)) ok = ok & isfinite(w[i]);
-    return ok;
-}
-
 // May the hinted fast bracket (layer_eval / bracket_mono) run for this cell,
 // field and particle, and over which levels?  `m` is the field's fast-path
 // word for the cell (mono_kernel): every vertex column is either identically
@@ -1306,10 +1401,11 @@ __device__ __forceinline__ bool eval_stream(const Cell<MAXV>& c, int L, int V, c
                                             double& wv) {
     double w[MAXV];
     MOPS_MARK(400 + NV);
-    if (!weights<MAXV, NV>(c, L, V, px, py, pz, w)) return false;
+    bool wfin;
+    if (!weights<MAXV, NV>(c, L, V, px, py, pz, w, wfin)) return false;
     Pair S;
     MOPS_MARK(410 + NV);
-    const int layer = layer_eval<MAXV, false, GR, 0>(c, w, fast_ok<MAXV, NV>(c, c.mono0, weights_finite<MAXV, NV>(c, w), w), f,
+    const int layer = layer_eval<MAXV, false, GR, 0>(c, w, fast_ok<MAXV, NV>(c, c.mono0, wfin, w), f,
                                                      L, d, hint, S);
     MOPS_MARK(420 + NV);
     if (layer < 0) return false;
@@ -1340,8 +1436,8 @@ __device__ __forceinline__ bool eval_path(const Cell<MAXV>& c, int L, int V, con
                                           const double2* tile = nullptr, int th0 = 0, int th1 = 0) {
     double w[MAXV];
     constexpr bool kBar = !COOP || (TCHK ? MOPS_SCHED_BAR_PR : MOPS_SCHED_BAR_PE);
-    if (!weights<MAXV, NV, COOP, kBar>(c, L, V, px, py, pz, w, reinterpret_cast<const double4*>(tile))) return false;
-    const bool wfin = weights_finite<MAXV, NV>(c, w);
+    bool wfin;
+    if (!weights<MAXV, NV, COOP, kBar>(c, L, V, px, py, pz, w, wfin, reinterpret_cast<const double4*>(tile))) return false;
     Pair F, B;
     const int lf = layer_eval<MAXV, true, GR, NV, COOP, TCHK>(
         c, w, fast_ok<MAXV, NV>(c, c.mono0, wfin, w), ff, L, d, hint0, F, tile + kTileOffRec, th0);
@@ -1424,8 +1520,9 @@ struct TrajArgs {
     const int* __restrict__ n_live;  // device count of leading live slots (compaction), NULL = all n
     const double4* __restrict__ cpoly;  // per-cell rotated polygon + Wachspress B_i (mops_mesh::d_cpoly)
     const double* __restrict__ cnrm;    // per-cell edge normals (mops_mesh::d_cnrm; NULL past maxEdges 7)
-    const double* __restrict__ unused0; // unused, always NULL: kept so that the kernel-argument offsets of the
-                                        // fields below stay where the measured builds have them
+    const double* alpha_tab;            // pathline: alpha(step) = step / n_steps per step (alpha_table), NULL = divide;
+                                        // in the slot of a retired argument, so that the kernel-argument offsets of
+                                        // the fields below stay where the measured builds have them
     const uint4* __restrict__ nbr;      // per-cell neighbour table (mops_mesh::d_nbr; NULL past maxEdges 7)
     const double2* __restrict__ cpolyr;  // mops_mesh::d_cpolyr (NULL past maxEdges 7)
     const uint32_t* __restrict__ crank;  // mops_mesh::d_cell_rank
@@ -1539,6 +1636,10 @@ struct LdsNormals {
 #endif
 #ifndef MOPS_W_PR_HAND
 #define MOPS_W_PR_HAND 3
+#endif
+// The pathline time fraction from the run's table instead of a division per lane and step
+#ifndef MOPS_ALPHA_TAB
+#define MOPS_ALPHA_TAB 1
 #endif
 template <int MAXV, bool PATH, bool EULER, bool COOP = false, bool HAND = false>
 struct TrajWaves {
@@ -1878,7 +1979,23 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
         double hx = 0, hy = 0, hz = 0, wv = 0;
         double nx, ny, nz;
         double alpha = 0.0;
-        if constexpr (PATH) alpha = (double)step / (double)a.n_steps;
+        if constexpr (PATH) {
+            // the run's table (alpha_table): through a constant-address-space pointer with the wave-uniform
+            // step as index this is one s_load_dwordx2 whose SGPR pair feeds the blend directly; no table
+            // (a run past kAlphaTabMax steps): the quotient itself.  The same bits either way.
+#if MOPS_ALPHA_TAB
+            using ctab_t = const double __attribute__((address_space(4)))*;
+            const ctab_t atab = (ctab_t)(uintptr_t)a.alpha_tab;
+            // (the NULL test takes the step as an input it ignores, like dev::kconst: hoisted out of the loop its
+            // result is a spilled SGPR pair, two v_readlane per step instead of this s_or + s_cmp)
+            unsigned have_tab;
+            asm("s_or_b32 %0, %1, %2" : "=s"(have_tab) : "s"((unsigned)(uintptr_t)a.alpha_tab),
+                "s"((unsigned)((uintptr_t)a.alpha_tab >> 32)), "s"(step) : "scc");
+            if (__builtin_expect(have_tab != 0u, 1)) alpha = atab[step];
+            else
+#endif
+                alpha = (double)step / (double)a.n_steps;
+        }
         if (EULER) {
             bool ok = dev::eval_at<MAXV, PATH, PairGroup<PATH, EULER>::value>(hex, c, a.L, a.V, a.f0, a.f1, x, y, z, d, alpha, hint0, hint1, hx, hy, hz, wv,
                                                                               coop, tile);
@@ -2015,6 +2132,40 @@ __global__ void selftest_math_kernel(int64_t n, const double* __restrict__ x, do
         out[6 * i + 3] = b > 1e-12 ? a0 / b : 0.0;
         out[6 * i + 4] = b > 1e-12 ? a1 / b : 0.0;
         out[6 * i + 5] = b > 1e-12 ? a2 / b : 0.0;
+        return;
+    }
+    if (op == 3) {  // x[0] = the number of steps; out[i] = the pathline kernels' alpha(i), divided on the device
+        out[i] = (double)(int)i / (double)(int64_t)x[0];
+        return;
+    }
+    if (op == 4) {  // x = n pairs (a, b); out = {a / b by xdiv_ns inside its window (else `/`), a / b, took xdiv_ns}
+        const double a = x[2 * i], b = x[2 * i + 1];
+        const bool ns = dev::ns_window(a) && dev::ns_window(b);
+        out[3 * i] = ns ? dev::xdiv_ns(a, b) : a / b;
+        out[3 * i + 1] = a / b;
+        out[3 * i + 2] = ns ? 1.0 : 0.0;
+        return;
+    }
+    if (op == 5) {  // x = n x {6 numerators 4 B_i, 6 doubled areas R_i}; out = {6 weights by the guarded block of
+                    // dev::weights, 6 by the plain block, 1.0 where the guard passed}
+        double num[6], wf[6], wp[6];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) num[j] = x[12 * i + j];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) wf[j] = wp[j] = x[12 * i + 6 + j] * x[12 * i + 6 + (j + 1) % 6];
+        double sum = 0.0;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) { wp[j] = num[j] / wp[j]; sum += wp[j]; }
+        const double recp = 1.0 / sum;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) wp[j] *= recp;
+        const bool fast = dev::wach_fast<6>(num, wf, dev::wach_cell_bad(num, 6, 1));
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            out[13 * i + j] = fast ? wf[j] : wp[j];
+            out[13 * i + 6 + j] = wp[j];
+        }
+        out[13 * i + 12] = fast ? 1.0 : 0.0;
         return;
     }
     const double v = x[i];
@@ -2763,11 +2914,13 @@ __global__ void vertex_mono_kernel(int64_t V, int L, const double* __restrict__ 
 }
 
 __global__ void mono_kernel(int64_t C, int maxv, int rec_ints, const int* cellrec, const int32_t* vfail,
-                            const uint8_t* vzero, int L, uint32_t* mono) {
+                            const uint8_t* vzero, int L, const double4* __restrict__ cpoly, uint32_t* mono) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= C) return;
     const int* r = cellrec + i * rec_ints;
     const int nv = r[0];
+    // bits 29-30: the cell's Wachspress numerators do not all qualify for the no-scale quotients (dev::wach_fast)
+    const uint32_t wbad = (nv >= 1 && nv <= maxv) ? dev::wach_cell_bad(&cpoly[i * maxv].w, nv, 4) : dev::kWachCellBad;
     bool ok = (nv >= 1 && nv <= kMaxVertex && L >= 2);
     bool any_dec = false;
     int km = L - 1;
@@ -2782,7 +2935,7 @@ __global__ void mono_kernel(int64_t C, int maxv, int rec_ints, const int* cellre
         }
     }
     ok = ok && any_dec && km >= 1;
-    mono[i] = ok ? (0x80000000u | ((uint32_t)km << 20) | zmask) : 0u;
+    mono[i] = (ok ? (0x80000000u | ((uint32_t)km << 20) | zmask) : 0u) | wbad;
 }
 
 // The neighbour table of dev::nbr_stay (maxEdges <= 7): the centre c (doubles), the offsets q_k - c of
@@ -3180,6 +3333,7 @@ void free_mesh(mops_mesh* m) {
     (void)hipFree(m->d_eoc); (void)hipFree(m->d_coe); (void)hipFree(m->d_exyz); (void)hipFree(m->d_rbf_coef);
     (void)hipFree(m->d_rbf_slot);
     for (auto& f : m->coop_flags) (void)hipFree(f.second);
+    for (auto& t : m->alpha_tabs) (void)hipFree(t.second);
     (void)hipFree(m->d_vold);
     delete m;
 }
@@ -3251,6 +3405,34 @@ static mops_status coop_flag(const mops_mesh* mesh, hipStream_t s, int** out) {
     return MOPS_OK;
 }
 
+// The pathline kernels' time fraction alpha(step) = (double)step / (double)n_steps as a table (TrajArgs::alpha_tab):
+// the same correctly rounded IEEE quotient of the same two doubles, computed once on the host instead of in every
+// lane at every step.  The kernel reads it with scalar loads (the step index is wave-uniform).  At most
+// kAlphaTabMax steps (512 KiB; config 5's 44 640-step months fit): a longer run gets no table and divides.
+constexpr int64_t kAlphaTabMax = 65536;
+static void alpha_table_host(int64_t n_steps, double* out) {
+    for (int64_t s = 0; s < n_steps; ++s) out[s] = (double)s / (double)n_steps;
+}
+
+// The mesh's table for n_steps (mops_mesh::alpha_tabs), built and uploaded on the first launch that asks for it;
+// NULL past kAlphaTabMax.
+static mops_status alpha_table(const mops_mesh* mesh, int64_t n_steps, const double** out) {
+    *out = nullptr;
+    if (n_steps > kAlphaTabMax) return MOPS_OK;
+    std::lock_guard<std::mutex> lk(mesh->coop_mu);
+    for (const auto& t : mesh->alpha_tabs)
+        if (t.first == n_steps) { *out = t.second; return MOPS_OK; }
+    std::vector<double> h((size_t)n_steps);
+    alpha_table_host(n_steps, h.data());
+    double* d = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), (size_t)n_steps * sizeof(double)));
+    const hipError_t e = hipMemcpy(d, h.data(), (size_t)n_steps * sizeof(double), hipMemcpyHostToDevice);  // (blocking)
+    if (e != hipSuccess) { (void)hipFree(d); HIP_TRY(e); }
+    mesh->alpha_tabs.emplace_back(n_steps, d);
+    *out = d;
+    return MOPS_OK;
+}
+
 template <int MAXV>
 void launch_traj(const TrajArgs& a, bool path, bool euler, hipStream_t s) {
     const unsigned g = (unsigned)((a.n + kTrajBlock - 1) / kTrajBlock);
@@ -3274,14 +3456,14 @@ void launch_traj(const TrajArgs& a, bool path, bool euler, hipStream_t s) {
 }
 
 // The trajectory kernel's exact fast sqrt / sin / cos / a/|a| restate the device library's and the
-// compiler's own expansions (dev::sqrt_core, sincos_small, xdiv_norm3).  A toolchain whose
+// compiler's own expansions (dev::sqrt_core, sincos_small, xdiv_norm3, xdiv_ns / wach_fast).  A toolchain whose
 // expansions changed would break the bit parity silently, so every mesh creation first checks
 // them against the library on fixed arguments (the full sweep is mops_selftest_math's test).
 static mops_status check_fast_math(hipStream_t s) {
     constexpr int n = 512;  // arguments per op (op 2: n vectors of 3)
     std::vector<double> x(3 * n), out(6 * n);
-    double* d = nullptr;  // [3n inputs | 6n outputs]
-    HIP_TRY(hipMalloc(&d, 9 * n * sizeof(double)));
+    double* d = nullptr;  // ops 0-2: [3n inputs | 6n outputs]; ops 4, 5: [12n inputs | 13n outputs]
+    HIP_TRY(hipMalloc(&d, 25 * n * sizeof(double)));
     mops_status st = MOPS_OK;
     for (int op = 0; op < 3 && st == MOPS_OK; ++op) {
         const int nin = (op == 2) ? 3 * n : n, width = (op == 0) ? 2 : (op == 1 ? 4 : 2);  // outputs per input
@@ -3304,6 +3486,37 @@ static mops_status check_fast_math(hipStream_t s) {
             if (std::memcmp(&out[a], &out[b], sizeof(double)) != 0)
                 st = fail(MOPS_ERR_UNSUPPORTED, "the engine's exact fast-math helpers differ from the device library "
                                                 "on this toolchain (bit parity would be lost)");
+        }
+    }
+    // op 4: xdiv_ns against `/` on quotients across its window; op 5: the guarded Wachspress block against the
+    // plain one on hexagon-sized areas (the guard must pass there, or the check would compare `/` with itself)
+    std::vector<double> xi(12 * n), xo(13 * n);
+    for (int op = 4; op <= 5 && st == MOPS_OK; ++op) {
+        const int win = (op == 4) ? 2 : 12, wout = (op == 4) ? 3 : 13;
+        for (int i = 0; i < n; ++i) {
+            const double t = (i + 0.5) / n;
+            if (op == 4) {
+                xi[2 * i] = std::ldexp(1.0 + t, (int)(599.0 * std::sin(113.0 * t)) / 2) * ((i & 1) ? -1.0 : 1.0);
+                xi[2 * i + 1] = std::ldexp(1.0 + std::fabs(std::cos(57.0 * t)), (int)(599.0 * std::cos(71.0 * t)) / 2);
+            } else {
+                for (int j = 0; j < 6; ++j) {
+                    xi[12 * i + j] = 4.0e9 * (1.0 + 0.3 * std::sin(17.0 * t + j));          // 4 B_i, m^2
+                    xi[12 * i + 6 + j] = 1.0e6 + 3.0e9 * std::fabs(std::cos(29.0 * t + 1.7 * j));  // R_i, m^2
+                }
+            }
+        }
+        hipError_t e = hipMemcpyAsync(d, xi.data(), (size_t)win * n * sizeof(double), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) selftest_math_kernel<<<grid_for(n), kBlock, 0, s>>>(n, d, d + 12 * n, op);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(xo.data(), d + 12 * n, (size_t)wout * n * sizeof(double), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { st = fail(MOPS_ERR_HIP, std::string("fast-math check: ") + hipGetErrorString(e)); break; }
+        const int nq = (op == 4) ? 1 : 6;  // {nq fast, nq plain, took the fast path} per item
+        for (int i = 0; i < n && st == MOPS_OK; ++i) {
+            const double* o = &xo[(size_t)wout * i];
+            if (std::memcmp(o, o + nq, nq * sizeof(double)) != 0 || o[2 * nq] != 1.0)
+                st = fail(MOPS_ERR_UNSUPPORTED, "the engine's exact no-scale division differs from `/` on this toolchain "
+                                                "(bit parity would be lost)");
         }
     }
     (void)hipFree(d);
@@ -3356,12 +3569,17 @@ mops_status mops_selftest_walk(const mops_mesh* mesh, int64_t n, const double* d
 }
 
 mops_status mops_selftest_math(int64_t n, const double* d_x, double* d_out, int32_t op, void* stream) {
-    if (n < 0 || (n > 0 && (!d_x || !d_out)) || (op != 0 && op != 1 && op != 2))
+    if (n < 0 || (n > 0 && (!d_x || !d_out)) || op < 0 || op > 5)
         return fail(MOPS_ERR_INVALID, "mops_selftest_math: bad arguments");
     if (n == 0) return MOPS_OK;
     selftest_math_kernel<<<grid_for(n), kBlock, 0, (hipStream_t)stream>>>(n, d_x, d_out, op);
     HIP_TRY(hipGetLastError());
     return MOPS_OK;
+}
+
+int64_t mops_traj_alpha_table(int64_t n_steps, double* h_out) {
+    if (n_steps > 0 && n_steps <= kAlphaTabMax && h_out) alpha_table_host(n_steps, h_out);
+    return kAlphaTabMax;
 }
 
 mops_status mops_mesh_create(const mops_mesh_desc* desc, void* stream, mops_mesh** out) {
@@ -3702,7 +3920,7 @@ static mops_status compute_flags(const mops_mesh* mesh, mops_field* f, hipStream
     vertex_mono_kernel<<<grid_for(mesh->V * mesh->L), kBlock, 0, s>>>(mesh->V, mesh->L, f->d_zt, f->d_vmono,
                                                                       f->d_vzero);
     mono_kernel<<<grid_for(mesh->C), kBlock, 0, s>>>(mesh->C, mesh->maxv, mesh->rec_ints, mesh->d_cellrec, f->d_vmono,
-                                                    f->d_vzero, mesh->L, f->d_mono);
+                                                    f->d_vzero, mesh->L, mesh->d_cpoly, f->d_mono);
     HIP_TRY(hipGetLastError());
     return MOPS_OK;
 }
@@ -4122,7 +4340,8 @@ mops_status mops_traj_advance(const mops_mesh* mesh, const mops_field* front, co
     a.n_live = p->d_n_live;
     a.cpoly = mesh->d_cpoly;
     a.cnrm = mesh->d_cnrm;
-    a.unused0 = nullptr;
+    a.alpha_tab = nullptr;
+    if (back) MOPS_TRY(alpha_table(mesh, n_steps, &a.alpha_tab));
     a.nbr = mesh->d_nbr;
     a.cpolyr = mesh->d_cpolyr;
     a.crank = mesh->d_cell_rank;
