@@ -228,6 +228,47 @@ std::vector<TrajectoryLine> MOPS_RunPathLine(TrajectorySettings* config, std::ve
 // image 0 the ENU velocity, image 1 the first two double attributes when there are at least two
 std::vector<ImageBuffer<double>> MOPS_RunRemapping(VisualizationSettings* config);
 void MOPS_GenerateSamplePoints(SamplingSettings* config, std::vector<CartesianCoord>& sample_points);
+
+// SaveToPNG (src/Common/ImageBuffer.hpp:91-136) for the double image (the one instantiation the reference
+// uses): one channel (default 3, alpha) through the Viridis map -- NaN pixels transparent -- into an 8-bit
+// RGBA PNG.  The colouring runs on the GPU (mops_colormap_image), the file is written by
+// mops_write_png_rgba8 (stored deflate blocks: the decoded pixels are the reference's, the bytes are not
+// stb's).  false for a channel outside 0..3, an empty image or a failed write.
+bool SaveToPNG(const ImageBuffer<double>& buffer, const std::string& filename, int channel = 3);
+
+// TypeToStr (src/IO/VTKFileManager.hpp:12-20)
+inline std::string TypeToStr(VisualizeType type) {
+    switch (type) {
+        case VisualizeType::kFixedLayer: return "fixed_layer_";
+        case VisualizeType::kFixedDepth: return "fixed_depth_";
+    }
+    return "unknown_";
+}
+
+// VTKFileManager::SaveVTI (src/IO/VTKFileManager.hpp:25-138), both overloads, without VTK: the file is
+// outputName + "_" + TypeToStr(VisType) + std::to_string(k) + ".vti" with k = FixedDepth / FixedLayer
+// ("..._fixed_depth_10.000000.vti"), origin (LonRange.x, LatRange.x, k), spacing (range / (size - 1)) and
+// z spacing k (single image, one 3-component array "ImageScalars") or 1 (image list, three one-component
+// arrays per image named from attribute_names, then "attr_<i>").  Written by mops_write_image[s]_vti.
+class VTKFileManager {
+  public:
+    static void SaveVTI(ImageBuffer<double>* img, VisualizationSettings* config, std::string outputName = "output");
+    static void SaveVTI(const std::vector<ImageBuffer<double>>& img_list, VisualizationSettings* config,
+                        const std::vector<std::string>& attribute_names, const std::string& outputName = "output");
+};
+
+// MPASOVisualizer::VisualizeFixedLayer (src/Core/MPASOVisualizer.h:114, MPASOVisualizer.cpp:17-20 ->
+// Kernel::VisualizeFixedLayer, MPASOVisualizerKernels.cpp:141-236).  The reference's static takes the
+// MPASOField and a runtime context; this one reads the global app's mesh and active front solution, as
+// MOPS_RunRemapping does.  Writes {zonal, meridional, 0}
+// (alpha 1) at layer ClampLayer((int)config->FixedLayer, nVertLevels) into the pixels of *img that lie inside
+// imageSize (ImageBuffer::setPixel's bounds check).  MOPS_RunRemapping itself stays fixed-depth whatever
+// VisType says, as in the reference (MOPSApp.cpp:192).
+class MPASOVisualizer {
+  public:
+    static void VisualizeFixedLayer(VisualizationSettings* config, ImageBuffer<double>* img);
+};
+
 // Extension (the reference has no teardown): releases the mesh and fields held in HBM by the
 // global app.  Call it before the HIP runtime shuts down; nothing is freed from a static
 // destructor at exit.

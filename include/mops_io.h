@@ -6,6 +6,8 @@
  *   temperature, salinity [n][P] f64
  * The xyz -> geographic conversion runs on the GPU (mops_lines_geo); the
  * writers are host code streaming to a file, as the reference's are.
+ * Images are [height][width][4] f64 (mops_remap_*) or uint8 RGBA planes
+ * (mops_colormap_rgba8), on the host.
  */
 #ifndef MOPS_IO_H
 #define MOPS_IO_H
@@ -51,6 +53,35 @@ mops_status mops_write_lines_txt(const char* path, int64_t n, int64_t P, const d
 mops_status mops_write_pathline_binary(const char* path, int64_t n, int64_t P, const double* h_geo,
                                        const double* h_velocity, const double* h_temperature,
                                        const double* h_salinity, int include_velocity, int include_scalars);
+
+/* ---- images -------------------------------------------------------------- */
+
+/* The file MOPS::SaveToPNG ends with (src/Common/ImageBuffer.hpp:135,
+ * stbi_write_png of 4 components): an 8-bit RGBA PNG of h_rgba
+ * [height][width][4] (one plane of mops_colormap_rgba8).  Self-contained:
+ * signature, IHDR, one IDAT holding filter byte 0 + the row for every row in
+ * deflate *stored* blocks (own CRC-32 and Adler-32, no zlib), IEND.  The
+ * decoded pixels are the contract, not stb's bytes: a remapped plane is
+ * written in a fraction of the time a compressor takes. */
+mops_status mops_write_png_rgba8(const char* path, int32_t width, int32_t height, const uint8_t* h_rgba);
+
+/* VTKFileManager::SaveVTI, multi-attribute overload (src/IO/VTKFileManager.hpp:
+ * 80-138): one VTK XML ImageData file, WholeExtent "0 W-1 0 H-1 0 0", with
+ * 3 * n_images one-component Float64 point-data arrays from h_images
+ * [n_images][height][width][4]: array 3k + c is channel c of image k, VTK row
+ * i is image row height - 1 - i.  Array i is named names[i], or "attr_<i>"
+ * for i >= n_names (:106).  origin / spacing: 3 doubles each (:94-95).  Raw
+ * appended little-endian data as mops_write_lines_vtp's binary form (VTK's
+ * writer compresses its blocks: the arrays are the contract, not the bytes).
+ * `path` is used as given. */
+mops_status mops_write_images_vti(const char* path, int32_t n_images, int32_t width, int32_t height,
+                                  const double* h_images, const double* origin, const double* spacing,
+                                  const char* const* names, int32_t n_names);
+
+/* VTKFileManager::SaveVTI, single-image overload (:25-78): one 3-component
+ * Float64 array "ImageScalars" (the image's x, y, z), rows flipped as above. */
+mops_status mops_write_image_vti(const char* path, int32_t width, int32_t height, const double* h_image,
+                                 const double* origin, const double* spacing);
 
 #ifdef __cplusplus
 }

@@ -356,6 +356,8 @@ typedef struct {
     double fixed_latitude;               /* FixedLatitude (fixed latitude only) */
     double min_depth, max_depth;         /* fixed latitude rows: cellRefBottomDepth_vec.front() / .back() (:496-497) */
     int32_t layer_rule;                  /* MOPS_LAYER_REFERENCE / MOPS_LAYER_BRACKET (fixed depth only) */
+    double fixed_layer;                  /* FixedLayer (fixed layer only; read by mops_remap_fixed_layer alone, so a
+                                            caller of the other entries may pass the struct without it) */
 } mops_remap_cfg;
 
 /* Images MOPSApp::runRemapping returns for a solution with n_attr double
@@ -398,6 +400,46 @@ mops_status mops_remap_fixed_depth(const mops_mesh* mesh, const mops_field* fiel
  * [width] (optional) receives them.  Synchronises `stream`. */
 mops_status mops_remap_fixed_latitude(const mops_mesh* mesh, const mops_field* field, const mops_remap_cfg* cfg,
                                       double* d_image, int32_t* d_cells, void* stream);
+
+/* Kernel::VisualizeFixedLayer (MPASOVisualizerKernels.cpp:141-236), bit for
+ * bit: pixel positions and cells as mops_remap_fixed_depth (LatRange,
+ * LonRange); a pixel is {NaN, NaN, NaN, 1} where its cell is out of range, the
+ * cell's vertex count is outside 1..20 or TBBKernel::IsInMesh fails, else
+ * {zonal, meridional, 0, 1} of the Wachspress-weighted vertex velocity
+ * (TBBKernel::CalcVelocity) at layer ClampLayer((int)cfg->fixed_layer, L)
+ * (:14-26, :166): the double truncates toward zero, a negative value gives 0,
+ * L or more gives L - 1 (a NaN, undefined there, gives 0).  d_image
+ * [height][width][4]; d_cells [height*width] (optional) receives the cell of
+ * each pixel.  Synchronises `stream`. */
+mops_status mops_remap_fixed_layer(const mops_mesh* mesh, const mops_field* field, const mops_remap_cfg* cfg,
+                                   double* d_image, int32_t* d_cells, void* stream);
+
+/* ---- colour mapping ------------------------------------------------------ */
+
+/* MOPS::SaveToPNG's pixel work (src/Common/ImageBuffer.hpp:91-136) on the
+ * device, bit for bit, for the channels of an [height][width][4] float64
+ * device image (16-byte aligned) selected by channel_mask (bit c = channel c;
+ * 0 = x .. 3 = alpha, SaveToPNG's default).  Per channel: the float min / max
+ * of static_cast<float>(v) over the non-NaN pixels, starting from FLT_MAX /
+ * -FLT_MAX, then `if (min >= max) max = min + 1e-5f` (:101-111); per pixel a
+ * NaN gives {0, 0, 0, 0}, any other value norm = (f - min) / (max - min) in
+ * float, tinycolormap's Viridis lerp in double (tinycolormap.hpp:162-171) and
+ * {(unsigned char)(c * 255.0) for r, g, b; 255} (:115-132).  d_rgba receives
+ * one [height][width][4] uint8 plane per selected channel, in ascending
+ * channel order.  h_minmax (optional, host, [4][2] floats) receives every
+ * channel's {min, max} as used (the sign of a zero may differ from the
+ * reference's; no colour depends on it).  An infinite pixel makes the
+ * reference index its table from a NaN (undefined behaviour); here a NaN norm
+ * takes table entry 0.  The table is include/mops_viridis.h.  Synchronises
+ * `stream`. */
+mops_status mops_colormap_rgba8(const double* d_image, int32_t width, int32_t height, int32_t channel_mask,
+                                uint8_t* d_rgba, float* h_minmax, void* stream);
+
+/* mops_colormap_rgba8 with host buffers (the caller of MOPS::SaveToPNG holds
+ * an ImageBuffer on the host): uploads h_image, runs the kernels, downloads
+ * the planes into h_rgba. */
+mops_status mops_colormap_image(const double* h_image, int32_t width, int32_t height, int32_t channel_mask,
+                                uint8_t* h_rgba, float* h_minmax, void* stream);
 
 /* Identity of the engine build: a hash of the engine's sources, headers,
  * compiler flags and ROCm version, stamped at compile time (no reference

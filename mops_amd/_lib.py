@@ -24,8 +24,10 @@ EXPORTED = (
     "mops_traj_alpha_table",
     "mops_remove_nan_lines", "mops_remove_nan_ragged", "mops_run_trajectories", "mops_build_id",
     "mops_remap_num_images", "mops_remap_tables", "mops_remap_fixed_depth", "mops_remap_fixed_latitude",
+    "mops_remap_fixed_layer", "mops_colormap_rgba8", "mops_colormap_image",
     # include/mops_io.h
     "mops_lines_geo", "mops_write_lines_vtp", "mops_write_lines_txt", "mops_write_pathline_binary",
+    "mops_write_png_rgba8", "mops_write_images_vti", "mops_write_image_vti",
     # include/mops_netcdf.h
     "mops_nc_open", "mops_nc_close", "mops_nc_dim_len", "mops_nc_var_info", "mops_nc_read_f64", "mops_nc_read_i64",
     "mops_nc_read_bytes",
@@ -71,7 +73,7 @@ class RemapCfg(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("min_lat", C.c_double), ("max_lat", C.c_double),
                 ("min_lon", C.c_double), ("max_lon", C.c_double), ("fixed_depth", C.c_double),
                 ("fixed_latitude", C.c_double), ("min_depth", C.c_double), ("max_depth", C.c_double),
-                ("layer_rule", C.c_int32)]
+                ("layer_rule", C.c_int32), ("fixed_layer", C.c_double)]
 
 
 class MopsError(RuntimeError):
@@ -170,6 +172,13 @@ def load(path: str | None = None):
     lib.mops_remap_tables.argtypes = [P, I32, P, P, P, P]; lib.mops_remap_tables.restype = st
     lib.mops_remap_fixed_depth.argtypes = [P, P, P, I32, P, P, P, P, P, P]; lib.mops_remap_fixed_depth.restype = st
     lib.mops_remap_fixed_latitude.argtypes = [P, P, P, P, P, P]; lib.mops_remap_fixed_latitude.restype = st
+    lib.mops_remap_fixed_layer.argtypes = [P, P, P, P, P, P]; lib.mops_remap_fixed_layer.restype = st
+    lib.mops_colormap_rgba8.argtypes = [P, I32, I32, I32, P, P, P]; lib.mops_colormap_rgba8.restype = st
+    lib.mops_colormap_image.argtypes = [P, I32, I32, I32, P, P, P]; lib.mops_colormap_image.restype = st
+    lib.mops_write_png_rgba8.argtypes = [C.c_char_p, I32, I32, P]; lib.mops_write_png_rgba8.restype = st
+    lib.mops_write_images_vti.argtypes = [C.c_char_p, I32, I32, I32, P, P, P, P, I32]
+    lib.mops_write_images_vti.restype = st
+    lib.mops_write_image_vti.argtypes = [C.c_char_p, I32, I32, P, P, P]; lib.mops_write_image_vti.restype = st
     _lib = lib
     return lib
 

@@ -8,18 +8,18 @@ Mirrors the reference's command-line driver (CLI/main.cpp) option for option:
     -r/--range     timestep list ("-r 1,2" or repeated) "range,r"
     -g/--day       day gap (default 1)                  "day,g"
     -d/--depth     fixed depth in metres (default 10)   "depth,d"
+    --vti          extension: also write the VTI of the reference's MOPS_VTK build branch
 
 and its run (CLI/main.cpp:94-262): grid and one solution per timestep from the
 YAML (initGrid_DemoLoading / initSolution_DemoLoading, with temperature and
-salinity attributes), a 31x31 sample lattice in lat [35, 45), lon [-90, -15)
-at the fixed depth, and -- for a single timestep -- a StreamLine with
-deltaT = 1 h, simulationDuration = day_gap days, recordT = 6 h, written as
-``traj_line_<t>.txt`` (the reference's text dump) and ``traj_line_<t>.vtp``
-(its VTK build's SaveTrajectoryLinesAsVTP) in the working directory.
-
-The per-timestep remapping images (MOPS_RunRemapping, PNG/VTI) are out of scope
-of this build; the CLI says so and goes on, as the reference
-does when a stage produces nothing.
+salinity attributes); per timestep a 3601 x 1801 global fixed-depth remap
+written as ``output_<i>_ch<c>.png`` (:133-187; with ``--vti`` also
+``timestep_<t>_tile_0_fixed_depth_<depth>.vti``); a 31x31 sample lattice in
+lat [35, 45), lon [-90, -15) at the fixed depth, and -- for a single timestep
+-- a StreamLine with deltaT = 1 h, simulationDuration = day_gap days,
+recordT = 6 h, written as ``traj_line_<t>.txt`` (the reference's text dump)
+and ``traj_line_<t>.vtp`` (its VTK build's SaveTrajectoryLinesAsVTP) in the
+working directory.
 """
 from __future__ import annotations
 
@@ -48,6 +48,7 @@ def parse_command_line(argv):
     p.add_argument("-r", "--range", action="append", default=None, help="Timestep range")
     p.add_argument("-g", "--day", type=int, default=1, help="Day Gap")
     p.add_argument("-d", "--depth", type=float, default=10.0, help="Fixed depth")
+    p.add_argument("--vti", action="store_true", help="Also write the remapped images as VTK ImageData")
     p.add_argument("-h", "--help", action="store_true", help="Print this information")
     args = p.parse_args(argv)
     if args.help:
@@ -58,6 +59,40 @@ def parse_command_line(argv):
         return None
     args.range = _int_list(args.range)
     return args
+
+
+REMAP_WIDTH, REMAP_HEIGHT = 3601, 1801   # CLI/main.cpp:137
+VTI_NAMES = ("E: Zonal Velocity", "N: Meridional Velocity", "Velocity Magnitude",
+             "Temperature", "Salinity", "None")  # CLI/main.cpp:157-160 (image 1 holds salinity first: quirk Q16)
+
+
+def run_remapping_stage(M, mio, timestep, depth, vti=False, width=REMAP_WIDTH, height=REMAP_HEIGHT):
+    """CLI/main.cpp:133-187 for one active timestep: the global fixed-depth remap, then ``output_<i>_ch<c>.png``
+    for every image i and channel c < 3 (the same names at every timestep, as the reference), and with ``vti``
+    ``timestep_<t>_tile_0_fixed_depth_<depth>.vti``.  The images are coloured on the device; only their RGBA
+    bytes come to the host (the doubles too for a VTI, which stores them).  Returns the files written."""
+    from . import engine
+    cfg = M.VisualizationSettings()
+    cfg.imageSize = (float(width), float(height))
+    cfg.LatRange = (-90.0, 90.0)
+    cfg.LonRange = (-180.0, 180.0)
+    cfg.FixedDepth = depth
+    cfg.TimeStep = timestep
+    cfg.SaveType = M.SaveType.kVTI if vti else M.SaveType.kPNG
+    images = M._remap_device(cfg)
+    if images is None:
+        return []
+    written = []
+    for i in range(images.shape[0]):
+        planes = engine.colormap_rgba(images[i], channels=(0, 1, 2)).cpu().numpy()
+        for ch in range(3):
+            name = f"output_{i}_ch{ch}.png"
+            mio.write_png_rgba8(name, planes[ch])
+            written.append(name)
+    if vti:
+        written.append(M.SaveVTI(images.cpu().numpy(), cfg, VTI_NAMES, f"timestep_{timestep}_tile_{cfg.tile_index}"))
+    print(f"[MOPS_CLI] timestep {timestep}: remapping images written: " + " ".join(written))
+    return written
 
 
 def main(argv=None) -> int:
@@ -93,10 +128,10 @@ def main(argv=None) -> int:
         M.MOPS_AddAttribute(t, s)
     M.MOPS_End()
 
-    # 5-6. per-timestep remapping (out of scope); the last timestep stays active, as in the reference
+    # 5-6. per-timestep remapping (CLI/main.cpp:133-187); the last timestep stays active, as in the reference
     for t in timesteps:
         M.MOPS_ActiveAttribute(t)
-        print(f"[MOPS_CLI] timestep {t}: remapping images (MOPS_RunRemapping) are not part of this build; skipped")
+        run_remapping_stage(M, mio, t, args.depth, args.vti)
 
     # 7. sample points: 31 x 31 lattice request in [35, 45] x [-90, -15] (exclusive upper bounds)
     print("== generate sample points ==")

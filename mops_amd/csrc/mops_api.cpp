@@ -5,6 +5,7 @@
 // RunStreamLine / RunPathLine / RunRemapping.  Every computation goes to the HIP
 // engine; this file only marshals host containers.
 #include "mops/MOPS.h"
+#include "mops_io.h"
 
 #include <hip/hip_runtime.h>
 
@@ -416,6 +417,105 @@ std::vector<ImageBuffer<double>> MOPS_RunRemapping(VisualizationSettings* config
         hip(hipMemcpy(img_vec[(size_t)k].mPixels.data(), d_img + px * k, px * sizeof(double), hipMemcpyDeviceToHost),
             "hipMemcpy image");
     return img_vec;
+}
+
+void MPASOVisualizer::VisualizeFixedLayer(VisualizationSettings* config, ImageBuffer<double>* img) {
+    ScopedTimer t("GPUKernel::FixedLayer", "GPUKernel");
+    if (config == nullptr || img == nullptr || g_app.mesh == nullptr || g_app.front == nullptr) {  // :143-146
+        Error("[MI355X::VisualizeFixedLayer] invalid inputs");
+        return;
+    }
+    const int W = (int)config->imageSize.x, H = (int)config->imageSize.y;
+    if (W <= 0 || H <= 0) {  // :158-161
+        Error("[MI355X::VisualizeFixedLayer] invalid image size or layer metadata");
+        return;
+    }
+    mops_remap_cfg cfg{};
+    cfg.width = W; cfg.height = H;
+    cfg.min_lat = config->LatRange.x; cfg.max_lat = config->LatRange.y;
+    cfg.min_lon = config->LonRange.x; cfg.max_lon = config->LonRange.y;
+    cfg.fixed_layer = config->FixedLayer;
+    const size_t px = (size_t)W * H * 4;
+    struct DevBuf {
+        void* p = nullptr;
+        ~DevBuf() { (void)hipFree(p); }
+    } buf;
+    if (hipMalloc(&buf.p, px * sizeof(double)) != hipSuccess) throw std::runtime_error("VisualizeFixedLayer: hipMalloc");
+    check(mops_remap_fixed_layer(g_app.mesh, g_app.front, &cfg, static_cast<double*>(buf.p), nullptr, nullptr),
+          "mops_remap_fixed_layer");
+    std::vector<double> host(px);
+    if (hipMemcpy(host.data(), buf.p, px * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+        throw std::runtime_error("VisualizeFixedLayer: hipMemcpy");
+    for (int i = 0; i < H && i < img->getHeight(); ++i)  // img->setPixel: in-bounds pixels only
+        for (int j = 0; j < W && j < img->getWidth(); ++j)
+            std::memcpy(&img->mPixels[(size_t)img->getIndex(i, j)], &host[((size_t)i * W + j) * 4], 4 * sizeof(double));
+}
+
+bool SaveToPNG(const ImageBuffer<double>& buffer, const std::string& filename, int channel) {
+    const int w = buffer.getWidth(), h = buffer.getHeight();
+    if (channel < 0 || channel > 3 || w <= 0 || h <= 0 || buffer.mPixels.size() < (size_t)w * h * 4) return false;  // :98
+    std::vector<uint8_t> rgba((size_t)w * h * 4);
+    if (mops_colormap_image(buffer.mPixels.data(), w, h, 1 << channel, rgba.data(), nullptr, nullptr) != MOPS_OK) {
+        Error("SaveToPNG: %s", mops_last_error());
+        return false;
+    }
+    return mops_write_png_rgba8(filename.c_str(), w, h, rgba.data()) == MOPS_OK;
+}
+
+namespace {
+// the file name and geometry both SaveVTI overloads share (VTKFileManager.hpp:27-36, :86-90)
+struct VtiGeometry {
+    int W, H;
+    double origin[3], spacing[3];
+    std::string file;
+};
+VtiGeometry vti_geometry(const VisualizationSettings& c, const std::string& outputName, bool single) {
+    VtiGeometry g;
+    g.W = (int)c.imageSize.x; g.H = (int)c.imageSize.y;
+    const double latSpacing = (c.LatRange.y - c.LatRange.x) / (c.imageSize.y - 1);
+    const double lonSpacing = (c.LonRange.y - c.LonRange.x) / (c.imageSize.x - 1);
+    const double k = (c.VisType == VisualizeType::kFixedDepth) ? c.FixedDepth : c.FixedLayer;
+    g.origin[0] = c.LonRange.x; g.origin[1] = c.LatRange.x; g.origin[2] = k;
+    g.spacing[0] = lonSpacing; g.spacing[1] = latSpacing; g.spacing[2] = single ? k : 1.0;  // :47 / :95
+    g.file = outputName + "_" + TypeToStr(c.VisType) + std::to_string(k) + ".vti";
+    return g;
+}
+}  // namespace
+
+void VTKFileManager::SaveVTI(ImageBuffer<double>* img, VisualizationSettings* config, std::string outputName) {
+    if (!config) return;
+    if (!img) {  // :50-53
+        Error("SaveVTI:: ImageBuffer is nullptr.....");
+        return;
+    }
+    const VtiGeometry g = vti_geometry(*config, outputName, true);
+    if (g.W != img->getWidth() || g.H != img->getHeight()) {  // :59-63 skips every pixel outside the image
+        Error("SaveVTI:: imageSize %d x %d differs from the image's %d x %d", g.W, g.H, img->getWidth(), img->getHeight());
+        return;
+    }
+    if (mops_write_image_vti(g.file.c_str(), g.W, g.H, img->mPixels.data(), g.origin, g.spacing) != MOPS_OK)
+        Error("SaveVTI: %s", mops_last_error());
+}
+
+void VTKFileManager::SaveVTI(const std::vector<ImageBuffer<double>>& img_list, VisualizationSettings* config,
+                             const std::vector<std::string>& attribute_names, const std::string& outputName) {
+    if (!config || img_list.empty()) return;
+    const VtiGeometry g = vti_geometry(*config, outputName, false);
+    const size_t px = (size_t)(g.W > 0 ? g.W : 0) * (size_t)(g.H > 0 ? g.H : 0) * 4;
+    std::vector<double> all;
+    all.reserve(px * img_list.size());
+    for (const auto& img : img_list) {
+        if (img.getWidth() != g.W || img.getHeight() != g.H || img.mPixels.size() != px) {
+            Error("SaveVTI:: imageSize %d x %d differs from an image's %d x %d", g.W, g.H, img.getWidth(), img.getHeight());
+            return;
+        }
+        all.insert(all.end(), img.mPixels.begin(), img.mPixels.end());
+    }
+    std::vector<const char*> names;
+    for (const auto& s : attribute_names) names.push_back(s.c_str());
+    if (mops_write_images_vti(g.file.c_str(), (int32_t)img_list.size(), g.W, g.H, all.data(), g.origin, g.spacing,
+                              names.empty() ? nullptr : names.data(), (int32_t)names.size()) != MOPS_OK)
+        Error("SaveVTI: %s", mops_last_error());
 }
 
 void MOPS_GenerateSamplePoints(SamplingSettings* config, std::vector<CartesianCoord>& points) {

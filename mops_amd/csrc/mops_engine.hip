@@ -27,6 +27,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -4893,6 +4894,29 @@ __global__ void __launch_bounds__(256) remap_fixed_latitude_kernel(RemapArgs a) 
     remap_set_pixel(a.img0, g, zonal, meridional, 0.0);
 }
 
+// Kernel::VisualizeFixedLayer (MPASOVisualizerKernels.cpp:141-236): the fixed-depth kernel without the column
+// search -- the velocity at one layer (ClampLayer(FixedLayer, L), from the host) for every pixel inside its cell
+template <int MAXV>
+__global__ void __launch_bounds__(256) remap_fixed_layer_kernel(RemapArgs a, int layer) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= a.n) return;
+    const double nan = __builtin_nan("");
+    const int cell = a.cells[g];
+    const double px = a.pts[3 * g], py = a.pts[3 * g + 1], pz = a.pts[3 * g + 2];
+    RemapStencil<MAXV> s;
+    bool ok = cell >= 0 && cell < a.C;                               // :191
+    if (ok) ok = remap_stencil<MAXV, false>(a, cell, px, py, pz, s);  // :196-220
+    if (!ok) {
+        remap_set_pixel(a.img0, g, nan, nan, nan);
+        return;
+    }
+    double vx, vy, vz;
+    remap_velocity<MAXV>(a, s, layer, vx, vy, vz);  // :222-228
+    double zonal, meridional;
+    remap_enu(px, py, pz, vx, vy, vz, zonal, meridional);
+    remap_set_pixel(a.img0, g, zonal, meridional, 0.0);
+}
+
 // GeoConverter::convertPixelToLatLonToRadians (GeoConverter.hpp:28-32) per row / per column, then the
 // libm cos / sin of convertRadianLatLonToXYZ (:120-121)
 void remap_depth_tables(const mops_remap_cfg* c, double* row_cos, double* row_sin, double* col_cos, double* col_sin) {
@@ -4958,6 +4982,13 @@ void launch_remap_latitude(int maxv, const RemapArgs& a, hipStream_t s) {
     if (maxv <= 7) remap_fixed_latitude_kernel<7><<<grid, 256, 0, s>>>(a);
     else if (maxv <= 12) remap_fixed_latitude_kernel<12><<<grid, 256, 0, s>>>(a);
     else remap_fixed_latitude_kernel<20><<<grid, 256, 0, s>>>(a);
+}
+
+void launch_remap_layer(int maxv, const RemapArgs& a, int layer, hipStream_t s) {
+    const unsigned grid = grid_for(a.n);
+    if (maxv <= 7) remap_fixed_layer_kernel<7><<<grid, 256, 0, s>>>(a, layer);
+    else if (maxv <= 12) remap_fixed_layer_kernel<12><<<grid, 256, 0, s>>>(a, layer);
+    else remap_fixed_layer_kernel<20><<<grid, 256, 0, s>>>(a, layer);
 }
 
 // positions -> locate -> `eval` on one scratch allocation: tables [2 rows + 2 W] | points [np][3] | cells [np]
@@ -5063,6 +5094,238 @@ mops_status mops_remap_fixed_latitude(const mops_mesh* mesh, const mops_field* f
         a.pts = pts; a.cells = cells;
         launch_remap_latitude(maxv, a, s);
     });
+}
+
+mops_status mops_remap_fixed_layer(const mops_mesh* mesh, const mops_field* field, const mops_remap_cfg* cfg,
+                                   double* d_image, int32_t* d_cells, void* stream) {
+    MOPS_TRY(remap_check("mops_remap_fixed_layer", mesh, field, cfg, d_image));
+    if (mesh->L <= 0) return fail(MOPS_ERR_INVALID, "mops_remap_fixed_layer: invalid layer metadata");  // :158
+    hipStream_t s = (hipStream_t)stream;
+    const int W = cfg->width, H = cfg->height;
+    std::vector<double> tables(2 * (size_t)H + 2 * (size_t)W);
+    remap_depth_tables(cfg, tables.data(), tables.data() + H, tables.data() + 2 * H, tables.data() + 2 * H + W);
+    RemapArgs a = remap_args(mesh, field, cfg);
+    a.n = (int64_t)W * H;
+    // ClampLayer((int)FixedLayer, L) (:14-26, :166): the double truncates toward zero; a NaN (undefined in the
+    // reference) gives layer 0
+    const double fl = cfg->fixed_layer;
+    const int layer = !(fl >= 1.0) ? 0 : (fl >= (double)mesh->L ? mesh->L - 1 : (int)fl);
+    a.img0 = d_image;
+    const int maxv = mesh->maxv;
+    return remap_run(mesh, H, W, tables, d_cells, nullptr, s, [&](const double* pts, const int32_t* cells) {
+        a.pts = pts; a.cells = cells;
+        launch_remap_layer(maxv, a, layer, s);
+    });
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// colour mapping: MOPS::SaveToPNG's pixel work (src/Common/ImageBuffer.hpp:91-136) for an [H][W][4]
+// float64 device image, channels together.  Two passes over the image: the float range of every channel
+// (per-block partials, then one block reduces them -- min / max do not depend on the order, so no atomics and
+// no hand-off between workgroups are needed), then tinycolormap's Viridis lerp (tinycolormap.hpp:162-171) per
+// pixel and selected channel, one uchar4 store per plane.  The table (include/mops_viridis.h, generated from
+// matplotlib's published Viridis samples) is staged in LDS: the per-lane index is data dependent.
+//
+// Infinities: an infinite pixel makes max - min infinite or NaN, and the reference then indexes its table
+// with static_cast<size_t>(NaN), which is undefined.  Here a NaN `norm` takes table entry 0.
+// ===========================================================================
+#include "mops_viridis.h"
+
+namespace {
+
+constexpr int kCmapMaxBlocks = 1024;  // range-pass grid cap: 4 blocks of 256 lanes per CU on 256 CUs
+
+__device__ __forceinline__ void cmap_acc(float& mn, float& mx, double v) {
+    const float f = static_cast<float>(v);  // :105
+    if (!(f != f)) {                        // :106
+        mn = f < mn ? f : mn;               // std::min / std::max (:107-108)
+        mx = mx < f ? f : mx;
+    }
+}
+
+// per block and channel {min, max} of the non-NaN float values -> partial [gridDim.x][4][2].  The values are
+// order independent; only the sign of a zero minimum or maximum may differ from the reference's, and it
+// reaches no colour: x - (+0) and x - (-0) differ for no x but -0, whose norm is a zero of either sign.
+__global__ void __launch_bounds__(256) colormap_range_kernel(int64_t n, const double2* __restrict__ img,
+                                                             float* __restrict__ partial) {
+    __shared__ float red[4][8];  // [wave][channel * 2 + {min, max}]
+    float mn[4], mx[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { mn[c] = FLT_MAX; mx[c] = -FLT_MAX; }  // :101-102
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += (int64_t)gridDim.x * blockDim.x) {
+        const double2 xy = img[2 * g], za = img[2 * g + 1];  // the 32-B pixel as two 16-B loads
+        cmap_acc(mn[0], mx[0], xy.x);
+        cmap_acc(mn[1], mx[1], xy.y);
+        cmap_acc(mn[2], mx[2], za.x);
+        cmap_acc(mn[3], mx[3], za.y);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            mn[c] = fminf(mn[c], __shfl_xor(mn[c], off, 64));
+            mx[c] = fmaxf(mx[c], __shfl_xor(mx[c], off, 64));
+        }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { red[wave][2 * c] = mn[c]; red[wave][2 * c + 1] = mx[c]; }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        const bool is_max = threadIdx.x & 1;
+        float r = red[0][threadIdx.x];
+        for (int w = 1; w < 4; ++w) r = is_max ? fmaxf(r, red[w][threadIdx.x]) : fminf(r, red[w][threadIdx.x]);
+        partial[(int64_t)blockIdx.x * 8 + threadIdx.x] = r;
+    }
+}
+
+// one block: partial [n_blocks][4][2] -> minmax [4][2], with `if (min >= max) max = min + 1e-5f` (:111)
+__global__ void __launch_bounds__(256) colormap_reduce_kernel(int n_blocks, const float* __restrict__ partial,
+                                                              float* __restrict__ minmax) {
+    __shared__ float red[256];
+    const int k = threadIdx.x & 7;  // channel * 2 + {min, max}
+    const bool is_max = k & 1;
+    float r = is_max ? -FLT_MAX : FLT_MAX;
+    for (int b = threadIdx.x >> 3; b < n_blocks; b += 32) {
+        const float v = partial[(int64_t)b * 8 + k];
+        r = is_max ? fmaxf(r, v) : fminf(r, v);
+    }
+    red[threadIdx.x] = r;
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        for (int j = 1; j < 32; ++j) {
+            const float v = red[j * 8 + k];
+            r = is_max ? fmaxf(r, v) : fminf(r, v);
+        }
+        red[threadIdx.x] = r;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const float minVal = red[2 * threadIdx.x];
+        float maxVal = red[2 * threadIdx.x + 1];
+        if (minVal >= maxVal) maxVal = minVal + 1e-5f;
+        minmax[2 * threadIdx.x] = minVal;
+        minmax[2 * threadIdx.x + 1] = maxVal;
+    }
+}
+
+// :115-132 for one value: norm in float, tinycolormap::GetViridisColor in double, truncation to bytes
+__device__ __forceinline__ uchar4 cmap_pixel(double v, float minVal, float maxVal, const double (*T)[3]) {
+    const float raw_val = static_cast<float>(v);
+    if (raw_val != raw_val) return make_uchar4(0, 0, 0, 0);
+    const float norm_val = (raw_val - minVal) / (maxVal - minVal);
+    const double x = norm_val;
+    double cl = (x < 0.0) ? 0.0 : (x > 1.0) ? 1.0 : x;  // Clamp01
+    if (cl != cl) cl = 0.0;                              // NaN norm: entry 0 (see the section comment)
+    const double a = cl * (MOPS_VIRIDIS_N - 1);
+    const double i = floor(a);
+    const double t = a - i;
+    const int i0 = (int)i, i1 = (int)ceil(a);
+    const double u = 1.0 - t;
+    const double r = u * T[i0][0] + t * T[i1][0];
+    const double g = u * T[i0][1] + t * T[i1][1];
+    const double b = u * T[i0][2] + t * T[i1][2];
+    return make_uchar4((unsigned char)(r * 255.0), (unsigned char)(g * 255.0), (unsigned char)(b * 255.0), 255);
+}
+
+__global__ void __launch_bounds__(256) colormap_map_kernel(int64_t n, const double2* __restrict__ img,
+                                                           const double* __restrict__ table,
+                                                           const float* __restrict__ minmax, int mask,
+                                                           uchar4* __restrict__ out) {
+    __shared__ double T[MOPS_VIRIDIS_N][3];
+    for (int k = threadIdx.x; k < MOPS_VIRIDIS_N * 3; k += blockDim.x) (&T[0][0])[k] = table[k];
+    __syncthreads();
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    const double2 xy = img[2 * g], za = img[2 * g + 1];
+    const double v[4] = {xy.x, xy.y, za.x, za.y};
+    int plane = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+        if (mask & (1 << c)) {
+            out[(int64_t)plane * n + g] = cmap_pixel(v[c], minmax[2 * c], minmax[2 * c + 1], T);
+            ++plane;
+        }
+}
+
+std::mutex g_cmap_mutex;
+double* g_cmap_table[64] = {};  // the table in HBM, per device, uploaded on first use (6 KB, kept)
+
+mops_status cmap_table(const double** out) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64) return fail(MOPS_ERR_UNSUPPORTED, "mops_colormap_rgba8: device index above 63");
+    std::lock_guard<std::mutex> lock(g_cmap_mutex);
+    if (!g_cmap_table[dev]) {
+        double* p = nullptr;
+        HIP_TRY(hipMalloc(&p, sizeof(MOPS_VIRIDIS_TABLE)));
+        hipError_t e = hipMemcpy(p, MOPS_VIRIDIS_TABLE, sizeof(MOPS_VIRIDIS_TABLE), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(p);
+            return fail(MOPS_ERR_HIP, std::string("mops_colormap_rgba8: ") + hipGetErrorString(e));
+        }
+        g_cmap_table[dev] = p;
+    }
+    *out = g_cmap_table[dev];
+    return MOPS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+mops_status mops_colormap_rgba8(const double* d_image, int32_t width, int32_t height, int32_t channel_mask,
+                                uint8_t* d_rgba, float* h_minmax, void* stream) {
+    if (!d_image || !d_rgba || width <= 0 || height <= 0 || (int64_t)width * height > 0x7fffffffLL ||
+        channel_mask <= 0 || channel_mask > 15)
+        return fail(MOPS_ERR_INVALID, "mops_colormap_rgba8: invalid argument");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = (int64_t)width * height;
+    // at least four grid-stride rounds per lane where the image allows it, so few partials are left to reduce
+    const int n_blocks = (int)std::min<int64_t>((n + 4 * 256 - 1) / (4 * 256), kCmapMaxBlocks);
+    const double* table = nullptr;
+    MOPS_TRY(cmap_table(&table));
+    float* scratch = nullptr;  // partial [n_blocks][4][2] | minmax [4][2]
+    MOPS_TRY(dmalloc(&scratch, (size_t)n_blocks * 8 + 8, nullptr));
+    float* minmax = scratch + (size_t)n_blocks * 8;
+    colormap_range_kernel<<<n_blocks, 256, 0, s>>>(n, (const double2*)d_image, scratch);
+    colormap_reduce_kernel<<<1, 256, 0, s>>>(n_blocks, scratch, minmax);
+    colormap_map_kernel<<<grid_for(n), 256, 0, s>>>(n, (const double2*)d_image, table, minmax, channel_mask,
+                                                    (uchar4*)d_rgba);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && h_minmax) e = hipMemcpyAsync(h_minmax, minmax, 8 * sizeof(float), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(scratch);
+    if (e != hipSuccess) return fail(MOPS_ERR_HIP, std::string("mops_colormap_rgba8: ") + hipGetErrorString(e));
+    return MOPS_OK;
+}
+
+mops_status mops_colormap_image(const double* h_image, int32_t width, int32_t height, int32_t channel_mask,
+                                uint8_t* h_rgba, float* h_minmax, void* stream) {
+    if (!h_image || !h_rgba || width <= 0 || height <= 0 || (int64_t)width * height > 0x7fffffffLL ||
+        channel_mask <= 0 || channel_mask > 15)
+        return fail(MOPS_ERR_INVALID, "mops_colormap_image: invalid argument");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)width * height;
+    const size_t planes = (size_t)__builtin_popcount((unsigned)channel_mask);
+    double* d_image = nullptr;
+    uint8_t* d_rgba = nullptr;
+    mops_status st = MOPS_OK;
+    do {
+        if ((st = dmalloc(&d_image, n * 4, nullptr)) != MOPS_OK) break;
+        if ((st = dmalloc(&d_rgba, planes * n * 4, nullptr)) != MOPS_OK) break;
+        hipError_t e = hipMemcpyAsync(d_image, h_image, n * 4 * sizeof(double), hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) { st = fail(MOPS_ERR_HIP, std::string("mops_colormap_image: ") + hipGetErrorString(e)); break; }
+        if ((st = mops_colormap_rgba8(d_image, width, height, channel_mask, d_rgba, h_minmax, stream)) != MOPS_OK) break;
+        e = hipMemcpyAsync(h_rgba, d_rgba, planes * n * 4, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) st = fail(MOPS_ERR_HIP, std::string("mops_colormap_image: ") + hipGetErrorString(e));
+    } while (0);
+    (void)hipFree(d_image);
+    (void)hipFree(d_rgba);
+    return st;
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
-// mops_io.cpp -- host writers for the trajectory output formats (include/mops_io.h).
-// They stream already-converted lines (mops_lines_geo runs on the GPU) to disk.
+// mops_io.cpp -- host writers for the trajectory and image output formats (include/mops_io.h).
+// They stream already-converted lines (mops_lines_geo runs on the GPU) and already-coloured or raw
+// images (mops_colormap_rgba8 runs on the GPU) to disk.
 #include "mops_io.h"
 
 #include <cmath>
@@ -209,6 +210,180 @@ mops_status mops_write_pathline_binary(const char* path, int64_t n, int64_t P, c
           << offsets[i].second << "\n    }";
     m << (offsets.empty() ? "]" : "\n  ]") << "\n}";
     return m ? MOPS_OK : mops_io_fail(MOPS_ERR_INVALID, "mops_write_pathline_binary: meta write failed");
+}
+
+}  // extern "C"
+
+// ---- images: PNG (deflate stored blocks) and VTK XML ImageData ------------------------------------------
+namespace {
+
+const uint32_t* crc_table() {
+    static uint32_t table[256];
+    static bool ready = [] {
+        for (uint32_t n = 0; n < 256; ++n) {
+            uint32_t c = n;
+            for (int k = 0; k < 8; ++k) c = (c & 1u) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
+            table[n] = c;
+        }
+        return true;
+    }();
+    (void)ready;
+    return table;
+}
+
+uint32_t crc32_update(uint32_t crc, const uint8_t* p, size_t n) {  // PNG specification, annex D
+    const uint32_t* t = crc_table();
+    for (size_t i = 0; i < n; ++i) crc = t[(crc ^ p[i]) & 0xFFu] ^ (crc >> 8);
+    return crc;
+}
+
+uint32_t adler32(const uint8_t* p, size_t n) {  // RFC 1950 section 8.2; 5552 bytes keep the sums below 2^32
+    uint32_t a = 1, b = 0;
+    while (n > 0) {
+        const size_t k = n < 5552 ? n : 5552;
+        for (size_t i = 0; i < k; ++i) { a += p[i]; b += a; }
+        a %= 65521u; b %= 65521u;
+        p += k; n -= k;
+    }
+    return (b << 16) | a;
+}
+
+void be32(uint8_t* p, uint32_t v) {
+    p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v;
+}
+
+bool png_chunk(std::ofstream& f, const char type[4], const uint8_t* data, size_t n) {
+    uint8_t head[8], tail[4];
+    be32(head, (uint32_t)n);
+    std::memcpy(head + 4, type, 4);
+    uint32_t crc = crc32_update(0xFFFFFFFFu, head + 4, 4);
+    crc = crc32_update(crc, data, n) ^ 0xFFFFFFFFu;
+    be32(tail, crc);
+    f.write(reinterpret_cast<const char*>(head), 8);
+    if (n) f.write(reinterpret_cast<const char*>(data), (std::streamsize)n);
+    f.write(reinterpret_cast<const char*>(tail), 4);
+    return (bool)f;
+}
+
+std::string xml_escape(const std::string& s) {
+    std::string o;
+    for (char c : s) {
+        switch (c) {
+            case '&': o += "&amp;"; break;
+            case '<': o += "&lt;"; break;
+            case '>': o += "&gt;"; break;
+            case '"': o += "&quot;"; break;
+            default: o += c;
+        }
+    }
+    return o;
+}
+
+// One VTK XML ImageData file of a w x h x 1 point grid.  split: 3 one-component arrays per image (array
+// 3k + c = channel c of image k); otherwise one 3-component array "ImageScalars" of image 0.  VTK row i is
+// image row h - 1 - i (VTKFileManager.hpp:64, :117).  Appended raw data with UInt64 block headers, the
+// encoding of mops_write_lines_vtp's binary form.
+mops_status write_vti(const char* what, const char* path, int32_t n_images, int32_t w, int32_t h,
+                      const double* h_images, const double* origin, const double* spacing, const char* const* names,
+                      int32_t n_names, bool split) {
+    if (!path || n_images <= 0 || w <= 0 || h <= 0 || !h_images || !origin || !spacing || n_names < 0 ||
+        (n_names > 0 && !names))
+        return mops_io_fail(MOPS_ERR_INVALID, (std::string(what) + ": invalid argument").c_str());
+    std::ofstream f(path, std::ios::binary);
+    if (!f) return mops_io_fail(MOPS_ERR_INVALID, (std::string(what) + ": cannot open " + path).c_str());
+    const size_t np = (size_t)w * h;
+    const int n_arrays = split ? 3 * n_images : 1;
+    const uint64_t bytes = (uint64_t)np * 8u * (split ? 1u : 3u);
+    f.precision(17);
+    f << "<?xml version=\"1.0\"?>\n"
+      << "<VTKFile type=\"ImageData\" version=\"1.0\" byte_order=\"LittleEndian\" header_type=\"UInt64\">\n"
+      << "  <ImageData WholeExtent=\"0 " << w - 1 << " 0 " << h - 1 << " 0 0\" Origin=\"" << origin[0] << " " << origin[1]
+      << " " << origin[2] << "\" Spacing=\"" << spacing[0] << " " << spacing[1] << " " << spacing[2] << "\">\n"
+      << "    <Piece Extent=\"0 " << w - 1 << " 0 " << h - 1 << " 0 0\">\n"
+      << (split ? "      <PointData>\n" : "      <PointData Scalars=\"ImageScalars\">\n");
+    for (int i = 0; i < n_arrays; ++i) {
+        std::string name = "ImageScalars";
+        if (split) name = (i < n_names && names[i]) ? std::string(names[i]) : "attr_" + std::to_string(i);  // :106
+        f << "        <DataArray type=\"Float64\" Name=\"" << xml_escape(name) << "\"";
+        if (!split) f << " NumberOfComponents=\"3\"";
+        f << " format=\"appended\" offset=\"" << (uint64_t)i * (8u + bytes) << "\"/>\n";
+    }
+    f << "      </PointData>\n      <CellData>\n      </CellData>\n    </Piece>\n  </ImageData>\n"
+      << "  <AppendedData encoding=\"raw\">\n   _";
+    std::vector<double> row((size_t)w * (split ? 1 : 3));
+    for (int i = 0; i < n_arrays; ++i) {
+        put<uint64_t>(f, bytes);
+        const double* img = h_images + (size_t)(split ? i / 3 : 0) * np * 4;
+        const int c = split ? i % 3 : 0;
+        for (int r = 0; r < h; ++r) {
+            const double* src = img + (size_t)(h - 1 - r) * w * 4;
+            if (split)
+                for (int j = 0; j < w; ++j) row[(size_t)j] = src[4 * (size_t)j + c];
+            else
+                for (int j = 0; j < w; ++j)
+                    for (int k = 0; k < 3; ++k) row[3 * (size_t)j + k] = src[4 * (size_t)j + k];
+            f.write(reinterpret_cast<const char*>(row.data()), (std::streamsize)(row.size() * sizeof(double)));
+        }
+    }
+    f << "\n  </AppendedData>\n</VTKFile>\n";
+    if (!f) return mops_io_fail(MOPS_ERR_INVALID, (std::string(what) + ": write failed: " + path).c_str());
+    return MOPS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+mops_status mops_write_png_rgba8(const char* path, int32_t width, int32_t height, const uint8_t* h_rgba) {
+    if (!path || width <= 0 || height <= 0 || !h_rgba)
+        return mops_io_fail(MOPS_ERR_INVALID, "mops_write_png_rgba8: invalid argument");
+    const size_t stride = (size_t)width * 4, raw = (size_t)height * (1 + stride);
+    const size_t n_blocks = (raw + 65534) / 65535;
+    const size_t idat_bytes = 2 + n_blocks * 5 + raw + 4;
+    if (idat_bytes > 0x7fffffffu) return mops_io_fail(MOPS_ERR_INVALID, "mops_write_png_rgba8: image too large");
+    // the filtered scanlines: filter type 0 (None) before every row
+    std::vector<uint8_t> lines(raw);
+    for (int32_t r = 0; r < height; ++r) {
+        lines[(size_t)r * (1 + stride)] = 0;
+        std::memcpy(&lines[(size_t)r * (1 + stride) + 1], h_rgba + (size_t)r * stride, stride);
+    }
+    // the zlib stream (RFC 1950 / 1951): header, stored blocks of at most 65535 bytes, Adler-32
+    std::vector<uint8_t> idat(idat_bytes);
+    size_t o = 0;
+    idat[o++] = 0x78; idat[o++] = 0x01;
+    for (size_t b = 0, pos = 0; b < n_blocks; ++b) {
+        const size_t len = raw - pos < 65535 ? raw - pos : 65535;
+        idat[o++] = (b + 1 == n_blocks) ? 1 : 0;  // BFINAL, BTYPE 00
+        idat[o++] = (uint8_t)(len & 0xFF); idat[o++] = (uint8_t)(len >> 8);
+        idat[o++] = (uint8_t)(~len & 0xFF); idat[o++] = (uint8_t)((~len >> 8) & 0xFF);
+        std::memcpy(&idat[o], &lines[pos], len);
+        o += len; pos += len;
+    }
+    be32(&idat[o], adler32(lines.data(), raw));
+    std::ofstream f(path, std::ios::binary);
+    if (!f) return mops_io_fail(MOPS_ERR_INVALID, (std::string("mops_write_png_rgba8: cannot open ") + path).c_str());
+    static const uint8_t signature[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+    f.write(reinterpret_cast<const char*>(signature), 8);
+    uint8_t ihdr[13];
+    be32(ihdr, (uint32_t)width);
+    be32(ihdr + 4, (uint32_t)height);
+    ihdr[8] = 8; ihdr[9] = 6; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;  // 8 bits, RGBA, deflate, adaptive, no interlace
+    if (!png_chunk(f, "IHDR", ihdr, 13) || !png_chunk(f, "IDAT", idat.data(), idat.size()) ||
+        !png_chunk(f, "IEND", nullptr, 0))
+        return mops_io_fail(MOPS_ERR_INVALID, (std::string("mops_write_png_rgba8: write failed: ") + path).c_str());
+    return MOPS_OK;
+}
+
+mops_status mops_write_images_vti(const char* path, int32_t n_images, int32_t width, int32_t height,
+                                  const double* h_images, const double* origin, const double* spacing,
+                                  const char* const* names, int32_t n_names) {
+    return write_vti("mops_write_images_vti", path, n_images, width, height, h_images, origin, spacing, names, n_names,
+                     true);
+}
+
+mops_status mops_write_image_vti(const char* path, int32_t width, int32_t height, const double* h_image,
+                                 const double* origin, const double* spacing) {
+    return write_vti("mops_write_image_vti", path, 1, width, height, h_image, origin, spacing, nullptr, 0, false);
 }
 
 }  // extern "C"

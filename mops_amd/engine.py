@@ -639,7 +639,7 @@ LAYER_RULES = {"reference": L.MOPS_LAYER_REFERENCE, "bracket": L.MOPS_LAYER_BRAC
 
 
 def _remap_cfg(width, height, lat_range=(0.0, 0.0), lon_range=(0.0, 0.0), depth=0.0, latitude=0.0,
-               depth_range=(0.0, 0.0), layer_rule="reference") -> L.RemapCfg:
+               depth_range=(0.0, 0.0), layer_rule="reference", layer=0.0) -> L.RemapCfg:
     if layer_rule not in LAYER_RULES:
         raise ValueError(f"layer_rule must be one of {sorted(LAYER_RULES)}, not {layer_rule!r}")
     width, height = int(width), int(height)
@@ -647,7 +647,7 @@ def _remap_cfg(width, height, lat_range=(0.0, 0.0), lon_range=(0.0, 0.0), depth=
         raise ValueError(f"invalid image size {width} x {height}")
     return L.RemapCfg(width, height, float(lat_range[0]), float(lat_range[1]), float(lon_range[0]),
                       float(lon_range[1]), float(depth), float(latitude), float(depth_range[0]),
-                      float(depth_range[1]), LAYER_RULES[layer_rule])
+                      float(depth_range[1]), LAYER_RULES[layer_rule], float(layer))
 
 
 def remap_tables(width, height, lat_range=(0.0, 0.0), lon_range=(0.0, 0.0), latitude=None):
@@ -735,3 +735,45 @@ def remap_fixed_latitude(mesh: DeviceMesh, field: DeviceField, width: int, heigh
                                                None if cells is None else C.c_void_p(cells.data_ptr()),
                                                _stream_handle(h)), "mops_remap_fixed_latitude")
     return (image, cells) if return_cells else image
+
+
+def remap_fixed_layer(mesh: DeviceMesh, field: DeviceField, width: int, height: int, lat_range, lon_range,
+                      layer: float, return_cells: bool = False, stream=None):
+    """Kernel::VisualizeFixedLayer (mops_remap_fixed_layer): one float64 CUDA tensor [height, width, 4] =
+    {zonal, meridional, 0, 1} at layer ClampLayer(int(layer), nVertLevels) -- ``layer`` is the settings'
+    double FixedLayer, truncated toward zero and clamped into the levels; NaN outside the mesh.
+    ``return_cells``: also the int32 [height, width] cell map."""
+    import torch
+    cfg = _remap_cfg(width, height, lat_range, lon_range, layer=layer)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    image = torch.empty((cfg.height, cfg.width, 4), dtype=torch.float64, device=dev)
+    cells = torch.empty((cfg.height, cfg.width), dtype=torch.int32, device=dev) if return_cells else None
+    h = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    L.check(L.load().mops_remap_fixed_layer(mesh.handle, field.handle, C.byref(cfg), C.c_void_p(image.data_ptr()),
+                                            None if cells is None else C.c_void_p(cells.data_ptr()),
+                                            _stream_handle(h)), "mops_remap_fixed_layer")
+    return (image, cells) if return_cells else image
+
+
+def colormap_rgba(image_cuda, channels=(0, 1, 2), return_minmax: bool = False, stream=None):
+    """MOPS::SaveToPNG's colouring on the device (mops_colormap_rgba8): a float64 CUDA image [H, W, 4] -> a
+    uint8 CUDA tensor [len(channels), H, W, 4] (RGBA, Viridis; NaN pixels {0, 0, 0, 0}), one plane per entry of
+    ``channels`` (each 0..3, strictly ascending).  ``return_minmax``: also a float32 numpy array
+    [len(channels), 2], every selected channel's {min, max} as the map used them."""
+    import torch
+    t = image_cuda
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 3
+            and t.shape[2] == 4 and t.is_contiguous() and t.numel() > 0):
+        raise ValueError("colormap_rgba: expected a contiguous float64 CUDA tensor [H, W, 4]")
+    channels = [int(c) for c in channels]
+    if not channels or any(c < 0 or c > 3 for c in channels) or any(b <= a for a, b in zip(channels, channels[1:])):
+        raise ValueError("colormap_rgba: channels must be strictly ascending values in 0..3")
+    mask = sum(1 << c for c in channels)
+    hgt, wid = int(t.shape[0]), int(t.shape[1])
+    out = torch.empty((len(channels), hgt, wid, 4), dtype=torch.uint8, device=t.device)
+    mm = np.empty((4, 2), dtype=np.float32) if return_minmax else None
+    with torch.cuda.device(t.device):
+        h = stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream
+        L.check(L.load().mops_colormap_rgba8(C.c_void_p(t.data_ptr()), wid, hgt, mask, C.c_void_p(out.data_ptr()),
+                                             _ptr(mm), _stream_handle(h)), "mops_colormap_rgba8")
+    return (out, mm[channels]) if return_minmax else out

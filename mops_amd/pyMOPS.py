@@ -16,6 +16,13 @@ script runs unchanged with ``from mops_amd import pyMOPS``:
     MOPS_ResetTiming / MOPS_PrintTimingSummary / MOPS_PrintTimingDetailed /
     MOPS_GetCategoryTime / MOPS_GetTotalTime   (:457-475)
 
+and, beyond the pybind module, the image output of the reference's C++ side:
+
+    SaveToPNG(image, filename, channel=3)      MOPS::SaveToPNG (src/Common/ImageBuffer.hpp:91-136)
+    SaveVTI(images, config, names, outputName) VTKFileManager::SaveVTI (src/IO/VTKFileManager.hpp:25-138)
+    MOPS_RunRemappingFixedLayer(config)        extension: Kernel::VisualizeFixedLayer, which MOPS_RunRemapping
+                                               never reaches (MOPSApp.cpp:192)
+
 Every trajectory and every image goes through the HIP engine
 (``engine.run_trajectories`` / ``engine.remap_fixed_depth`` /
 ``engine.remap_fixed_latitude`` on the C ABI); there is no CPU path.
@@ -282,6 +289,7 @@ class VisualizationSettings:
         self.FixedLatitude = 0.0
         self.FixedDepth = 0.0
         self.TimeStep = 0.0
+        self.tile_index = 0                 # uninitialised in the reference; its CLI prints it into the VTI name
         self.CalcType = CalcAttributeType.kZonalMerimoal
         self.VisType = VisualizeType.kFixedDepth
         self.PositionType = CalcPositionType.kPoint
@@ -293,7 +301,13 @@ class VisualizationSettings:
             if len(value) != 2:
                 raise RuntimeError(f"{name} must be a tuple of size 2")
             value = (float(value[0]), float(value[1]))
+        if name == "FixedLayer":  # `union { double FixedDepth; double FixedLayer; }` (MPASOVisualizer.h:31-35)
+            name = "FixedDepth"
         object.__setattr__(self, name, value)
+
+    @property
+    def FixedLayer(self):
+        return self.FixedDepth
 
 
 class SeedsSettings:
@@ -554,17 +568,83 @@ def _front_vertex_attrs():
 
 def MOPS_RunRemapping(config: VisualizationSettings):
     """MOPSApp::runRemapping (MOPSApp.cpp:171-196) -> a list of [H, W, 4] float64 arrays (bindings.cpp:287-299)."""
+    images = _remap_device(config)
+    if images is None:
+        return []
+    host = images.cpu().numpy()
+    return [host[k] for k in range(host.shape[0])]
+
+
+def _remap_device(config: VisualizationSettings):
+    """MOPS_RunRemapping's images where the kernel wrote them: one float64 CUDA tensor [n, H, W, 4], or None
+    for invalid inputs.  Fixed depth whatever ``VisType`` says, as the reference (MOPSApp.cpp:192).  The CLI
+    colours these in place and never copies the doubles to the host."""
     with _Timer("GPUKernel::Remapping", "GPUKernel"):
         if config is None or _app.mesh is None or _app.front is None:  # MPASOVisualizerKernels.cpp:240-243
             _error("[MI355X::VisualizeFixedDepth] invalid inputs")
-            return []
+            return None
         w, h = int(config.imageSize[0]), int(config.imageSize[1])
         n_attr, vattrs = _front_vertex_attrs()
-        images = _E.remap_fixed_depth(_app.mesh, _app.front, w, h, config.LatRange, config.LonRange,
-                                      float(config.FixedDepth), n_attr=n_attr, vertex_attrs=vattrs,
-                                      layer_rule=getattr(config, "layerRule", "reference"))
-        host = images.cpu().numpy()
-        return [host[k] for k in range(host.shape[0])]
+        return _E.remap_fixed_depth(_app.mesh, _app.front, w, h, config.LatRange, config.LonRange,
+                                    float(config.FixedDepth), n_attr=n_attr, vertex_attrs=vattrs,
+                                    layer_rule=getattr(config, "layerRule", "reference"))
+
+
+def MOPS_RunRemappingFixedLayer(config: VisualizationSettings):
+    """Extension (the reference's MOPSApp has no fixed-layer entry; its kernel is reached through
+    MPASOVisualizer::VisualizeFixedLayer): Kernel::VisualizeFixedLayer (MPASOVisualizerKernels.cpp:141-236) of
+    the active front solution at ``config.FixedLayer`` -> one [H, W, 4] float64 array {zonal, meridional, 0, 1}."""
+    with _Timer("GPUKernel::FixedLayer", "GPUKernel"):
+        w, h = (int(config.imageSize[0]), int(config.imageSize[1])) if config is not None else (0, 0)
+        if config is None or _app.mesh is None or _app.front is None or w <= 0 or h <= 0:  # :143-161
+            _error("[MI355X::VisualizeFixedLayer] invalid inputs")
+            return np.zeros((max(h, 0), max(w, 0), 4))
+        image = _E.remap_fixed_layer(_app.mesh, _app.front, w, h, config.LatRange, config.LonRange,
+                                     float(config.FixedLayer))
+        return image.cpu().numpy()
+
+
+def SaveToPNG(image, filename: str, channel: int = 3) -> bool:
+    """MOPS::SaveToPNG (ImageBuffer.hpp:91-136): one channel of an [H, W, 4] image (numpy or CUDA tensor)
+    through the Viridis map into an RGBA PNG; the colouring runs on the GPU (io.save_image_png)."""
+    from . import io as _io
+    with _Timer("IO::SavePNG", "IO"):
+        return _io.save_image_png(filename, image, channel)
+
+
+def TypeToStr(vis_type) -> str:
+    """VTKFileManager.hpp:12-20."""
+    return {int(VisualizeType.kFixedLayer): "fixed_layer_", int(VisualizeType.kFixedDepth): "fixed_depth_"}.get(
+        int(vis_type), "unknown_")
+
+
+def vti_file_name(config: VisualizationSettings, outputName: str = "output") -> str:
+    """outputName + "_" + TypeToStr(VisType) + std::to_string(k) + ".vti" (VTKFileManager.hpp:74, :133);
+    std::to_string(double) prints "%f": fixed_depth_10.000000."""
+    return f"{outputName}_{TypeToStr(config.VisType)}{float(config.FixedDepth):f}.vti"
+
+
+def SaveVTI(images, config: VisualizationSettings, names=(), outputName: str = "output") -> str:
+    """VTKFileManager::SaveVTI (VTKFileManager.hpp:25-138).  A list (or [n, H, W, 4] array) of images takes the
+    multi-attribute overload: three one-component arrays per image, named from ``names`` then "attr_<i>",
+    z spacing 1.  One [H, W, 4] image takes the single-image overload: one 3-component array "ImageScalars",
+    z spacing k.  Origin (LonRange[0], LatRange[0], k), spacing range / (size - 1), k = FixedDepth / FixedLayer
+    (one union).  Returns the file name written."""
+    from . import io as _io
+    with _Timer("IO::SaveVTI", "IO"):
+        k = float(config.FixedDepth)
+        w, h = config.imageSize
+        with np.errstate(all="ignore"):
+            lat_sp = float(np.float64(config.LatRange[1] - config.LatRange[0]) / np.float64(h - 1))
+            lon_sp = float(np.float64(config.LonRange[1] - config.LonRange[0]) / np.float64(w - 1))
+        origin = (config.LonRange[0], config.LatRange[0], k)
+        name = vti_file_name(config, outputName)
+        single = not isinstance(images, (list, tuple)) and getattr(images, "ndim", 0) == 3
+        if single:
+            _io.save_image_vti(name, images, origin, (lon_sp, lat_sp, k))
+        else:
+            _io.save_images_vti(name, images, origin, (lon_sp, lat_sp, 1.0), names)
+        return name
 
 
 def MOPS_RunReGrid(config: VisualizationSettings):
