@@ -140,6 +140,11 @@ struct TrajectorySettings {
     CalcDirection directionType = CalcDirection::kForward;
     CalcMethodType methodType = CalcMethodType::kEuler;
     bool hasPerParticleDepths() const { return !particle_depths.empty(); }
+    // This engine's extension (default: the reference's output, quirk Q9).  True: MOPS_RunPathLine samples the
+    // first two double attributes, in name order, that both active solutions carry (Kernel::PathLine's
+    // current_attrs, MPASOVisualizerKernels.cpp:1288-1324) and fills TrajectoryLine::temperature / salinity with
+    // the attributes of those names (zeros for a name that is not sampled).  MOPS_RunStreamLine ignores it.
+    bool sampleAttributes = false;
 };
 
 struct SamplingSettings {

@@ -321,6 +321,70 @@ mops_status mops_traj_finalize(int64_t n, int64_t K, const double* d_seeds, cons
 mops_status mops_traj_last_points(int64_t n, int64_t K, const double* d_seeds, const double* d_records,
                                   int64_t record_stride, const int32_t* d_line, double* d_last_point, void* stream);
 
+/* ---- attribute sampling along pathlines (opt-in) -------------------------- */
+
+/* Attributes one call samples at most (the reference's vec3 channel holds two,
+ * MPASOVisualizerKernels.cpp:1288-1324). */
+#define MOPS_MAX_SAMPLE_ATTRS 4
+
+/* The attribute channel of Kernel::PathLine (MPASOVisualizerKernels.cpp:
+ * 1091-1104, :1288-1324, :1431, :1453-1456, :1476-1478), which the reference
+ * computes at every evaluation and FinalizeTrajectoryLinesWithAttrs then drops
+ * (src/Common/TrajectoryCommon.h:176-185, quirk Q9).  Attribute arrays are
+ * DEVICE vertex arrays [V*L] in the caller's vertex order, as
+ * mops_cell_to_vertex_attr makes them (mDoubleAttributes_CtoV), one per field
+ * and attribute.  The slab d_attr_records is [K][n_attr][attr_stride] doubles,
+ * zero-filled by the caller before step 0 (the reference's update_attrs after
+ * vector::resize); a particle that never reaches a slot leaves its zero there.
+ *
+ * Sample steps of a run, with ri = record_t / delta_t (:1470): step 0 writes
+ * slot 0 (the first_attr pre-write, :1453-1456, which a later record into
+ * slot 0 overwrites); every step j < n_steps with ri > 0 and (j + 1) % ri == 0
+ * writes slot (j + 1) / ri - 1 when that slot is below K (:1470-1481).
+ *
+ * mops_traj_sample_attrs: one sample step for particles that stand exactly at
+ * `step` (after mops_traj_advance over [.., step), or fresh seeds for step 0).
+ * It evaluates that step as the pathline loop does before the move -- the
+ * one-hop walk (:1361-1381, step > 0), calc_velocity_at with its attributes at
+ * the position, cell, float depth and alpha the step starts from; for RK4 the
+ * four stages and their weighted mean (:1404-1432) -- and writes current_attrs
+ * into the step's slot for every live particle the step does not kill.  It
+ * reads the particle state only: positions, depths, cells and death steps
+ * stay untouched.  d_order and d_n_live are honoured as by mops_traj_advance.
+ * MOPS_ERR_INVALID for a null handle or pointer, n_attr outside
+ * 1..MOPS_MAX_SAMPLE_ATTRS, attr_stride < n or a step that is not a sample
+ * step; MOPS_ERR_UNSUPPORTED for back == NULL (the reference's StreamLine has
+ * no attribute channel).  Every argument is checked before any device work. */
+mops_status mops_traj_sample_attrs(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                   const mops_traj_cfg* cfg, const mops_particles* particles, int64_t step,
+                                   int32_t n_attr, const double* const* d_front_attrs,
+                                   const double* const* d_back_attrs, double* d_attr_records, int64_t attr_stride,
+                                   void* stream);
+
+/* mops_traj_advance over [step_begin, step_end) with the attribute channel
+ * (Kernel::PathLine, MPASOVisualizerKernels.cpp:1329-1483): one host call that
+ * advances to each sample step of the range, samples it
+ * (mops_traj_sample_attrs) and goes on.  Positions, records, depths and death
+ * steps are those of mops_traj_advance over the same range, bit for bit
+ * (mops_traj_advance is exact over consecutive step ranges).  Argument checks
+ * as mops_traj_sample_attrs, before any device work. */
+mops_status mops_traj_advance_sampled(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                      const mops_traj_cfg* cfg, const mops_particles* particles, int64_t step_begin,
+                                      int64_t step_end, double* d_records, int64_t record_stride, int32_t n_attr,
+                                      const double* const* d_front_attrs, const double* const* d_back_attrs,
+                                      double* d_attr_records, int64_t attr_stride, void* stream);
+
+/* The attribute lines from the slab, with the cleanup
+ * RemoveNaNTrajectoriesAndReindex applies to temperature / salinity
+ * (src/Common/TrajectoryCommon.h:88-121): entry j < K of a line is slot j,
+ * entry K the appended 0 (:88-90); with k the first non-finite point of the
+ * line (the seed at index 0, record j at index j + 1), k == 0 sets every entry
+ * to entry 0 and 0 < k < K + 1 sets the entries j >= k to entry k - 1.
+ * d_line as in mops_traj_finalize; d_attr_lines is [n_attr][n*(K+1)]. */
+mops_status mops_traj_finalize_attrs(int64_t n, int64_t K, const double* d_seeds, const double* d_records,
+                                     int64_t record_stride, int32_t n_attr, const double* d_attr_records,
+                                     int64_t attr_stride, const int32_t* d_line, double* d_attr_lines, void* stream);
+
 /* RemoveNaNTrajectoriesAndReindex alone on n lines of P points each, in
  * place (device pointers; [n*P*3], [n*P*3], [n*P], [n*P], out [n*3]). */
 mops_status mops_remove_nan_lines(int64_t n, int64_t P, double* d_points, double* d_velocity,
@@ -462,6 +526,22 @@ mops_status mops_run_trajectories(const mops_mesh* mesh, const mops_field* front
                                   double* h_velocity, double* h_temperature, double* h_salinity,
                                   double* h_last_point, double* h_final_pos, float* h_final_depth,
                                   int32_t* h_death_step, void* stream);
+
+/* mops_run_trajectories for a PathLine with the attribute channel
+ * (Kernel::PathLine's current_attrs, MPASOVisualizerKernels.cpp:1288-1324,
+ * :1431, :1453-1456, :1476-1478): the same arguments and outputs -- h_temperature
+ * / h_salinity keep the velocity x / y of quirk Q9 -- plus n_attr (1..
+ * MOPS_MAX_SAMPLE_ATTRS) pairs of DEVICE vertex attribute arrays [V*L]
+ * (mops_cell_to_vertex_attr) and h_attr_lines [n_attr][n*(K+1)], the sampled
+ * attribute lines after the reference's cleanup (mops_traj_finalize_attrs).
+ * MOPS_ERR_UNSUPPORTED for back == NULL. */
+mops_status mops_run_pathline_attrs(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                    const mops_traj_cfg* cfg, int64_t n, const double* h_seeds,
+                                    const float* h_depths, float depth, int32_t* h_cells, double* h_points,
+                                    double* h_velocity, double* h_temperature, double* h_salinity,
+                                    double* h_last_point, double* h_final_pos, float* h_final_depth,
+                                    int32_t* h_death_step, int32_t n_attr, const double* const* d_front_attrs,
+                                    const double* const* d_back_attrs, double* h_attr_lines, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -63,6 +64,7 @@ struct App {
     mops_field* front = nullptr;
     mops_field* back = nullptr;
     int front_id = 0;  // the solution behind `front` (its attributes feed the remapping)
+    int back_id = 0;   // the solution behind `back` (attribute sampling along pathlines)
 
     void release() {
         for (auto& kv : fields) mops_field_destroy(kv.second);
@@ -134,11 +136,70 @@ std::vector<TrajectoryLine> run(TrajectorySettings* config, std::vector<Cartesia
     const int64_t P = K + 1;
     std::vector<double> hp((size_t)(n * P * 3)), hv((size_t)(n * P * 3)), ht((size_t)(n * P)), hs((size_t)(n * P)),
         hl((size_t)(n * 3));
-    check(mops_run_trajectories(g_app.mesh, g_app.front, pathline ? g_app.back : nullptr, &cfg, n,
-                                reinterpret_cast<const double*>(pts.data()), depths.data(), config->depth, nullptr,
-                                hp.data(), hv.data(), ht.data(), hs.data(), hl.data(), nullptr, nullptr, nullptr,
-                                nullptr),
-          "mops_run_trajectories");
+    if (pathline && config->sampleAttributes) {
+        // TrajectorySettings::sampleAttributes: the first two names, in std::map order, that both solutions carry
+        // (the reference's size() > 1 gate, MPASOVisualizerKernels.cpp:1093, is not kept: one name is enough)
+        const auto fs = g_app.sols.find(g_app.front_id), bs = g_app.sols.find(g_app.back_id);
+        std::vector<std::string> names;
+        if (fs != g_app.sols.end() && bs != g_app.sols.end() && fs->second && bs->second)
+            for (const auto& kv : fs->second->mDoubleAttributes)
+                if (names.size() < 2 && bs->second->mDoubleAttributes.count(kv.first)) names.push_back(kv.first);
+        const size_t VL = (size_t)g_app.grid->mVertexSize * g_app.grid->mVertLevels,
+                     CL = (size_t)g_app.grid->mCellsSize * g_app.grid->mVertLevels;
+        const int na = (int)names.size();
+        struct DevBuf {
+            void* p = nullptr;
+            ~DevBuf() { (void)hipFree(p); }
+        } buf;  // 2 na vertex arrays | one cell staging array
+        auto hip = [](hipError_t e, const char* what) {
+            if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+        };
+        const double* d_fa[2] = {nullptr, nullptr};
+        const double* d_ba[2] = {nullptr, nullptr};
+        if (na > 0) {
+            hip(hipMalloc(&buf.p, (2 * (size_t)na * VL + CL) * sizeof(double)), "MOPS_RunPathLine: hipMalloc");
+            double* base = static_cast<double*>(buf.p);
+            double* d_cell = base + 2 * (size_t)na * VL;
+            for (int k = 0; k < 2 * na; ++k) {  // mDoubleAttributes_CtoV (MOPSApp.cpp:119-127) of both solutions
+                const auto& sol = (k < na) ? fs->second : bs->second;
+                const auto& vec = sol->mDoubleAttributes.at(names[(size_t)(k % na)]);
+                if (vec.size() != CL)
+                    throw std::runtime_error("MOPS_RunPathLine: attribute " + names[(size_t)(k % na)] +
+                                             " is not [nCells*nVertLevels]");
+                double* d_v = base + (size_t)k * VL;
+                hip(hipMemcpy(d_cell, vec.data(), CL * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy attribute");
+                check(mops_cell_to_vertex_attr(g_app.mesh, d_cell, d_v, nullptr), "mops_cell_to_vertex_attr");
+                hip(hipDeviceSynchronize(), "mops_cell_to_vertex_attr");
+                (k < na ? d_fa : d_ba)[k % na] = d_v;
+            }
+        }
+        std::vector<double> ha((size_t)(std::max(na, 1) * n * P));
+        if (na > 0)
+            check(mops_run_pathline_attrs(g_app.mesh, g_app.front, g_app.back, &cfg, n,
+                                          reinterpret_cast<const double*>(pts.data()), depths.data(), config->depth,
+                                          nullptr, hp.data(), hv.data(), ht.data(), hs.data(), hl.data(), nullptr, nullptr,
+                                          nullptr, na, d_fa, d_ba, ha.data(), nullptr),
+                  "mops_run_pathline_attrs");
+        else
+            check(mops_run_trajectories(g_app.mesh, g_app.front, g_app.back, &cfg, n,
+                                        reinterpret_cast<const double*>(pts.data()), depths.data(), config->depth, nullptr,
+                                        hp.data(), hv.data(), ht.data(), hs.data(), hl.data(), nullptr, nullptr, nullptr,
+                                        nullptr),
+                  "mops_run_trajectories");
+        // temperature / salinity by NAME (map order puts salinity first); zeros for a name that is not sampled
+        std::fill(ht.begin(), ht.end(), 0.0);
+        std::fill(hs.begin(), hs.end(), 0.0);
+        for (int a = 0; a < na; ++a) {
+            std::vector<double>* dst = names[(size_t)a] == "temperature" ? &ht : (names[(size_t)a] == "salinity" ? &hs : nullptr);
+            if (dst) std::copy(ha.begin() + (size_t)a * n * P, ha.begin() + (size_t)(a + 1) * n * P, dst->begin());
+        }
+    } else {
+        check(mops_run_trajectories(g_app.mesh, g_app.front, pathline ? g_app.back : nullptr, &cfg, n,
+                                    reinterpret_cast<const double*>(pts.data()), depths.data(), config->depth, nullptr,
+                                    hp.data(), hv.data(), ht.data(), hs.data(), hl.data(), nullptr, nullptr, nullptr,
+                                    nullptr),
+              "mops_run_trajectories");
+    }
     for (int64_t i = 0; i < n; ++i) {  // FinalizeTrajectoryLines[WithAttrs] + RemoveNaN (device-side)
         auto& l = lines[(size_t)i];
         l.points.resize((size_t)P);
@@ -338,6 +399,7 @@ void MOPS_ActiveAttribute(int t1, std::optional<int> t2) {  // MOPSApp.cpp:145-1
             return;
         }
         g_app.back = it2->second;
+        g_app.back_id = t2.value();
     }
     g_app.front = it->second;
     g_app.front_id = t1;

@@ -758,6 +758,13 @@ __device__ __forceinline__ void load_cell(Cell<MAXV>& c, int cell, const int* __
 // polygon), 2.4x slower
 template <int NV, int MAXV>
 __device__ __forceinline__ int nverts(const Cell<MAXV>& c) { return NV > 0 ? NV : c.nv; }
+// NV = kNvSample (< 0) is NV = 0 -- the count read from the cell -- in instantiations of its own, for the
+// attribute sampling kernel (eval_path_attrs; layer_eval passes it on to the brackets as their TAG).  The
+// compiler's interprocedural passes run before inlining and fold what all call sites of an instantiation agree
+// on, so a new caller of the trajectory kernels' instantiations changed a few lines of the wide-stencil (MAXV
+// 12 / 20) trajectory kernels.  With a set of its own the sampling kernel leaves every trajectory kernel's
+// device code as it was profiled (tools/asm_compare.py).
+constexpr int kNvSample = -1;
 
 template <int MAXV, int NV>
 __device__ __forceinline__ bool weights_finite(const Cell<MAXV>& c, const double* w) {
@@ -900,7 +907,7 @@ __device__ __forceinline__ double col(const Cell<MAXV>& c, const double* w, cons
 // the scan stops at the first level where both are known.  If a exists the
 // reference's "below the bottom" test is provably false (z'_{L-1} <= z'_a).
 // Returns the layer (or -1 = fail) and z'_layer, z'_{layer-1}.
-template <int MAXV, bool PATH>
+template <int MAXV, bool PATH, int TAG = 0>  // (TAG: see kNvSample)
 __device__ __forceinline__ int bracket_scan(const Cell<MAXV>& c, const double* w, const double* __restrict__ zt,
                                             int L, double d, double& zdn, double& zup) {
     const double eps = 1e-8;
@@ -981,7 +988,7 @@ __device__ __forceinline__ int bracket_scan(const Cell<MAXV>& c, const double* w
 // below its bottom.  A NaN below the prefix (the column is no longer
 // non-increasing there) returns -2 and the caller runs bracket_scan, as does a
 // binary-search layer strictly inside (a, b) below the prefix.
-template <int MAXV, bool PATH>
+template <int MAXV, bool PATH, int TAG = 0>  // (TAG: see kNvSample)
 __device__ __forceinline__ int bracket_mono(const Cell<MAXV>& c, const double* w, const double* __restrict__ zt,
                                             int L, int km, double d, int& hint, double& zdn, double& zup) {
     const double eps = 1e-8;
@@ -1383,9 +1390,9 @@ __device__ __forceinline__ int layer_eval(const Cell<MAXV>& c, const double* w, 
     MOPS_CNT(6, 1);
     double zdn, zup;
     int layer = -2;
-    if (km >= 1) layer = bracket_mono<MAXV, PATH>(c, w, f.zt, L, km, d, hint, zdn, zup);
+    if (km >= 1) layer = bracket_mono<MAXV, PATH, (NV < 0)>(c, w, f.zt, L, km, d, hint, zdn, zup);
     if (layer == -2) {
-        layer = bracket_scan<MAXV, PATH>(c, w, f.zt, L, d, zdn, zup);
+        layer = bracket_scan<MAXV, PATH, (NV < 0)>(c, w, f.zt, L, d, zdn, zup);
         hint = layer;
     }
     if (layer < 0) return -1;
@@ -1428,8 +1435,9 @@ __device__ __forceinline__ bool eval_stream(const Cell<MAXV>& c, int L, int V, c
 }
 
 // pathline calc_velocity_at (MPASOVisualizerKernels.cpp:1124-1327).  The
-// attribute channel is not evaluated: FinalizeTrajectoryLinesWithAttrs never
-// reads it (TrajectoryCommon.h:176-185, quirk Q9), so it is unobservable.
+// attribute channel is not evaluated here: FinalizeTrajectoryLinesWithAttrs never
+// reads it (TrajectoryCommon.h:176-185, quirk Q9).  The opt-in sampling evaluates
+// it between launches (eval_path_attrs, traj_sample_attrs_kernel).
 template <int MAXV, int GR, int NV, bool COOP = false, bool TCHK = false>
 __device__ __forceinline__ bool eval_path(const Cell<MAXV>& c, int L, int V, const Field& ff, const Field& fb,
                                           double px, double py, double pz, double d, double alpha, int& hint0,
@@ -1463,6 +1471,66 @@ __device__ __forceinline__ bool eval_path(const Cell<MAXV>& c, int L, int V, con
     const double wf = tf * F.wm + (1.0 - tf) * F.wk;
     const double wb = tb * B.wm + (1.0 - tb) * B.wk;
     wv = alpha * wb + (1.0 - alpha) * wf;
+    return true;
+}
+
+// eval_path with the attribute channel (calc_velocity_at's current_attr, MPASOVisualizerKernels.cpp:1288-1324),
+// for the sampling kernel (traj_sample_attrs_kernel): per lane, general vertex count, no tile.  The weights, the
+// layers, tf, tb and every failure test come from the same code as eval_path, so it fails exactly where that
+// does.  Per attribute: the CalcAttribute sums (TBBKernel.h:149-166) at the layer and the one above it -- adjacent
+// doubles of a vertex row -- in vertex order from 0.0, blended by tf / tb and then by alpha.  The attribute arrays
+// are in the caller's vertex order (vold: internal vertex -> the caller's, NULL = identity).  Returns the
+// horizontal velocity too (the RK4 stage positions need it); the vertical one is not formed (nothing moves).
+template <int MAXV, int GR>
+__device__ __forceinline__ bool eval_path_attrs(const Cell<MAXV>& c, int L, int V, const Field& ff, const Field& fb,
+                                                double px, double py, double pz, double d, double alpha, int& hint0,
+                                                int& hint1, double& hx, double& hy, double& hz, int n_attr,
+                                                const double* const* af, const double* const* ab,
+                                                const int* __restrict__ vold, double* attr) {
+    double w[MAXV];
+    bool wfin;
+    constexpr int NV = kNvSample;  // the general vertex count, instantiations of its own
+    if (!weights<MAXV, NV>(c, L, V, px, py, pz, w, wfin)) return false;
+    Pair F, B;
+    const int lf = layer_eval<MAXV, true, GR, NV>(c, w, fast_ok<MAXV, NV>(c, c.mono0, wfin, w), ff, L, d, hint0, F);
+    const int lb = layer_eval<MAXV, true, GR, NV>(c, w, fast_ok<MAXV, NV>(c, c.mono1, wfin, w), fb, L, d, hint1, B);
+    if (lf < 0 || lb < 0) return false;
+    const double xf = dmax(F.zk, dmin(d, F.zm));
+    const double denf = F.zm - F.zk;
+    if (fabs(denf) < 1e-12) return false;
+    const double tf = (xf - F.zk) / denf;
+    const double xb = dmax(B.zk, dmin(d, B.zm));
+    const double denb = B.zm - B.zk;
+    if (fabs(denb) < 1e-12) return false;
+    const double tb = (xb - B.zk) / denb;
+    const double fx = F.um0 * tf + F.uk0 * (1.0 - tf), fy = F.um1 * tf + F.uk1 * (1.0 - tf),
+                 fz = F.um2 * tf + F.uk2 * (1.0 - tf);
+    const double gx = B.um0 * tb + B.uk0 * (1.0 - tb), gy = B.um1 * tb + B.uk1 * (1.0 - tb),
+                 gz = B.um2 * tb + B.uk2 * (1.0 - tb);
+    hx = gx * alpha + fx * (1.0 - alpha);
+    hy = gy * alpha + fy * (1.0 - alpha);
+    hz = gz * alpha + fz * (1.0 - alpha);
+    // rows of the stencil's vertices in the attribute arrays (layers are 1..L-1: the level above exists)
+    int64_t row[MAXV];
+#pragma unroll
+    for (int v = 0; v < MAXV; ++v) row[v] = (v < c.nv) ? (int64_t)(vold ? vold[c.vid[v]] : c.vid[v]) * L : 0;
+    for (int a = 0; a < n_attr; ++a) {
+        const double* __restrict__ pf = af[a] + lf;
+        const double* __restrict__ pb = ab[a] + lb;
+        double dnf = 0.0, upf = 0.0, dnb = 0.0, upb = 0.0;
+#pragma unroll
+        for (int v = 0; v < MAXV; ++v) {
+            if (v < c.nv) {
+                dnf += w[v] * pf[row[v]];
+                upf += w[v] * pf[row[v] - 1];
+                dnb += w[v] * pb[row[v]];
+                upb += w[v] * pb[row[v] - 1];
+            }
+        }
+        const double attr_f = tf * upf + (1.0 - tf) * dnf;
+        const double attr_b = tb * upb + (1.0 - tb) * dnb;
+        attr[a] = alpha * attr_b + (1.0 - alpha) * attr_f;
+    }
     return true;
 }
 
@@ -2100,6 +2168,99 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
     }
 }
 
+// ===========================================================================
+// attribute sampling along pathlines (mops_traj_sample_attrs)
+// ===========================================================================
+struct SampleArgs {
+    TrajArgs t;  // the mesh, the fields and the particle state as traj_kernel takes them; step_begin = the sample step
+    const int* __restrict__ vold;  // internal vertex -> the caller's vertex (mops_mesh::d_vold), NULL = identity
+    int n_attr;
+    const double* af[MOPS_MAX_SAMPLE_ATTRS];  // front / back vertex attribute arrays [V][L], the caller's vertex order
+    const double* ab[MOPS_MAX_SAMPLE_ATTRS];
+    double* out;  // the step's slot of the attribute slab: [n_attr][stride]
+    int64_t stride;
+};
+
+// One lane per slot: what step t.step_begin of Kernel::PathLine's loop (MPASOVisualizerKernels.cpp:1344-1437) does
+// before the move, with calc_velocity_at's attribute channel (:1288-1324), for a particle whose state stands
+// exactly at that step (between two traj_kernel launches).  Reads the state only: nothing is stored to the
+// position, depth, cell or death step.  A dead lane does nothing; a lane the step kills (a cell out of range,
+// a failed evaluation or RK4 stage) writes nothing either -- the reference's lambda returns before the
+// first_attr pre-write (:1453-1456) and the record write (:1476-1478), so the slot keeps its zero.  The walk is
+// the plain one-hop walk from the stored cell (dev::walk): traj_kernel's stay-ball and neighbour-table shortcuts
+// are exact, so it gives their answer.  Gather-bound (2 nv eight-byte loads per attribute, field and
+// evaluation), no LDS; built with the engine's flags (no contraction).
+template <int MAXV, bool EULER>
+__global__ void __launch_bounds__(256) traj_sample_attrs_kernel(SampleArgs s) {
+    const TrajArgs& a = s.t;
+    int64_t n = a.n;
+    if (a.n_live) {
+        const int64_t nl = *a.n_live;
+        n = nl < n ? nl : n;
+    }
+    const int64_t slot = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= n) return;
+    const int64_t pid = a.order ? (int64_t)a.order[slot] : slot;
+    if (a.death[pid] >= 0) return;  // the reference's lambda has returned
+    const int step = (int)a.step_begin;
+    const double x = a.px[pid], y = a.py[pid], z = a.pz[pid];
+    int cell = a.cell[pid];
+    const int C = a.C;
+    if (cell < 0 || cell >= C) return;  // :1354-1356, :1362-1364 (the step kills the particle)
+    dev::Cell<MAXV> c;
+    c.id = -1;
+    c.nv = 0;
+    c.V = a.V;
+    c.cpolyr = a.cpolyr;
+    c.crank = a.crank;
+    c.C = (uint32_t)C;
+    c.nrm = nullptr;
+    c.lds_n = false;  // (edge normals per evaluation, polygon re-read per evaluation: no register cache, no LDS)
+    dev::load_cell<MAXV, false, false>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly);
+    if (step > 0) {  // the one-hop nearest-centre walk (:1361-1381)
+        cell = dev::walk<MAXV>(c, cell, x, y, z, a.cellrec, a.cxyz, C);
+        if (c.id != cell) dev::load_cell<MAXV, false, false>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly);
+    }
+    const double d = -1.0 * (double)a.depth[pid];
+    const double alpha = a.alpha_tab ? a.alpha_tab[step] : (double)step / (double)a.n_steps;  // (the same bits)
+    int hint0 = -1, hint1 = -1;
+    constexpr int GR = PairGroup<true, EULER>::value;
+    double attr[MOPS_MAX_SAMPLE_ATTRS] = {0.0, 0.0, 0.0, 0.0};
+    double hx, hy, hz;
+    if (EULER) {
+        if (!dev::eval_path_attrs<MAXV, GR>(c, a.L, a.V, a.f0, a.f1, x, y, z, d, alpha, hint0, hint1, hx, hy, hz,
+                                            s.n_attr, s.af, s.ab, s.vold, attr))
+            return;
+    } else {
+        // the four stages (:1403-1428) in the start cell (quirk Q1), one evaluation in a loop: stage 0 at the
+        // position, stages 1-2 half a step along the previous stage's velocity, stage 3 a whole step; the mean
+        // ((s1 + 2 s2) + 2 s3 + s4) / 6 in traj_kernel's form for the velocity (:1431)
+        const double dt = (double)a.delta_t;
+        const double a2 = dev::dclamp(alpha + 0.5 * a.dalpha, 0.0, 1.0), a4 = dev::dclamp(alpha + a.dalpha, 0.0, 1.0);
+        double sum[MOPS_MAX_SAMPLE_ATTRS] = {0.0, 0.0, 0.0, 0.0};
+        double qx = x, qy = y, qz = z;
+#pragma unroll 1
+        for (int st = 0; st < 4; ++st) {
+            if (st > 0) dev::advect((unsigned)step, x, y, z, hx, hy, hz, st == 3 ? dt : dt * 0.5, qx, qy, qz);
+            const double as = st == 0 ? alpha : (st == 3 ? a4 : a2);
+            if (!dev::eval_path_attrs<MAXV, GR>(c, a.L, a.V, a.f0, a.f1, qx, qy, qz, d, as, hint0, hint1, hx, hy, hz,
+                                                s.n_attr, s.af, s.ab, s.vold, attr))
+                return;
+#pragma unroll
+            for (int k = 0; k < MOPS_MAX_SAMPLE_ATTRS; ++k) {
+                if (st == 0) sum[k] = attr[k];
+                else if (st < 3) sum[k] = sum[k] + attr[k] * 2.0;
+                else sum[k] = (sum[k] + attr[k]) / 6.0;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < MOPS_MAX_SAMPLE_ATTRS; ++k) attr[k] = sum[k];
+    }
+#pragma unroll
+    for (int k = 0; k < MOPS_MAX_SAMPLE_ATTRS; ++k)
+        if (k < s.n_attr) s.out[(int64_t)k * s.stride + pid] = attr[k];
+}
+
 // the neighbour-table test against the walk it short-cuts (mops_selftest_walk): bit 0 = dev::nbr_stay kept
 // the cell, bit 1 = dev::walk kept it, bits 8.. = the stay-ball radius nbr_stay set, in metres (clamped)
 __global__ void selftest_walk_kernel(int64_t n, const double* __restrict__ pts, const int* __restrict__ cells,
@@ -2403,6 +2564,47 @@ __global__ void __launch_bounds__(256) last_point_kernel(int64_t n, int K, const
     last[3 * o] = lx;
     last[3 * o + 1] = ly;
     last[3 * o + 2] = lz;
+}
+
+// The attribute lines from the slab [K][n_attr][stride] with RemoveNaNTrajectoriesAndReindex's cleanup of
+// temperature / salinity (TrajectoryCommon.h:88-121), 64 slots per block: each slot's first non-finite point is
+// found first (one lane per slot, the records' position rows read coalesced across the slots), then every line
+// entry is written with consecutive threads on consecutive doubles of a line -- entry j < K is slot j, entry K
+// the appended 0, the entries from the cut on hold the last entry before it (all of them entry 0 when the seed
+// itself is not finite).  Line of slot i = line ? line[i] : i; lines is [n_attr][n * (K + 1)].
+constexpr int kAttrAsmSlots = 64;
+__global__ void __launch_bounds__(256) assemble_attrs_kernel(int64_t n, int K, const double* __restrict__ seeds,
+                                                             const double* __restrict__ rec, int64_t stride,
+                                                             int n_attr, const double* __restrict__ slab,
+                                                             int64_t attr_stride, const int32_t* __restrict__ line,
+                                                             double* __restrict__ lines) {
+    __shared__ int64_t row[kAttrAsmSlots];
+    __shared__ int cut[kAttrAsmSlots];
+    const int t = threadIdx.x;
+    const int64_t s0 = (int64_t)blockIdx.x * kAttrAsmSlots;
+    const int ns = (int)((n - s0) < kAttrAsmSlots ? (n - s0) : kAttrAsmSlots);
+    const int P = K + 1;
+    if (t < ns) {
+        const int64_t i = s0 + t;
+        int k = 0;  // the first non-finite point: the seed is point 0, record j point j + 1
+        if (finite3(seeds[3 * i], seeds[3 * i + 1], seeds[3 * i + 2])) {
+            for (k = 1; k < P; ++k) {
+                const double* r = rec + (int64_t)(k - 1) * 6 * stride + i;
+                if (!finite3(r[0], r[stride], r[2 * stride])) break;
+            }
+        }
+        cut[t] = k;
+        row[t] = line ? (int64_t)line[i] : i;
+    }
+    __syncthreads();
+    for (int a = 0; a < n_attr; ++a) {
+        double* out = lines + (int64_t)a * n * P;
+        for (int e = t; e < ns * P; e += blockDim.x) {
+            const int i = e / P, j = e - i * P, k = cut[i];
+            const int src = (k < P && (k == 0 || j >= k)) ? (k == 0 ? 0 : k - 1) : j;  // the held entry's index
+            out[row[i] * P + j] = (src < K) ? slab[((int64_t)src * n_attr + a) * attr_stride + s0 + i] : 0.0;
+        }
+    }
 }
 
 // ===========================================================================
@@ -4411,6 +4613,155 @@ mops_status mops_traj_last_points(int64_t n, int64_t K, const double* d_seeds, c
     return MOPS_OK;
 }
 
+// The attribute slot step j of a pathline run writes, or -1 where j is no sample step (mops_traj.h: the first_attr
+// pre-write of step 0, MPASOVisualizerKernels.cpp:1453-1456, and the record steps, :1470-1481)
+static int64_t sample_slot(int64_t j, int64_t ri, int64_t K, int64_t n_steps) {
+    if (j < 0 || j >= n_steps) return -1;
+    if (ri > 0 && (j + 1) % ri == 0 && (j + 1) / ri - 1 < K) return (j + 1) / ri - 1;
+    return j == 0 ? 0 : -1;
+}
+
+// The argument checks of the sampling entries, all before any device work
+static mops_status sample_check(const char* who, const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                const mops_traj_cfg* cfg, const mops_particles* p, int32_t n_attr,
+                                const double* const* d_fa, const double* const* d_ba, const double* d_slab,
+                                int64_t attr_stride) {
+    const std::string w(who);
+    if (!mesh || !front || !cfg || !p) return fail(MOPS_ERR_INVALID, w + ": invalid inputs");
+    if (!back) return fail(MOPS_ERR_UNSUPPORTED, w + ": attributes are sampled along pathlines only (back == NULL)");
+    if (cfg->delta_t <= 0 || cfg->record_t <= 0 || cfg->simulation_duration <= 0)
+        return fail(MOPS_ERR_INVALID, "invalid trajectory settings");
+    const int64_t K = mops_traj_num_records(cfg), n_steps = mops_traj_num_steps(cfg);
+    if (K <= 0 || n_steps <= 0) return fail(MOPS_ERR_INVALID, "invalid integration steps");
+    if (n_steps > INT32_MAX || K > INT32_MAX || cfg->record_t / cfg->delta_t > INT32_MAX || cfg->delta_t > INT32_MAX)
+        return fail(MOPS_ERR_INVALID, w + ": the number of steps, the number of records, the record period in steps "
+                                          "and deltaT must each be below 2^31");
+    if (front->mesh != mesh || back->mesh != mesh) return fail(MOPS_ERR_INVALID, "field/mesh mismatch");
+    if (n_attr < 1 || n_attr > MOPS_MAX_SAMPLE_ATTRS)
+        return fail(MOPS_ERR_INVALID, w + ": n_attr must be 1.." + std::to_string(MOPS_MAX_SAMPLE_ATTRS));
+    if (p->n < 0 || attr_stride < p->n) return fail(MOPS_ERR_INVALID, w + ": attr_stride < n");
+    if (!d_fa || !d_ba) return fail(MOPS_ERR_INVALID, w + ": null attribute array list");
+    for (int a = 0; a < n_attr; ++a)
+        if (!d_fa[a] || !d_ba[a]) return fail(MOPS_ERR_INVALID, w + ": null attribute array");
+    if (p->n > 0 && (!p->d_x || !p->d_y || !p->d_z || !p->d_depth || !p->d_cell || !p->d_death_step || !d_slab))
+        return fail(MOPS_ERR_INVALID, w + ": null device pointer");
+    return MOPS_OK;
+}
+
+// One launch of the sampling kernel for checked arguments; `slot` = sample_slot(step)
+static mops_status sample_launch(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                 const mops_traj_cfg* cfg, const mops_particles* p, int64_t step, int64_t slot,
+                                 int32_t n_attr, const double* const* d_fa, const double* const* d_ba, double* d_slab,
+                                 int64_t attr_stride, hipStream_t s) {
+    if (p->n == 0) return MOPS_OK;
+    SampleArgs sa{};
+    TrajArgs& a = sa.t;
+    a.cellrec = mesh->d_cellrec; a.cxyz = mesh->d_cxyz; a.vxyz = mesh->d_vxyz;
+    a.C = (int)mesh->C; a.V = (int)mesh->V; a.L = mesh->L;
+    a.f0 = dev::Field{front->d_zt, front->d_pr};
+    a.f1 = dev::Field{back->d_zt, back->d_pr};
+    a.mono0 = front->d_mono;
+    a.mono1 = back->d_mono;
+    a.order = p->d_order;
+    a.n_live = p->d_n_live;
+    a.cpoly = mesh->d_cpoly;
+    a.cpolyr = mesh->d_cpolyr;
+    a.crank = mesh->d_cell_rank;
+    a.n_steps = mops_traj_num_steps(cfg);
+    MOPS_TRY(alpha_table(mesh, a.n_steps, &a.alpha_tab));  // the table the trajectory launches read (or the division)
+    a.px = p->d_x; a.py = p->d_y; a.pz = p->d_z; a.depth = p->d_depth; a.cell = p->d_cell; a.death = p->d_death_step;
+    a.n = p->n;
+    a.step_begin = step; a.step_end = step + 1;
+    a.delta_t = ((cfg->direction == MOPS_FORWARD) ? 1 : -1) * (int)cfg->delta_t;
+    a.dalpha = (double)a.delta_t / (double)cfg->simulation_duration;
+    sa.vold = mesh->d_vold;
+    sa.n_attr = n_attr;
+    for (int k = 0; k < n_attr; ++k) { sa.af[k] = d_fa[k]; sa.ab[k] = d_ba[k]; }
+    sa.out = d_slab + slot * n_attr * attr_stride;
+    sa.stride = attr_stride;
+    const bool euler = (cfg->method == MOPS_EULER);
+    const unsigned g = (unsigned)((p->n + 255) / 256);
+    switch (mesh->maxv) {
+        case 7:
+            if (euler) traj_sample_attrs_kernel<7, true><<<g, 256, 0, s>>>(sa);
+            else traj_sample_attrs_kernel<7, false><<<g, 256, 0, s>>>(sa);
+            break;
+#if !defined(MOPS_ONLY7)
+        case 12:
+            if (euler) traj_sample_attrs_kernel<12, true><<<g, 256, 0, s>>>(sa);
+            else traj_sample_attrs_kernel<12, false><<<g, 256, 0, s>>>(sa);
+            break;
+        default:
+            if (euler) traj_sample_attrs_kernel<20, true><<<g, 256, 0, s>>>(sa);
+            else traj_sample_attrs_kernel<20, false><<<g, 256, 0, s>>>(sa);
+            break;
+#else
+        default: return fail(MOPS_ERR_UNSUPPORTED, "experiment build: MAXV 7 only");
+#endif
+    }
+    HIP_TRY(hipGetLastError());
+    return MOPS_OK;
+}
+
+mops_status mops_traj_sample_attrs(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                   const mops_traj_cfg* cfg, const mops_particles* p, int64_t step, int32_t n_attr,
+                                   const double* const* d_front_attrs, const double* const* d_back_attrs,
+                                   double* d_attr_records, int64_t attr_stride, void* stream) {
+    MOPS_TRY(sample_check("mops_traj_sample_attrs", mesh, front, back, cfg, p, n_attr, d_front_attrs, d_back_attrs,
+                          d_attr_records, attr_stride));
+    const int64_t K = mops_traj_num_records(cfg), n_steps = mops_traj_num_steps(cfg);
+    const int64_t slot = sample_slot(step, cfg->record_t / cfg->delta_t, K, n_steps);
+    if (slot < 0)
+        return fail(MOPS_ERR_INVALID, "mops_traj_sample_attrs: step " + std::to_string(step) + " is not a sample step");
+    return sample_launch(mesh, front, back, cfg, p, step, slot, n_attr, d_front_attrs, d_back_attrs, d_attr_records,
+                         attr_stride, (hipStream_t)stream);
+}
+
+mops_status mops_traj_advance_sampled(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                      const mops_traj_cfg* cfg, const mops_particles* p, int64_t step_begin,
+                                      int64_t step_end, double* d_records, int64_t record_stride, int32_t n_attr,
+                                      const double* const* d_front_attrs, const double* const* d_back_attrs,
+                                      double* d_attr_records, int64_t attr_stride, void* stream) {
+    MOPS_TRY(sample_check("mops_traj_advance_sampled", mesh, front, back, cfg, p, n_attr, d_front_attrs, d_back_attrs,
+                          d_attr_records, attr_stride));
+    if (record_stride < p->n) return fail(MOPS_ERR_INVALID, "record_stride < n");
+    if (p->n == 0) return MOPS_OK;
+    if (!d_records) return fail(MOPS_ERR_INVALID, "mops_traj_advance_sampled: null device pointer");
+    const int64_t K = mops_traj_num_records(cfg), n_steps = mops_traj_num_steps(cfg), ri = cfg->record_t / cfg->delta_t;
+    const int64_t sb = std::max<int64_t>(step_begin, 0), se = std::min<int64_t>(step_end, n_steps);
+    if (sb >= se) return MOPS_OK;
+    int64_t cur = sb;  // the step the particles stand at
+    auto sample_at = [&](int64_t j) -> mops_status {
+        if (cur < j) MOPS_TRY(mops_traj_advance(mesh, front, back, cfg, p, cur, j, d_records, record_stride, stream));
+        cur = j;
+        return sample_launch(mesh, front, back, cfg, p, j, sample_slot(j, ri, K, n_steps), n_attr, d_front_attrs,
+                             d_back_attrs, d_attr_records, attr_stride, (hipStream_t)stream);
+    };
+    if (sb == 0) MOPS_TRY(sample_at(0));
+    if (ri > 0) {
+        for (int64_t m = std::max<int64_t>(1, (sb + ri) / ri); m <= K; ++m) {  // record m - 1 at step m ri - 1 >= sb
+            const int64_t j = m * ri - 1;
+            if (j >= se) break;
+            if (j > 0) MOPS_TRY(sample_at(j));  // (step 0 is sampled above)
+        }
+    }
+    return mops_traj_advance(mesh, front, back, cfg, p, cur, se, d_records, record_stride, stream);
+}
+
+mops_status mops_traj_finalize_attrs(int64_t n, int64_t K, const double* d_seeds, const double* d_records,
+                                     int64_t record_stride, int32_t n_attr, const double* d_attr_records,
+                                     int64_t attr_stride, const int32_t* d_line, double* d_attr_lines, void* stream) {
+    if (n < 0 || K <= 0 || K >= INT32_MAX || !d_seeds || !d_records || !d_attr_records || !d_attr_lines ||
+        record_stride < n || attr_stride < n || n_attr < 1 || n_attr > MOPS_MAX_SAMPLE_ATTRS)
+        return fail(MOPS_ERR_INVALID, "mops_traj_finalize_attrs: invalid argument");
+    if (n == 0) return MOPS_OK;
+    const unsigned nb = (unsigned)((n + kAttrAsmSlots - 1) / kAttrAsmSlots);
+    assemble_attrs_kernel<<<nb, 256, 0, (hipStream_t)stream>>>(n, (int)K, d_seeds, d_records, record_stride, n_attr,
+                                                              d_attr_records, attr_stride, d_line, d_attr_lines);
+    HIP_TRY(hipGetLastError());
+    return MOPS_OK;
+}
+
 // error hook for the host writers in mops_io.cpp (not part of the public ABI)
 __attribute__((visibility("hidden"))) mops_status mops_io_fail(mops_status st, const char* msg) {
     return fail(st, msg ? msg : "");
@@ -4450,12 +4801,24 @@ mops_status mops_remove_nan_ragged(int64_t n, const int64_t* d_offsets, double* 
 
 const char* mops_build_id(void) { return MOPS_BUILD_ID; }
 
-mops_status mops_run_trajectories(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
-                                  const mops_traj_cfg* cfg, int64_t n, const double* h_seeds, const float* h_depths,
-                                  float depth, int32_t* h_cells, double* h_points, double* h_vel, double* h_tmp,
-                                  double* h_sal, double* h_last, double* h_final_pos, float* h_final_depth,
-                                  int32_t* h_death, void* stream) {
+// mops_run_trajectories and mops_run_pathline_attrs: n_attr == 0 is the former, to the launch; n_attr > 0 adds the
+// attribute slab, the sampled advance and the attribute lines
+static mops_status run_trajectories_impl(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                         const mops_traj_cfg* cfg, int64_t n, const double* h_seeds,
+                                         const float* h_depths, float depth, int32_t* h_cells, double* h_points,
+                                         double* h_vel, double* h_tmp, double* h_sal, double* h_last,
+                                         double* h_final_pos, float* h_final_depth, int32_t* h_death, int32_t n_attr,
+                                         const double* const* d_fa, const double* const* d_ba, double* h_attr_lines,
+                                         void* stream) {
     if (!mesh || !front || !cfg) return fail(MOPS_ERR_INVALID, "invalid inputs");  // :659-662
+    if (n_attr != 0) {
+        if (!back) return fail(MOPS_ERR_UNSUPPORTED, "mops_run_pathline_attrs: attributes are sampled along pathlines only (back == NULL)");
+        if (n_attr < 1 || n_attr > MOPS_MAX_SAMPLE_ATTRS || !d_fa || !d_ba || !h_attr_lines)
+            return fail(MOPS_ERR_INVALID, "mops_run_pathline_attrs: n_attr must be 1.." +
+                                              std::to_string(MOPS_MAX_SAMPLE_ATTRS) + " with its arrays and output");
+        for (int a = 0; a < n_attr; ++a)
+            if (!d_fa[a] || !d_ba[a]) return fail(MOPS_ERR_INVALID, "mops_run_pathline_attrs: null attribute array");
+    }
     if (n <= 0) return MOPS_OK;                                                      // :663-665 (empty)
     if (!h_seeds || !h_points) return fail(MOPS_ERR_INVALID, "mops_run_trajectories: null host buffer");
     if (cfg->delta_t <= 0 || cfg->record_t <= 0 || cfg->simulation_duration <= 0)
@@ -4467,6 +4830,7 @@ mops_status mops_run_trajectories(const mops_mesh* mesh, const mops_field* front
     // SoA state + record slab, one allocation
     double *seeds = nullptr, *x = nullptr, *y = nullptr, *z = nullptr, *rec = nullptr;
     double *pts = nullptr, *vel = nullptr, *tmp = nullptr, *sal = nullptr, *last = nullptr;
+    double *slab = nullptr, *alines = nullptr;  // n_attr > 0: [K][n_attr][n] and [n_attr][n * P]
     float* dep = nullptr;
     int *cells = nullptr, *death = nullptr, *order = nullptr;
     mops_status st = MOPS_OK;
@@ -4479,7 +4843,7 @@ mops_status mops_run_trajectories(const mops_mesh* mesh, const mops_field* front
     auto cleanup = [&]() {
         (void)hipFree(seeds); (void)hipFree(x); (void)hipFree(y); (void)hipFree(z); (void)hipFree(rec); (void)hipFree(pts); (void)hipFree(vel);
         (void)hipFree(tmp); (void)hipFree(sal); (void)hipFree(last); (void)hipFree(dep); (void)hipFree(cells); (void)hipFree(death);
-        (void)hipFree(order);
+        (void)hipFree(order); (void)hipFree(slab); (void)hipFree(alines);
     };
     do {
         if ((st = upload(h_seeds, (size_t)(3 * n), &seeds, nullptr, s)) != MOPS_OK) break;
@@ -4524,7 +4888,21 @@ mops_status mops_run_trajectories(const mops_mesh* mesh, const mops_field* front
         if ((st = dmalloc(&order, (size_t)n, nullptr)) != MOPS_OK) break;
         if ((st = mops_order_particles(mesh, n, cells, order, stream)) != MOPS_OK) break;
         mops_particles prt{n, x, y, z, dep, cells, death, order, nullptr};
-        if ((st = mops_traj_advance(mesh, front, back, cfg, &prt, 0, n_steps, rec, n, stream)) != MOPS_OK) break;
+        if (n_attr > 0) {
+            if ((st = dmalloc(&slab, (size_t)(K * n_attr * n), nullptr)) != MOPS_OK) break;
+            if ((st = dmalloc(&alines, (size_t)(n_attr * n * P), nullptr)) != MOPS_OK) break;
+            e = hipMemsetAsync(slab, 0, (size_t)(K * n_attr * n) * sizeof(double), s);  // update_attrs after resize
+            if (e != hipSuccess) { st = fail(MOPS_ERR_HIP, hipGetErrorString(e)); break; }
+            if ((st = mops_traj_advance_sampled(mesh, front, back, cfg, &prt, 0, n_steps, rec, n, n_attr, d_fa, d_ba, slab,
+                                                n, stream)) != MOPS_OK)
+                break;
+            if ((st = mops_traj_finalize_attrs(n, K, seeds, rec, n, n_attr, slab, n, nullptr, alines, stream)) != MOPS_OK)
+                break;
+            e = hipMemcpyAsync(h_attr_lines, alines, (size_t)(n_attr * n * P) * sizeof(double), hipMemcpyDeviceToHost, s);
+            if (e != hipSuccess) { st = fail(MOPS_ERR_HIP, hipGetErrorString(e)); break; }
+        } else if ((st = mops_traj_advance(mesh, front, back, cfg, &prt, 0, n_steps, rec, n, stream)) != MOPS_OK) {
+            break;
+        }
         if ((st = mops_traj_finalize(n, K, seeds, rec, n, back ? 1 : 0, nullptr, pts, vel, tmp, sal, last, stream)) !=
             MOPS_OK)
             break;
@@ -4549,6 +4927,28 @@ mops_status mops_run_trajectories(const mops_mesh* mesh, const mops_field* front
     } while (0);
     cleanup();
     return st;
+}
+
+mops_status mops_run_trajectories(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                  const mops_traj_cfg* cfg, int64_t n, const double* h_seeds, const float* h_depths,
+                                  float depth, int32_t* h_cells, double* h_points, double* h_vel, double* h_tmp,
+                                  double* h_sal, double* h_last, double* h_final_pos, float* h_final_depth,
+                                  int32_t* h_death, void* stream) {
+    return run_trajectories_impl(mesh, front, back, cfg, n, h_seeds, h_depths, depth, h_cells, h_points, h_vel, h_tmp,
+                                 h_sal, h_last, h_final_pos, h_final_depth, h_death, 0, nullptr, nullptr, nullptr, stream);
+}
+
+mops_status mops_run_pathline_attrs(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                    const mops_traj_cfg* cfg, int64_t n, const double* h_seeds, const float* h_depths,
+                                    float depth, int32_t* h_cells, double* h_points, double* h_vel, double* h_tmp,
+                                    double* h_sal, double* h_last, double* h_final_pos, float* h_final_depth,
+                                    int32_t* h_death, int32_t n_attr, const double* const* d_front_attrs,
+                                    const double* const* d_back_attrs, double* h_attr_lines, void* stream) {
+    if (n_attr == 0) return fail(MOPS_ERR_INVALID, "mops_run_pathline_attrs: n_attr must be 1.." +
+                                                       std::to_string(MOPS_MAX_SAMPLE_ATTRS));
+    return run_trajectories_impl(mesh, front, back, cfg, n, h_seeds, h_depths, depth, h_cells, h_points, h_vel, h_tmp,
+                                 h_sal, h_last, h_final_pos, h_final_depth, h_death, n_attr, d_front_attrs, d_back_attrs,
+                                 h_attr_lines, stream);
 }
 
 }  // extern "C"

@@ -217,12 +217,19 @@ class DeviceField:
 
 def run_trajectories(mesh: DeviceMesh, front: DeviceField, back: DeviceField | None, cfg: TrajectoryConfig,
                      seeds: np.ndarray, depths: np.ndarray | None = None, cells: np.ndarray | None = None,
-                     stream=None):
+                     stream=None, attrs=None):
     """Host-in/host-out StreamLine (back None) or PathLine (mops_run_trajectories).
 
     Returns a dict of numpy arrays shaped like the reference's finalized
     lines: points/velocity [N, K+1, 3], temperature/salinity [N, K+1],
     lastPoint [N, 3], plus final_pos, final_depth, death_step, cells.
+
+    ``attrs`` (pathlines only, mops_run_pathline_attrs): a mapping name -> (front_vertex_tensor,
+    back_vertex_tensor), at most 4 entries in the order given, each a [nVertices, nVertLevels] float64 CUDA
+    tensor as ``cell_to_vertex_attr`` makes it.  The attributes are sampled along every pathline
+    (Kernel::PathLine's current_attrs) and returned as ``attributes[name]`` [N, K+1]; ``temperature`` /
+    ``salinity`` then hold the attributes of those NAMES (zeros where that name is not sampled) instead of
+    the velocity x / y of quirk Q9.  None: the outputs above, unchanged.
     """
     lib = L.load()
     seeds = np.ascontiguousarray(seeds, dtype=np.float64).reshape(-1, 3)
@@ -235,6 +242,22 @@ def run_trajectories(mesh: DeviceMesh, front: DeviceField, back: DeviceField | N
     dep = None if depths is None else np.ascontiguousarray(depths, dtype=np.float32)
     cl = np.full(n, -1, dtype=np.int32) if cells is None else np.ascontiguousarray(cells, dtype=np.int32).copy()
     c = cfg.ctype()
+    if attrs is not None:
+        names = list(attrs)
+        fa, ba = _attr_ptr_lists(mesh, [attrs[k][0] for k in names], [attrs[k][1] for k in names])
+        lines = np.zeros((len(names), n, P))
+        st = lib.mops_run_pathline_attrs(mesh.handle, front.handle, None if back is None else back.handle,
+                                         C.byref(c), n, _ptr(seeds), _ptr(dep), C.c_float(cfg.depth), _ptr(cl),
+                                         _ptr(out["points"]), _ptr(out["velocity"]), _ptr(out["temperature"]),
+                                         _ptr(out["salinity"]), _ptr(out["lastPoint"]), _ptr(out["final_pos"]),
+                                         _ptr(out["final_depth"]), _ptr(out["death_step"]), len(names), fa, ba,
+                                         _ptr(lines), _stream_handle(stream))
+        L.check(st, "mops_run_pathline_attrs")
+        out["attributes"] = {k: lines[i] for i, k in enumerate(names)}
+        for k in ("temperature", "salinity"):  # by name, never by position (map order puts salinity first)
+            out[k] = out["attributes"][k].copy() if k in out["attributes"] else np.zeros((n, P))
+        out["cells"] = cl
+        return out
     st = lib.mops_run_trajectories(mesh.handle, front.handle, None if back is None else back.handle, C.byref(c), n,
                                    _ptr(seeds), _ptr(dep), C.c_float(cfg.depth), _ptr(cl), _ptr(out["points"]),
                                    _ptr(out["velocity"]), _ptr(out["temperature"]), _ptr(out["salinity"]),
@@ -245,6 +268,21 @@ def run_trajectories(mesh: DeviceMesh, front: DeviceField, back: DeviceField | N
     return out
 
 
+MAX_SAMPLE_ATTRS = 4  # MOPS_MAX_SAMPLE_ATTRS
+
+
+def _attr_ptr_lists(mesh: DeviceMesh, front_list, back_list):
+    """Two ctypes arrays of device pointers for the sampling entries' d_front_attrs / d_back_attrs."""
+    na = len(front_list)
+    if len(back_list) != na or not 1 <= na <= MAX_SAMPLE_ATTRS:
+        raise ValueError(f"1..{MAX_SAMPLE_ATTRS} attributes, each with a front and a back vertex array")
+    fa = (C.c_void_p * na)(*[_vertex_attr_ptr(mesh, t, f"front attribute {i}").value
+                             for i, t in enumerate(front_list)])
+    ba = (C.c_void_p * na)(*[_vertex_attr_ptr(mesh, t, f"back attribute {i}").value
+                             for i, t in enumerate(back_list)])
+    return fa, ba
+
+
 class ParticleSet:
     """Device-resident SoA particle state + [K][6][n] record slab (torch tensors).
 
@@ -253,10 +291,11 @@ class ParticleSet:
     """
 
     def __init__(self, mesh: DeviceMesh, seeds_xyz, depth: float | np.ndarray, cfg: TrajectoryConfig, device=None,
-                 cells=None, use_order: bool = True, record_stride: int | None = None):
+                 cells=None, use_order: bool = True, record_stride: int | None = None, n_attr: int = 0):
         """``record_stride``: columns of the [K][6][stride] record slab (default n); a multi-GPU
         shard pads it to the largest shard so every rank's slab has one shape
-        (distributed.RecordGather)."""
+        (distributed.RecordGather).  ``n_attr`` (pathlines, at most 4): also keep a zero-filled
+        [K][n_attr][stride] attribute slab, which ``advance(..., attrs=...)`` samples into."""
         import torch
         self.use_order = use_order
         self.torch = torch
@@ -286,6 +325,11 @@ class ParticleSet:
         if self.rec_stride < self.n:
             raise ValueError("record_stride below the particle count")
         self.records = torch.zeros((max(self.K, 1), 6, self.rec_stride), dtype=torch.float64, device=dev)
+        self.n_attr = int(n_attr)
+        if not 0 <= self.n_attr <= MAX_SAMPLE_ATTRS:
+            raise ValueError(f"n_attr must be 0..{MAX_SAMPLE_ATTRS}")
+        self.attr_records = None if self.n_attr == 0 else torch.zeros(
+            (max(self.K, 1), self.n_attr, self.rec_stride), dtype=torch.float64, device=dev)
         self.order = torch.empty((self.n,), dtype=torch.int32, device=dev)
         # slot -> particle index: with use_order the state is kept PHYSICALLY in
         # locality order (state loads/stores and record stores coalesce);
@@ -328,6 +372,8 @@ class ParticleSet:
         else:
             s = stream if stream is not None else torch.cuda.current_stream(self.seeds.device)
         names = [(k, e) for k, e in self._STATE] + ([("records", 8)] if record_slots > 0 else [])
+        if record_slots > 0 and self.attr_records is not None:
+            names.append(("attr_records", 8))  # (attribute slot k is written at the steps that write record slot k)
         with torch.cuda.stream(s):
             for k, _ in names:
                 if k not in self._spare:  # (allocated on first use, then kept)
@@ -337,6 +383,9 @@ class ParticleSet:
             if name == "records":
                 return L.PermArray(src.data_ptr() + 8 * lo, dst.data_ptr() + 8 * lo, 8, int(record_slots) * 6,
                                    self.rec_stride)
+            if name == "attr_records":
+                return L.PermArray(src.data_ptr() + 8 * lo, dst.data_ptr() + 8 * lo, 8,
+                                   int(record_slots) * self.n_attr, self.rec_stride)
             return L.PermArray(src.data_ptr() + eb * lo, dst.data_ptr() + eb * lo, eb, 1, n)
 
         lib = L.load()
@@ -369,6 +418,8 @@ class ParticleSet:
         writes each slot's line at its id).  Re-entrant across disjoint ranges on different
         streams (each range has its own scratch)."""
         torch = self.torch
+        if self.attr_records is not None:
+            raise ValueError("compact: not supported for a particle set with an attribute slab")
         n = hi - lo
         if n <= 1:
             return
@@ -422,6 +473,8 @@ class ParticleSet:
             self.depth.fill_(float(depth))
         self.death.fill_(-1)
         self._written = False  # (records: every slot is rewritten by the launches from step 0)
+        if self.attr_records is not None:
+            self.attr_records.zero_()  # (a particle that never reaches a slot leaves its zero there)
 
     def reseed(self, seeds, depth, stream=None, hint_cells: bool = False):
         """Start a new run from device-resident seeds [n,3] (f64) and depth (scalar
@@ -445,6 +498,8 @@ class ParticleSet:
             self.depth.fill_(float(np.float32(depth)))
         self.death.fill_(-1)
         self._written = False
+        if self.attr_records is not None:
+            self.attr_records.zero_()
         self.mesh.locate(self.seeds.data_ptr(), self.cell.data_ptr(), self.n, stream=h,
                          d_hint=None if hint is None else hint.data_ptr())
         self.reorder(stream=h)
@@ -454,10 +509,24 @@ class ParticleSet:
                            self.cell.data_ptr(), self.death.data_ptr(), None, None)  # physically ordered
 
     def advance(self, front: DeviceField, back: DeviceField | None, step_begin: int, step_end: int, stream=None,
-                live_count=None):
+                live_count=None, attrs=None):
         """Launch steps [step_begin, step_end) over every slot; ``live_count``: the device live count
-        compact(0, n) returned (only the leading live slots are spread over the XCDs)."""
+        compact(0, n) returned (only the leading live slots are spread over the XCDs).  ``attrs``: a pair
+        (front_list, back_list) of n_attr vertex attribute tensors each (``cell_to_vertex_attr``) -- the
+        range's sample steps are sampled into the attribute slab (mops_traj_advance_sampled); positions,
+        records, depths and death steps are those of the plain call."""
         p = self.particles() if live_count is None else self._sub_particles(0, self.n, live_count)
+        if attrs is not None:
+            if self.attr_records is None or len(attrs[0]) != self.n_attr:
+                raise ValueError("advance: attrs needs a particle set created with n_attr = the number of attributes")
+            fa, ba = _attr_ptr_lists(self.mesh, list(attrs[0]), list(attrs[1]))
+            st = L.load().mops_traj_advance_sampled(
+                self.mesh.handle, front.handle, None if back is None else back.handle, C.byref(self._c), C.byref(p),
+                int(step_begin), int(step_end), C.c_void_p(self.records.data_ptr()), self.rec_stride, self.n_attr, fa,
+                ba, C.c_void_p(self.attr_records.data_ptr()), self.rec_stride, _stream_handle(stream))
+            L.check(st, "mops_traj_advance_sampled")
+            self._written = True
+            return
         st = L.load().mops_traj_advance(self.mesh.handle, front.handle, None if back is None else back.handle,
                                         C.byref(self._c), C.byref(p), int(step_begin), int(step_end),
                                         C.c_void_p(self.records.data_ptr()), self.rec_stride, _stream_handle(stream))
@@ -490,6 +559,8 @@ class ParticleSet:
         (quirk Q1, half of them in a day at config 2), and a wave keeps its slots until its
         last live lane finishes."""
         torch = self.torch
+        if self.attr_records is not None:
+            raise ValueError("advance_pipelined: not supported for a particle set with an attribute slab")
         nparts = max(1, len(streams))
         pb = self.part_bounds(nparts)
         span = int(step_end) - int(step_begin)
@@ -557,9 +628,20 @@ class ParticleSet:
                                                _stream_handle(stream)), "mops_traj_last_points")
         return last
 
-    def finalize_from(self, seeds, ids, records, pathline: bool, stream=None):
+    def _attr_lines(self, n, seeds_ptr, records_ptr, attr_ptr, ids_ptr, stream):
+        """The attribute lines [n_attr, n, K + 1] of n slots (mops_traj_finalize_attrs)."""
+        out = self.torch.empty((self.n_attr, n, self.K + 1), dtype=self.torch.float64, device=self.seeds.device)
+        L.check(L.load().mops_traj_finalize_attrs(n, self.K, C.c_void_p(seeds_ptr), C.c_void_p(records_ptr),
+                                                  self.rec_stride, self.n_attr, C.c_void_p(attr_ptr), self.rec_stride,
+                                                  None if ids_ptr is None else C.c_void_p(ids_ptr),
+                                                  C.c_void_p(out.data_ptr()), _stream_handle(stream)),
+                "mops_traj_finalize_attrs")
+        return out
+
+    def finalize_from(self, seeds, ids, records, pathline: bool, stream=None, attr_records=None):
         """finalize over another set's seeds, slot ids and record slab (a chain's deferred assembly: the
-        buffers of a finished pair while this set runs the next)."""
+        buffers of a finished pair while this set runs the next); with that set's attribute slab
+        (``attr_records``) also ``attributes`` [n_attr, n, K + 1]."""
         torch = self.torch
         dev = self.seeds.device
         P = self.K + 1
@@ -572,15 +654,23 @@ class ParticleSet:
                                             C.c_void_p(pts.data_ptr()), C.c_void_p(vel.data_ptr()),
                                             C.c_void_p(tmp.data_ptr()), C.c_void_p(sal.data_ptr()), None,
                                             _stream_handle(stream)), "mops_traj_finalize")
-        return dict(points=pts, velocity=vel, temperature=tmp, salinity=sal)
+        out = dict(points=pts, velocity=vel, temperature=tmp, salinity=sal)
+        if attr_records is not None:
+            out["attributes"] = self._attr_lines(self.n, seeds.data_ptr(), records.data_ptr(), attr_records.data_ptr(),
+                                                 ids.data_ptr(), stream)
+        return out
 
     def finalize_range(self, lo: int, hi: int, out: dict, pathline: bool, stream=None):
         """The lines of slots [lo, hi) into ``out`` (device tensors points [m, P, 3], velocity [m, P, 3],
         temperature / salinity [m, P], m = hi - lo) in slot order -- row i is particle ids[lo + i] -- a
-        bounded piece of finalize (PathlineChain's writer hook)."""
+        bounded piece of finalize (PathlineChain's writer hook).  A set with an attribute slab also stores
+        ``out["attributes"]`` [n_attr, m, P]."""
         m = hi - lo
         if m <= 0:
             return out
+        if self.attr_records is not None:
+            out["attributes"] = self._attr_lines(m, self.seeds.data_ptr() + 24 * lo, self.records.data_ptr() + 8 * lo,
+                                                 self.attr_records.data_ptr() + 8 * lo, None, stream)
         L.check(L.load().mops_traj_finalize(m, self.K, C.c_void_p(self.seeds.data_ptr() + 24 * lo),
                                             C.c_void_p(self.records.data_ptr() + 8 * lo), self.rec_stride,
                                             1 if pathline else 0, None, C.c_void_p(out["points"].data_ptr()),
@@ -594,8 +684,12 @@ class ParticleSet:
         """Lines of every particle in seed order (mops_traj_finalize).  ``streams``: the
         advance_pipelined part streams -- each part's lines are assembled on its own stream right
         after its last chunk, so one part's assembly overlaps the other parts' final waves (the
-        caller joins the streams afterwards); ``timing`` receives (start, end) events per launch."""
+        caller joins the streams afterwards); ``timing`` receives (start, end) events per launch.  A set with
+        an attribute slab also returns ``attributes`` [n_attr, n, K + 1] (mops_traj_finalize_attrs; one
+        stream only)."""
         torch = self.torch
+        if streams and self.attr_records is not None:
+            raise ValueError("finalize: part streams are not supported for a particle set with an attribute slab")
         dev = self.seeds.device
         P = self.K + 1
         pts = torch.empty((self.n, P, 3), dtype=torch.float64, device=dev)
@@ -632,7 +726,11 @@ class ParticleSet:
             if timing is not None:
                 e1.record(ts)
                 timing.append((e0, e1))
-        return dict(points=pts, velocity=vel, temperature=tmp, salinity=sal, lastPoint=last)
+        out = dict(points=pts, velocity=vel, temperature=tmp, salinity=sal, lastPoint=last)
+        if self.attr_records is not None:
+            out["attributes"] = self._attr_lines(self.n, self.seeds.data_ptr(), self.records.data_ptr(),
+                                                 self.attr_records.data_ptr(), self.ids.data_ptr(), stream)
+        return out
 
 
 LAYER_RULES = {"reference": L.MOPS_LAYER_REFERENCE, "bracket": L.MOPS_LAYER_BRACKET}

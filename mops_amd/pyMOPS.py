@@ -220,7 +220,8 @@ class MPASOSolution:
 
     def add_attribute(self, name: str, arr=None):
         """Explicit array, or (pyMOPSAPI: ``add_attribute("temperature", AttributeFormat.kFloat)``) a name the
-        reader already loaded; attributes are unobservable in trajectory outputs (Q9)."""
+        reader already loaded.  Trajectory outputs carry attributes only where
+        ``TrajectorySettings.sampleAttributes`` asks for them (default: the reference's output, quirk Q9)."""
         if arr is not None and not isinstance(arr, (int, enum.Enum)):
             self.mDoubleAttributes[name] = np.ascontiguousarray(arr, dtype=np.float64).reshape(-1)
 
@@ -272,6 +273,9 @@ class TrajectorySettings:
         self.fileName = ""
         self.directionType = CalcDirection.kForward
         self.methodType = CalcMethodType.kEuler
+        # this engine's extension: MOPS_RunPathLine samples the first two attribute names, in sorted order, that
+        # both active solutions carry, and returns them as temperature / salinity BY NAME (see MOPS_RunPathLine)
+        self.sampleAttributes = False
 
     def hasPerParticleDepths(self) -> bool:
         return len(self.particle_depths) > 0
@@ -392,7 +396,8 @@ class _App:
         self.front = None
         self.back = None
         self.front_id = None
-        self.vertex_attrs = {}  # solID -> the first two attributes' vertex arrays (device), built on first use
+        self.back_id = None
+        self.vertex_attrs = {}  # solID -> {name: the attribute's vertex array (device)}, built on first use
 
 
 _app = _App()
@@ -473,6 +478,7 @@ def MOPS_ActiveAttribute(t1: int, t2: int | None = None):
     _app.front = _app.fields[t1]
     _app.front_id = t1
     _app.back = None if t2 is None else _app.fields[t2]
+    _app.back_id = t2
 
 
 def MOPS_GenerateSeedsPoints(setting: SeedsSettings) -> np.ndarray:
@@ -520,7 +526,18 @@ def _run(config: TrajectorySettings, sample_points_np, pathline: bool, stage: st
     if cfg.n_records <= 0 or cfg.n_steps <= 0:
         _error(f"[{stage}] invalid integration steps")  # seed-only lines (:709-712)
         return "seed_only", seeds, eff
-    r = _E.run_trajectories(_app.mesh, _app.front, _app.back if pathline else None, cfg, seeds, depths=depths)
+    attrs = None
+    if pathline and getattr(config, "sampleAttributes", False):
+        # the first two names, sorted (std::map order), that both solutions carry; one is enough (the
+        # reference's size() > 1 gate, MPASOVisualizerKernels.cpp:1093, is not kept)
+        fs, bs = _app.sols.get(_app.front_id), _app.sols.get(_app.back_id)
+        names = sorted(set(fs.mDoubleAttributes) & set(bs.mDoubleAttributes))[:2] if fs and bs else []
+        attrs = {k: (_vertex_attr(_app.front_id, k), _vertex_attr(_app.back_id, k)) for k in names}
+    r = _E.run_trajectories(_app.mesh, _app.front, _app.back if pathline else None, cfg, seeds, depths=depths,
+                            attrs=attrs or None)
+    if attrs is not None and not attrs:  # the flag is set and no name is shared: nothing sampled, zeros
+        r["temperature"] = np.zeros_like(r["temperature"])
+        r["salinity"] = np.zeros_like(r["salinity"])
     return r, seeds, eff
 
 
@@ -552,18 +569,23 @@ def MOPS_RunPathLine(config: TrajectorySettings, sample_points_np):
                  "depth": float(eff[i])} for i in range(len(seeds))]
 
 
+def _vertex_attr(sol_id, name: str):
+    """One attribute of one solution as a vertex array on the device (CalcCellCenterToVertex,
+    MOPSApp.cpp:121-127: mDoubleAttributes_CtoV), built once per solution id and name."""
+    cache = _app.vertex_attrs.setdefault(sol_id, {})
+    if name not in cache:
+        cache[name] = _E.cell_to_vertex_attr(_app.mesh, _app.sols[sol_id].mDoubleAttributes[name])
+    return cache[name]
+
+
 def _front_vertex_attrs():
     """The active front solution's attribute count and, with two or more, the vertex arrays of the first two
-    in name order (the reference's std::map order: mDoubleAttributes_CtoV), built on the device once per
-    solution (CalcCellCenterToVertex, MOPSApp.cpp:121-127)."""
+    in name order (the reference's std::map order: mDoubleAttributes_CtoV)."""
     sol = _app.sols.get(_app.front_id)
     names = sorted(sol.mDoubleAttributes) if sol is not None else []
     if len(names) < 2:
         return len(names), ()
-    if _app.front_id not in _app.vertex_attrs:
-        _app.vertex_attrs[_app.front_id] = tuple(_E.cell_to_vertex_attr(_app.mesh, sol.mDoubleAttributes[k])
-                                                 for k in names[:2])
-    return len(names), _app.vertex_attrs[_app.front_id]
+    return len(names), tuple(_vertex_attr(_app.front_id, k) for k in names[:2])
 
 
 def MOPS_RunRemapping(config: VisualizationSettings):
