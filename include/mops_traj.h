@@ -374,6 +374,65 @@ mops_status mops_traj_advance_sampled(const mops_mesh* mesh, const mops_field* f
                                       const double* const* d_front_attrs, const double* const* d_back_attrs,
                                       double* d_attr_records, int64_t attr_stride, void* stream);
 
+/* ---- the same in one launch per window: capture, then one batched sampler ---- */
+
+/* Bytes of a capture slab of `slots` window slots for `stride` particles: per
+ * particle and slot the state a sample step starts from -- x, y, z (double),
+ * the float depth, the cell its walk starts from -- 32 B, one plane per
+ * component ([5 planes][slots][stride]).  0 for an empty slab, -1 for a
+ * negative argument or an overflow.  Host only. */
+int64_t mops_traj_capture_bytes(int64_t stride, int64_t slots);
+
+/* The launches mops_traj_advance_captured makes for steps [step_begin,
+ * step_end) (clamped to the run) with a window of W = capture_slots slots
+ * (at most 65535 are used per launch).  Host only, no device work.  Returns
+ * the number of launches and stores the end step of launch i in out_bounds[i]
+ * for i < cap (out_bounds may be NULL with cap == 0): launch i runs
+ * [out_bounds[i - 1], out_bounds[i]), the first from step_begin, the last to
+ * step_end; the ends increase strictly.  Every sample step of the range is
+ * either a launch's first step -- sampled from the particle state by
+ * mops_traj_sample_attrs' kernel, as step 0 and a range that starts on a
+ * sample step are -- or interior to exactly one launch, which holds at most W
+ * interior sample steps: each launch ends at the (W + 1)-th sample step after
+ * its first step, or at step_end.  W = 0 is mops_traj_advance_sampled's split:
+ * a launch boundary at every sample step.  -1 (and mops_last_error) for a null
+ * or invalid cfg, capture_slots < 0, cap < 0 or a NULL out_bounds with
+ * cap > 0. */
+int64_t mops_traj_capture_plan(const mops_traj_cfg* cfg, int64_t step_begin, int64_t step_end, int64_t capture_slots,
+                               int64_t* out_bounds, int64_t cap);
+
+/* mops_traj_advance_sampled without a launch boundary at every sample step.
+ * Per launch of mops_traj_capture_plan, all on `stream`: the window's cell
+ * plane is marked "not captured" (all-ones bytes, cell = -1); a sample step
+ * that is the launch's first step is sampled from the particle state; the
+ * trajectory launch -- the capture instantiation of the same kernel -- stores
+ * the step-start state of every interior sample step for every particle still
+ * alive there (a dead particle never stores); one batched kernel then
+ * evaluates every captured (slot, particle) exactly as mops_traj_sample_attrs
+ * does from the particle state and writes the attribute slots.  A particle the
+ * sample step kills writes nothing, so the slot keeps its zero.  Slot 0 is
+ * written twice as in the reference: the step-0 pre-write first, then the
+ * sample of step ri - 1, which overwrites only on success (with ri == 1 step
+ * 0 is both).  The attribute slab, the records, positions, depths, cells and
+ * death steps are those of mops_traj_advance_sampled byte for byte, for every
+ * capture_slots and step range.
+ *
+ * d_capture: mops_traj_capture_bytes(n, capture_slots) bytes of device
+ * memory for this call's n = particles->n (scratch: nothing is kept in it
+ * between calls; concurrent calls on disjoint particle ranges need disjoint
+ * slabs).  d_n_live and d_order are honoured as by mops_traj_advance.
+ * capture_slots == 0, or a mesh past maxEdges 7 (no capture instantiations),
+ * takes mops_traj_advance_sampled's path inside this entry; d_capture may then
+ * be NULL.  Argument checks as mops_traj_advance_sampled plus
+ * MOPS_ERR_INVALID for capture_slots < 0 or a NULL d_capture with
+ * capture_slots > 0, all before any device work. */
+mops_status mops_traj_advance_captured(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                       const mops_traj_cfg* cfg, const mops_particles* particles, int64_t step_begin,
+                                       int64_t step_end, double* d_records, int64_t record_stride, int32_t n_attr,
+                                       const double* const* d_front_attrs, const double* const* d_back_attrs,
+                                       double* d_attr_records, int64_t attr_stride, void* d_capture,
+                                       int64_t capture_slots, void* stream);
+
 /* The attribute lines from the slab, with the cleanup
  * RemoveNaNTrajectoriesAndReindex applies to temperature / salinity
  * (src/Common/TrajectoryCommon.h:88-121): entry j < K of a line is slot j,

@@ -23,6 +23,7 @@ EXPORTED = (
     "mops_traj_num_records", "mops_traj_num_steps", "mops_traj_advance", "mops_traj_finalize", "mops_traj_last_points",
     "mops_traj_alpha_table",
     "mops_traj_sample_attrs", "mops_traj_advance_sampled", "mops_traj_finalize_attrs", "mops_run_pathline_attrs",
+    "mops_traj_capture_bytes", "mops_traj_capture_plan", "mops_traj_advance_captured",
     "mops_remove_nan_lines", "mops_remove_nan_ragged", "mops_run_trajectories", "mops_build_id",
     "mops_remap_num_images", "mops_remap_tables", "mops_remap_fixed_depth", "mops_remap_fixed_latitude",
     "mops_remap_fixed_layer", "mops_colormap_rgba8", "mops_colormap_image",
@@ -163,6 +164,10 @@ def load(path: str | None = None):
     lib.mops_traj_sample_attrs.restype = st
     lib.mops_traj_advance_sampled.argtypes = [P, P, P, P, P, I64, I64, P, I64, I32, P, P, P, I64, P]
     lib.mops_traj_advance_sampled.restype = st
+    lib.mops_traj_capture_bytes.argtypes = [I64, I64]; lib.mops_traj_capture_bytes.restype = I64
+    lib.mops_traj_capture_plan.argtypes = [P, I64, I64, I64, P, I64]; lib.mops_traj_capture_plan.restype = I64
+    lib.mops_traj_advance_captured.argtypes = [P, P, P, P, P, I64, I64, P, I64, I32, P, P, P, I64, P, I64, P]
+    lib.mops_traj_advance_captured.restype = st
     lib.mops_traj_finalize_attrs.argtypes = [I64, I64, P, P, I64, I32, P, I64, P, P, P]
     lib.mops_traj_finalize_attrs.restype = st
     lib.mops_run_pathline_attrs.argtypes = [P, P, P, P, I64, P, P, C.c_float, P, P, P, P, P, P, P, P, P, I32, P, P, P,

@@ -31,10 +31,13 @@ from datetime import datetime
 import numpy as np
 
 from . import _lib as L
-from .engine import DeviceField, DeviceMesh, ParticleSet, TrajectoryConfig
+from .engine import MAX_SAMPLE_ATTRS, DeviceField, DeviceMesh, ParticleSet, TrajectoryConfig, cell_to_vertex_attr
 
 EARTH_RADIUS_M = 6_371_000.0  # pyMOPSAPI.py:46
 REORDER_SECONDS = 3 * 86400  # default launch length of long pairs (simulated time), see PathlineChain.run
+# run(attrs=True, capture_slots=None): True = the capture path with one window per pair (the longest pair's record
+# count), False = a launch boundary at every sample step (the measurement decides)
+DEFAULT_CAPTURE = True
 XTIME_FORMAT = "%Y-%m-%d_%H:%M:%S"  # MPAS xtime (pyMOPSAPI.py:1285; Utils.hpp:118)
 
 
@@ -92,7 +95,8 @@ def month_timestamps(pairs) -> list:
 
 class PathlineChain:
     def __init__(self, mesh: DeviceMesh, make_field, n_snapshots: int, gap_seconds=None, device=None,
-                 own_fields: bool = True, prefetch: bool = True, overlap_stream=None, timestamps=None):
+                 own_fields: bool = True, prefetch: bool = True, overlap_stream=None, timestamps=None,
+                 make_attrs=None):
         """``make_field(i, stream) -> DeviceField`` builds snapshot i's field on ``stream``.
         Pair p's simulationDuration: ``gap_seconds`` (one int for every pair, or a sequence with
         one gap per pair), or from the snapshots' ``timestamps`` (MPAS xtime strings, one per
@@ -110,7 +114,12 @@ class PathlineChain:
         field buffers): snapshot p+2 is generated and derived into the buffer
         pair p-1 released, on that stream while pair p computes -- give it CUs
         of its own (``cu_split_streams``): the trajectory waves fill every CU
-        they may use, so a stream sharing them only runs once they drain."""
+        they may use, so a stream sharing them only runs once they drain.
+        ``make_attrs(i, stream) -> {name: vertex tensor [V, L]}`` (``snapshot_attr_factory``; needed by
+        ``run(attrs=True)``) builds snapshot i's vertex attributes for the sampling (``cell_to_vertex_attr``).
+        It is called wherever snapshot i's field is built or refilled, with that stream as torch's current
+        stream, and its tensors are dropped where field i is freed or recycled: they live exactly as long as
+        the field, on the prefetch, recycle and overlap paths alike."""
         if n_snapshots < 2:
             raise ValueError("a pathline chain needs at least two snapshots")
         self.mesh = mesh
@@ -134,12 +143,14 @@ class PathlineChain:
         self.own_fields = own_fields
         self.prefetch = prefetch
         self.overlap_stream = overlap_stream
+        self.make_attrs = make_attrs
 
     def run(self, seeds, depth: float, particle_depths=None, method: int = L.MOPS_EULER, delta_t: int = 60,
             record_t: int = 360, direction: int = L.MOPS_FORWARD, follow_last: bool = True, keep_lines: bool = True,
             compute_stream=None, on_pair=None, timing=None, segment_steps: int = -1, reorder: bool = True,
             record_stride: int | None = None, defer_lines: bool = False, compact: bool | None = None,
-            compact_chunks: int = 6, on_lines=None, lines_chunk: int | None = None):
+            compact_chunks: int = 6, on_lines=None, lines_chunk: int | None = None, attrs: bool = False,
+            capture_slots: int | None = None):
         """Run all pairs; returns device tensors {points, velocity, temperature,
         salinity, lastPoint, death_step (of the last pair)} when ``keep_lines``,
         else only lastPoint/death_step.  ``on_pair(p, last, ps)`` is called after pair p
@@ -170,8 +181,26 @@ class PathlineChain:
         temperature, salinity} -- pairs after the first without their first sample, as the reference
         appends them -- with ``ids`` (int32 device tensor: the particle of each row).  The chunk buffers
         are reused: the hook consumes or copies them, on the current (compute) stream, before returning.
-        The next pair's seeds come from mops_traj_last_points.  Not with ``keep_lines`` or ``defer_lines``."""
+        The next pair's seeds come from mops_traj_last_points.  Not with ``keep_lines`` or ``defer_lines``.
+        ``attrs``: sample the snapshots' attributes along the lines (``make_attrs``; the reference's caller
+        concatenates temperature / salinity across pairs, pyMOPSAPI.py:1497-1528).  The sampled names are those
+        every snapshot carries, sorted (std::map order: salinity before temperature), at most
+        MOPS_MAX_SAMPLE_ATTRS of them (``make_attrs.names``, when set, instead of the first two snapshots'
+        common names; a later snapshot without one of them is an error).  The result gains ``attributes``
+        {name: [n, points]} and ``temperature`` / ``salinity`` hold the attributes of those names (zeros where
+        the name is not sampled, as run_trajectories); later pairs drop their first sample like the points.
+        With ``on_lines`` the hook's ``lines`` gain ``attributes`` [n_attr, rows, samples] and the named columns.
+        Works in every mode above; an ``on_pair`` that reads the records (``reads_records``) is refused with
+        it.  ``capture_slots``: the window of the capture path (ParticleSet(capture_slots=)); None = the
+        default (``DEFAULT_CAPTURE``: the longest pair's record count, one launch per existing boundary, or 0),
+        0 = a launch boundary at every sample step.  Results are the same bytes for every value.  With
+        ``attrs`` False nothing changes: no ``attributes`` key, and temperature / salinity keep quirk Q9."""
         import torch
+        if attrs and self.make_attrs is None:
+            raise ValueError("attrs=True needs a chain created with make_attrs")
+        if attrs and on_pair is not None and getattr(on_pair, "reads_records", False):
+            raise ValueError("attrs: an on_pair that reads ps.records (reads_records, the multi-GPU record gather) "
+                             "does not collect the attribute slab")
         if on_lines is not None and (keep_lines or defer_lines):
             raise ValueError("on_lines hands each pair's lines to the hook: not with keep_lines or defer_lines")
         if defer_lines and on_pair is not None and getattr(on_pair, "reads_records", False):
@@ -209,29 +238,58 @@ class PathlineChain:
             raise ValueError("overlap_stream needs a recycling make_field with a buffer pool "
                              "(synth_device.DeviceFieldRecycler)")
         fields = {}
+        attr_t = {}  # snapshot -> {name: vertex tensor}, alive exactly as long as fields[snapshot]
+        names = []
+
+        def build_attrs(i, stream):
+            """Snapshot i's vertex attributes, inside ``with torch.cuda.stream(stream)``."""
+            if not attrs:
+                return
+            t = self.make_attrs(i, stream.cuda_stream)
+            missing = [k for k in names if k not in t]
+            if missing:
+                raise ValueError(f"snapshot {i} carries no attribute {missing[0]!r}")
+            for v in t.values():
+                if stream != cs:
+                    v.record_stream(cs)  # allocated beside the compute stream, read on it
+            attr_t[i] = t
+
         with torch.cuda.stream(cs):
             fields[0] = self.make_field(0, cs.cuda_stream)
+            build_attrs(0, cs)
             fields[1] = self.make_field(1, cs.cuda_stream)
+            build_attrs(1, cs)
+            if attrs:
+                given = getattr(self.make_attrs, "names", None)
+                names.extend(sorted(given) if given else sorted(set(attr_t[0]) & set(attr_t[1])))
+                del names[MAX_SAMPLE_ATTRS:]
+                if not names or any(k not in attr_t[i] for k in names for i in (0, 1)):
+                    raise ValueError("attrs=True: the snapshots share no attribute to sample")
             if overlap and self.n_snapshots > 2 and len(self.make_field.pool) < 1:
                 raise ValueError("overlap_stream needs a third field buffer in make_field.pool (seed the "
                                  "recycler with three fields and release them before the run)")
-            ps = ParticleSet(self.mesh, seeds0, cfg.depth, cfg, device=dev, record_stride=record_stride)
+            if capture_slots is None:
+                capture_slots = cfg.n_records if DEFAULT_CAPTURE else 0
+            ps = ParticleSet(self.mesh, seeds0, cfg.depth, cfg, device=dev, record_stride=record_stride,
+                             n_attr=len(names), capture_slots=int(capture_slots) if attrs else 0)
         period = ps.record_period(pathline=True)
-        pts_acc, vel_acc, tmp_acc, sal_acc = [], [], [], []
+        pts_acc, vel_acc, tmp_acc, sal_acc, att_acc = [], [], [], [], []
         last = None
         attempted = torch.zeros((), dtype=torch.int64, device=dev)
         ov = self.overlap_stream
         ready, pair_done = {}, {}
         asm = torch.cuda.Stream(device=dev) if defer_lines else None
-        dl = dict(slab=None, seeds=None, ids=None, assembled=None)  # the deferred assembly's buffers
+        dl = dict(slab=None, aslab=None, seeds=None, ids=None, assembled=None)  # the deferred assembly's buffers
         for p in range(self.n_snapshots - 1):
             if overlap and p + 2 < self.n_snapshots:
                 # snapshot p+2 into the buffer pair p-1 released (pair 0: the third pooled buffer)
                 buf = self.make_field.pool.pop() if p == 0 else fields.pop(p - 1)
                 if p > 0:
                     ov.wait_event(pair_done.pop(p - 1))
+                    attr_t.pop(p - 1, None)  # (freed blocks return to `ov`, which has waited for their reader)
                 with torch.cuda.stream(ov):
                     fields[p + 2] = self.make_field.refill(buf, p + 2, ov)
+                    build_attrs(p + 2, ov)
                     ready[p + 2] = torch.cuda.Event()
                     ready[p + 2].record(ov)
             if p + 1 in ready:
@@ -257,6 +315,7 @@ class PathlineChain:
                 # a continuation pair: each particle's current cell is an exact-locate hint
                 ps.reseed(s, d, stream=cs.cuda_stream, hint_cells=(p > 0 and follow_last))
                 front, back = fields[p], fields[p + 1]
+                lists = ([attr_t[p][k] for k in names], [attr_t[p + 1][k] for k in names]) if attrs else None
                 if (not overlap and recycle and p + 2 < self.n_snapshots
                         and hasattr(self.make_field, "prepare")):
                     # raw snapshot p+2 generated on a side stream beside pair p's first launch (started
@@ -282,7 +341,7 @@ class PathlineChain:
                         # live ones only.  Records written so far: slot 0's step-0 part .. the last completed
                         # record (as ParticleSet.advance_pipelined)
                         nrec = min(cfg.n_records, s0 // period + 1) if period else 1
-                        live = ps.compact(0, ps.n, cs, records_written=nrec)
+                        live = ps.compact(0, ps.n, cs, records_written=nrec, attr_slots_written=nrec if attrs else None)
                     elif reorder and s0 > 0:
                         # every record slot moves with its particle: a particle that died earlier in the
                         # pair already holds the reference's zeros in its later slots
@@ -290,10 +349,11 @@ class PathlineChain:
                     if timing is not None:  # (the launch alone: what rocprofv3 averages)
                         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
                         e0.record(cs)
-                    ps.advance(front, back, s0, s1, stream=cs.cuda_stream, live_count=live)
+                    ps.advance(front, back, s0, s1, stream=cs.cuda_stream, live_count=live, attrs=lists)
                     if timing is not None:
                         e1.record(cs)
                         timing.append((e0, e1))
+                lists = None  # (the attribute tensors live as long as their fields, not until the next pair)
                 if defer_lines:
                     last = ps.last_points(stream=cs.cuda_stream)
                     done_ev = torch.cuda.Event()
@@ -302,9 +362,12 @@ class PathlineChain:
                     if dl["slab"] is None:
                         dl.update(slab=torch.empty_like(ps.records), seeds=torch.empty_like(ps.seeds),
                                   ids=torch.empty_like(ps.ids))
+                        if attrs:  # (the next reseed zero-fills the slab it finds installed)
+                            dl["aslab"] = torch.empty_like(ps.attr_records)
                     if dl["assembled"] is not None:
                         cs.wait_event(dl["assembled"])  # the spare slab's last reader is done before it is rewritten
                     slab = ps.swap_records(dl["slab"])
+                    aslab = ps.swap_attr_records(dl["aslab"]) if attrs else None
                     with torch.cuda.stream(asm):
                         dl["seeds"].copy_(ps.seeds)
                         dl["ids"].copy_(ps.ids)
@@ -312,7 +375,10 @@ class PathlineChain:
                     copied.record(asm)
                     cs.wait_event(copied)  # the next reseed rewrites seeds and ids in place
                     with torch.cuda.stream(asm):
-                        out = ps.finalize_from(dl["seeds"], dl["ids"], slab, pathline=True, stream=asm.cuda_stream)
+                        out = ps.finalize_from(dl["seeds"], dl["ids"], slab, pathline=True, stream=asm.cuda_stream,
+                                               attr_records=aslab)
+                        if attrs:
+                            _name_columns(out, names)
                     if keep_lines:
                         # allocated on `asm`, read on `cs` by the concatenation below (after cs.wait_stream(asm)):
                         # the allocator must not hand the blocks back to `asm` while `cs` may still read them
@@ -321,18 +387,23 @@ class PathlineChain:
                     dl["assembled"] = torch.cuda.Event()
                     dl["assembled"].record(asm)
                     dl["slab"] = slab
+                    dl["aslab"] = aslab
                 elif on_lines is not None:
                     last = ps.last_points(stream=cs.cuda_stream)
-                    self._hand_lines(ps, p, on_lines, lines_chunk, cs)
+                    self._hand_lines(ps, p, on_lines, lines_chunk, cs, names if attrs else None)
                 else:
                     out = ps.finalize(pathline=True, stream=cs.cuda_stream)
                     last = out["lastPoint"].clone()
+                    if attrs:
+                        _name_columns(out, names)
                 dth = ps.death.to(torch.int64)
                 attempted += torch.where(dth < 0, torch.full_like(dth, cfg.n_steps), dth + 1).sum()
                 if keep_lines:
                     sl = slice(None) if p == 0 else slice(1, None)
                     pts_acc.append(out["points"][:, sl]); vel_acc.append(out["velocity"][:, sl])
                     tmp_acc.append(out["temperature"][:, sl]); sal_acc.append(out["salinity"][:, sl])
+                    if attrs:
+                        att_acc.append(out["attributes"][:, :, sl])
             if on_pair is not None:
                 on_pair(p, last, ps)
             if overlap:
@@ -340,24 +411,34 @@ class PathlineChain:
                 pair_done[p].record(cs)  # snapshot p's buffer is free once pair p has run
                 continue
             if recycle:  # re-derive snapshot p's buffers as snapshot p+2, stream-ordered after pair p
+                attr_t.pop(p, None)  # (allocated and read on `cs` alone)
                 if p + 2 < self.n_snapshots:
-                    fields[p + 2] = self.make_field.refill(fields.pop(p), p + 2, cs)
+                    with torch.cuda.stream(cs):
+                        fields[p + 2] = self.make_field.refill(fields.pop(p), p + 2, cs)
+                        build_attrs(p + 2, cs)
                 continue
             # overlap: build the field pair p+1 will need while pair p computes
             if p + 2 < self.n_snapshots and (self.prefetch or not self.own_fields):
                 if self.own_fields:
                     with torch.cuda.stream(side):
                         fields[p + 2] = self.make_field(p + 2, side.cuda_stream)
+                        build_attrs(p + 2, side)
                     cs.wait_stream(side)
                 else:
-                    fields[p + 2] = self.make_field(p + 2, cs.cuda_stream)
+                    with torch.cuda.stream(cs):
+                        fields[p + 2] = self.make_field(p + 2, cs.cuda_stream)
+                        build_attrs(p + 2, cs)
             done = fields.pop(p)
             if self.own_fields:
                 cs.synchronize()  # pair p finished with `done` before it is freed
                 done.close()
+                attr_t.pop(p, None)
                 if p + 2 < self.n_snapshots and not self.prefetch:
                     with torch.cuda.stream(cs):
                         fields[p + 2] = self.make_field(p + 2, cs.cuda_stream)
+                        build_attrs(p + 2, cs)
+            else:
+                attr_t.pop(p, None)  # (made and read on `cs`)
         if self.own_fields:
             cs.synchronize()
             if ov is not None:
@@ -374,14 +455,18 @@ class PathlineChain:
             if keep_lines:
                 res.update(points=torch.cat(pts_acc, 1), velocity=torch.cat(vel_acc, 1),
                            temperature=torch.cat(tmp_acc, 1), salinity=torch.cat(sal_acc, 1))
+                if attrs:
+                    att = torch.cat(att_acc, 2)
+                    res["attributes"] = {k: att[a] for a, k in enumerate(names)}
         if cs != torch.cuda.current_stream(dev):
             torch.cuda.current_stream(dev).wait_stream(cs)  # results are read on the caller's stream
         return res
 
 
     @staticmethod
-    def _hand_lines(ps, p: int, on_lines, lines_chunk, cs):
-        """Pair p's lines to the writer hook, assembled in chunks of particle slots (run(on_lines=...))."""
+    def _hand_lines(ps, p: int, on_lines, lines_chunk, cs, names=None):
+        """Pair p's lines to the writer hook, assembled in chunks of particle slots (run(on_lines=...));
+        ``names``: the sampled attributes -- ``attributes`` [n_attr, rows, samples] and the named columns."""
         import torch
         n = ps.n
         ch = n if not lines_chunk else max(1, min(int(lines_chunk), n))
@@ -401,7 +486,19 @@ class PathlineChain:
                 hi = min(n, lo + ch)
                 out = {k: v[:hi - lo] for k, v in bufs.items()}
                 ps.finalize_range(lo, hi, out, pathline=True, stream=cs.cuda_stream)
-                on_lines(p, {k: v[:, sl] for k, v in out.items()}, ps.ids[lo:hi])
+                if names is not None:
+                    _name_columns(out, names)
+                on_lines(p, {k: (v[:, :, sl] if k == "attributes" else v[:, sl]) for k, v in out.items()}, ps.ids[lo:hi])
+
+
+def _name_columns(out: dict, names):
+    """temperature / salinity of a pair's lines from its sampled ``attributes`` [n_attr, rows, P] by NAME: the
+    attribute of that name, zeros where it is not sampled (engine.run_trajectories' rule)."""
+    for col in ("temperature", "salinity"):
+        if col in names:
+            out[col].copy_(out["attributes"][names.index(col)])
+        else:
+            out[col].zero_()
 
 
 class HostLineSink:
@@ -474,8 +571,10 @@ class HostLineSink:
                              f"of {w} samples")
         self._row = hi
         st = self.stage[slot]
-        for k, v in lines.items():  # compute stream: device staging (the chain reuses its chunk buffers next)
-            st[k][lo:hi, :w].copy_(v)
+        # compute stream: device staging (the chain reuses its chunk buffers next); of a chain that samples
+        # attributes the two scalar buffers carry the named ones, `lines["attributes"]` is not staged
+        for k in ("points", "velocity", "temperature", "salinity"):
+            st[k][lo:hi, :w].copy_(lines[k])
         st["ids"][lo:hi].copy_(ids)
         ready = torch.cuda.Event()
         ready.record(cs)
@@ -540,6 +639,16 @@ def cu_split_streams(device, side_cus: int):
             raise RuntimeError(f"hipExtStreamCreateWithCUMask failed ({rc})")
         out.append(torch.cuda.ExternalStream(h.value, device=dev))
     return out[0], out[1]
+
+
+def snapshot_attr_factory(mesh: DeviceMesh, make_snapshot, names=None):
+    """``make_attrs`` for PathlineChain from a host ``make_snapshot(i)``: ``cell_to_vertex_attr`` of every
+    entry of ``snapshot.attributes`` (or of ``names`` only), on torch's current stream."""
+    def make(i, stream):
+        a = make_snapshot(i).attributes
+        return {k: cell_to_vertex_attr(mesh, a[k]) for k in (sorted(a) if names is None else names)}
+    make.names = None if names is None else list(names)
+    return make
 
 
 def snapshot_field_factory(mesh: DeviceMesh, make_snapshot):

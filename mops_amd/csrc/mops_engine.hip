@@ -35,6 +35,7 @@
 #include <limits>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -1611,6 +1612,33 @@ struct TrajArgs {
     double* rec;
     int64_t rec_stride;
 };
+// The CAP instantiations' argument (mops_traj_advance_captured): TrajArgs and, after its members, the capture slab --
+// planes x, y, z (double), depth (float), cell (int), each [cap_slots][cap_stride] -- and the record slot of the
+// first window slot.  A type of its own: the other instantiations keep TrajArgs as it is, so neither the offsets of
+// its members nor those of the hidden kernel arguments behind it (the grid and block sizes) move in their code
+// 
+struct TrajArgsCap : TrajArgs {
+    char* cap;
+    int64_t cap_stride;
+    int cap_first, cap_slots;
+};
+
+// The planes of a capture slab of `slots` window slots and `stride` columns (TrajArgs::cap): 32 B per particle and slot
+struct CapPlanes {
+    double *x, *y, *z;
+    float* dep;
+    int* cell;
+};
+__host__ __device__ inline CapPlanes cap_planes(char* base, int64_t stride, int64_t slots) {
+    const int64_t m = stride * slots;
+    CapPlanes c;
+    c.x = reinterpret_cast<double*>(base);
+    c.y = c.x + m;
+    c.z = c.y + m;
+    c.dep = reinterpret_cast<float*>(c.z + m);
+    c.cell = reinterpret_cast<int*>(c.dep + m);
+    return c;
+}
 
 // One piece of a cooperative wave's tile (traj_kernel's regroup): piece pc of group gg -- the polygon, the
 // edge normals, the front field's records, the back field's -- from the group headers hdi into s_tile[i]
@@ -1725,9 +1753,18 @@ struct TrajWaves {
 // cooperative kernel, launched after it (TrajArgs::handoff), runs only such waves, from that step on: the same
 // as a launch boundary at that step for them (the walk's shortcuts, the hints and the tile are exact or speed
 // only), so records and states are the same bits as one kernel's.
-template <int MAXV, bool PATH, bool EULER, bool COOP = false, bool HAND = false>
-__global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP, HAND>::value)) traj_kernel(TrajArgs a) {
+//
+// CAP (pathline, MAXV 7; mops_traj_advance_captured): the same kernel that also stores, at the top of every sample
+// step j inside its launch (step_begin < j, j a record step), the state step j starts from -- position, float depth,
+// the cell the walk starts from -- into slot (record index - cap_first) of the capture slab, per lane at pid, for
+// traj_sample_captured_kernel to evaluate the attributes from after the launch.  Only lanes still in the loop
+// store.  A wave handed over at a sample step has stored it in the hand-off kernel already; the resumed kernel
+// starts at that step with the same state and stores the same bytes again.
+template <int MAXV, bool PATH, bool EULER, bool COOP = false, bool HAND = false, bool CAP = false>
+__global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP, HAND>::value))
+traj_kernel(std::conditional_t<CAP, TrajArgsCap, TrajArgs> a) {
     static_assert(!HAND || (MAXV == 7 && PATH && !EULER && COOP), "the hand-off kernel is the pathline RK4 tile one");
+    static_assert(!CAP || (MAXV == 7 && PATH), "capture is for the pathline MAXV 7 kernels");
     if (a.coop_sel && ((*a.coop_sel != 0) != COOP)) return;  // the other instantiation runs this launch
     // XCD-aware mapping: blocks b, b+8, ... share an XCD (L2); give each XCD a
     // contiguous range of the locality-ordered particles (bijective remap)
@@ -1838,6 +1875,20 @@ __global__ void __launch_bounds__(kTrajBlock, (TrajWaves<MAXV, PATH, EULER, COOP
     for (int step = sb; step < step_end; ++step) {
         MOPS_MARK(100);
         if constexpr (HAND) cell_in = cell;  // (the walk restarts from it at a hand-off)
+        if constexpr (CAP) {
+            if ((uint32_t)step == rec_next && step > (int)a.step_begin) {  // an interior sample step of this launch
+                const int w = rec_k - a.cap_first;
+                if (rec_k < (int)a.K && w >= 0 && w < a.cap_slots) {
+                    const CapPlanes cp = cap_planes(a.cap, a.cap_stride, a.cap_slots);
+                    const int64_t at = (int64_t)w * a.cap_stride + pid;
+                    cp.x[at] = x;
+                    cp.y[at] = y;
+                    cp.z[at] = z;
+                    cp.dep[at] = dep;
+                    cp.cell[at] = cell;
+                }
+            }
+        }
         if (step == 0) {  // first_loop (:892-901)
             if (cell < 0 || cell >= C) { died = 0; break; }
             dev::load_cell<MAXV, kRC, kNrm, kCoop>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly, a.cnrm);
@@ -2190,21 +2241,28 @@ struct SampleArgs {
 // the plain one-hop walk from the stored cell (dev::walk): traj_kernel's stay-ball and neighbour-table shortcuts
 // are exact, so it gives their answer.  Gather-bound (2 nv eight-byte loads per attribute, field and
 // evaluation), no LDS; built with the engine's flags (no contraction).
-template <int MAXV, bool EULER>
-__global__ void __launch_bounds__(256) traj_sample_attrs_kernel(SampleArgs s) {
+//
+// sample_lane is that step for one lane; the step-start state -- the step, position, float depth and the cell the
+// walk starts from -- and the output slot come from a source `src`: SampleFromState (this kernel: the particle
+// arrays) or SampleFromCapture (traj_sample_captured_kernel: what a CAP trajectory launch captured).  Each read
+// stands where this kernel's own read stood before the two shared the body, so its code did not change.
+struct SampleFromState {
+    const SampleArgs& s;
+    int64_t pid;
+    __device__ int step() const { return (int)s.t.step_begin; }
+    __device__ double x() const { return s.t.px[pid]; }
+    __device__ double y() const { return s.t.py[pid]; }
+    __device__ double z() const { return s.t.pz[pid]; }
+    __device__ float depth() const { return s.t.depth[pid]; }
+    __device__ int cell() const { return s.t.cell[pid]; }
+    __device__ double* out() const { return s.out; }
+};
+template <int MAXV, bool EULER, class Src>
+__device__ __forceinline__ void sample_lane(const SampleArgs& s, const Src& src, const int64_t pid) {
     const TrajArgs& a = s.t;
-    int64_t n = a.n;
-    if (a.n_live) {
-        const int64_t nl = *a.n_live;
-        n = nl < n ? nl : n;
-    }
-    const int64_t slot = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= n) return;
-    const int64_t pid = a.order ? (int64_t)a.order[slot] : slot;
-    if (a.death[pid] >= 0) return;  // the reference's lambda has returned
-    const int step = (int)a.step_begin;
-    const double x = a.px[pid], y = a.py[pid], z = a.pz[pid];
-    int cell = a.cell[pid];
+    const int step = src.step();
+    const double x = src.x(), y = src.y(), z = src.z();
+    int cell = src.cell();
     const int C = a.C;
     if (cell < 0 || cell >= C) return;  // :1354-1356, :1362-1364 (the step kills the particle)
     dev::Cell<MAXV> c;
@@ -2221,7 +2279,7 @@ __global__ void __launch_bounds__(256) traj_sample_attrs_kernel(SampleArgs s) {
         cell = dev::walk<MAXV>(c, cell, x, y, z, a.cellrec, a.cxyz, C);
         if (c.id != cell) dev::load_cell<MAXV, false, false>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly);
     }
-    const double d = -1.0 * (double)a.depth[pid];
+    const double d = -1.0 * (double)src.depth();
     const double alpha = a.alpha_tab ? a.alpha_tab[step] : (double)step / (double)a.n_steps;  // (the same bits)
     int hint0 = -1, hint1 = -1;
     constexpr int GR = PairGroup<true, EULER>::value;
@@ -2258,7 +2316,60 @@ __global__ void __launch_bounds__(256) traj_sample_attrs_kernel(SampleArgs s) {
     }
 #pragma unroll
     for (int k = 0; k < MOPS_MAX_SAMPLE_ATTRS; ++k)
-        if (k < s.n_attr) s.out[(int64_t)k * s.stride + pid] = attr[k];
+        if (k < s.n_attr) src.out()[(int64_t)k * s.stride + pid] = attr[k];
+}
+
+template <int MAXV, bool EULER>
+__global__ void __launch_bounds__(256) traj_sample_attrs_kernel(SampleArgs s) {
+    const TrajArgs& a = s.t;
+    int64_t n = a.n;
+    if (a.n_live) {
+        const int64_t nl = *a.n_live;
+        n = nl < n ? nl : n;
+    }
+    const int64_t slot = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= n) return;
+    const int64_t pid = a.order ? (int64_t)a.order[slot] : slot;
+    if (a.death[pid] >= 0) return;  // the reference's lambda has returned
+    sample_lane<MAXV, EULER>(s, SampleFromState{s, pid}, pid);
+}
+
+// The batched form after a CAP trajectory launch: one lane per (window slot w, particle), blockIdx.y = w.  The
+// state is what the launch captured at the top of sample step j = (cap_first + w + 1) ri - 1; a lane whose cell
+// plane still holds the host's mark (-1: the particle was dead by then, or the window slot was not reached)
+// writes nothing, as does a lane the step kills.  It writes attribute slot cap_first + w.  s.t.step_begin is
+// unused; s.out is the slab's base.  Lanes run over pid directly (the capture is indexed by pid, like the slab).
+struct CapSampleArgs {
+    SampleArgs s;
+    const char* cap;
+    int64_t cap_stride;
+    int cap_first, cap_slots, n_win;  // n_win <= cap_slots: the window slots this launch captured
+    int ri;
+};
+struct SampleFromCapture {
+    CapPlanes cp;
+    int64_t at;    // window slot * stride + pid
+    int slot, ri;  // the attribute slot, written at step (slot + 1) ri - 1
+    double* o;
+    __device__ int step() const { return (slot + 1) * ri - 1; }
+    __device__ double x() const { return cp.x[at]; }
+    __device__ double y() const { return cp.y[at]; }
+    __device__ double z() const { return cp.z[at]; }
+    __device__ float depth() const { return cp.dep[at]; }
+    __device__ int cell() const { return cp.cell[at]; }
+    __device__ double* out() const { return o; }
+};
+template <int MAXV, bool EULER>
+__global__ void __launch_bounds__(256) traj_sample_captured_kernel(CapSampleArgs cs) {
+    const SampleArgs& s = cs.s;
+    const int64_t pid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int w = (int)blockIdx.y;
+    if (pid >= s.t.n || w >= cs.n_win) return;
+    const SampleFromCapture src{cap_planes(const_cast<char*>(cs.cap), cs.cap_stride, cs.cap_slots),
+                                (int64_t)w * cs.cap_stride + pid, cs.cap_first + w, cs.ri,
+                                s.out + (int64_t)(cs.cap_first + w) * s.n_attr * s.stride};
+    if (src.cell() < 0) return;
+    sample_lane<MAXV, EULER>(s, src, pid);
 }
 
 // the neighbour-table test against the walk it short-cuts (mops_selftest_walk): bit 0 = dev::nbr_stay kept
@@ -3658,6 +3769,19 @@ void launch_traj(const TrajArgs& a, bool path, bool euler, hipStream_t s) {
     }
 }
 
+// launch_traj's pathline MAXV 7 branch with the CAP instantiations (a.cap set; mops_traj_advance_captured)
+static void launch_traj_cap(const TrajArgsCap& a, bool euler, hipStream_t s) {
+    const unsigned g = (unsigned)((a.n + kTrajBlock - 1) / kTrajBlock);
+    if (euler) {
+        if (a.coop_sel) traj_kernel<7, true, true, true, false, true><<<g, kTrajBlock, 0, s>>>(a);
+        traj_kernel<7, true, true, false, false, true><<<g, kTrajBlock, 0, s>>>(a);
+    } else {
+        if (a.coop_sel && a.handoff) traj_kernel<7, true, false, true, true, true><<<g, kTrajBlock, 0, s>>>(a);
+        if (a.coop_sel) traj_kernel<7, true, false, true, false, true><<<g, kTrajBlock, 0, s>>>(a);
+        traj_kernel<7, true, false, false, false, true><<<g, kTrajBlock, 0, s>>>(a);
+    }
+}
+
 // The trajectory kernel's exact fast sqrt / sin / cos / a/|a| restate the device library's and the
 // compiler's own expansions (dev::sqrt_core, sincos_small, xdiv_norm3, xdiv_ns / wach_fast).  A toolchain whose
 // expansions changed would break the bit parity silently, so every mesh creation first checks
@@ -4508,9 +4632,18 @@ int64_t mops_traj_num_steps(const mops_traj_cfg* cfg) {
     return cfg->simulation_duration / cfg->delta_t;
 }
 
-mops_status mops_traj_advance(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
-                              const mops_traj_cfg* cfg, const mops_particles* p, int64_t step_begin,
-                              int64_t step_end, double* d_records, int64_t record_stride, void* stream) {
+// One capture window of mops_traj_advance_captured: the slab, its slots and the record slot of window slot 0
+struct CapWindow {
+    char* base;
+    int64_t stride;
+    int first, slots;
+};
+
+// mops_traj_advance; `cw` (pathline, maxv 7 only): the launch's CAP instantiations with that capture window
+static mops_status traj_advance_impl(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                     const mops_traj_cfg* cfg, const mops_particles* p, int64_t step_begin,
+                                     int64_t step_end, double* d_records, int64_t record_stride, void* stream,
+                                     const CapWindow* cw) {
     if (!mesh || !front || !cfg || !p) return fail(MOPS_ERR_INVALID, "mops_traj_advance: invalid inputs");
     if (cfg->delta_t <= 0 || cfg->record_t <= 0 || cfg->simulation_duration <= 0)
         return fail(MOPS_ERR_INVALID, "invalid trajectory settings");  // :666-669
@@ -4532,7 +4665,7 @@ mops_status mops_traj_advance(const mops_mesh* mesh, const mops_field* front, co
     step_end = std::min<int64_t>(step_end, n_steps);
     if (step_begin >= step_end) return MOPS_OK;
     if (cfg->delta_t > INT32_MAX) return fail(MOPS_ERR_INVALID, "deltaT too large");
-    TrajArgs a;
+    TrajArgsCap a;  // (launch_traj takes its TrajArgs part)
     a.cellrec = mesh->d_cellrec; a.cxyz = mesh->d_cxyz; a.vxyz = mesh->d_vxyz;
     a.C = (int)mesh->C; a.V = (int)mesh->V; a.L = mesh->L;
     a.f0 = dev::Field{front->d_zt, front->d_pr};
@@ -4568,6 +4701,15 @@ mops_status mops_traj_advance(const mops_mesh* mesh, const mops_field* front, co
         a.coop_sel = sel;
     }
     a.handoff = (MOPS_RK4_HANDOFF && !euler && a.coop_sel) ? 1 : 0;
+    a.cap = nullptr; a.cap_stride = 0; a.cap_first = 0; a.cap_slots = 0;
+    if (cw) {
+        if (!back || mesh->maxv != 7 || !cw->base || cw->slots < 1 || cw->stride < p->n)
+            return fail(MOPS_ERR_INVALID, "mops_traj_advance: invalid capture window");
+        a.cap = cw->base; a.cap_stride = cw->stride; a.cap_first = cw->first; a.cap_slots = cw->slots;
+        launch_traj_cap(a, euler, s);
+        HIP_TRY(hipGetLastError());
+        return MOPS_OK;
+    }
     switch (mesh->maxv) {
         case 7: launch_traj<7>(a, back != nullptr, euler, s); break;
 #if !defined(MOPS_ONLY7)  // experiment builds: MAXV 7 instantiations only
@@ -4579,6 +4721,12 @@ mops_status mops_traj_advance(const mops_mesh* mesh, const mops_field* front, co
     }
     HIP_TRY(hipGetLastError());
     return MOPS_OK;
+}
+
+mops_status mops_traj_advance(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                              const mops_traj_cfg* cfg, const mops_particles* p, int64_t step_begin,
+                              int64_t step_end, double* d_records, int64_t record_stride, void* stream) {
+    return traj_advance_impl(mesh, front, back, cfg, p, step_begin, step_end, d_records, record_stride, stream, nullptr);
 }
 
 mops_status mops_traj_finalize(int64_t n, int64_t K, const double* d_seeds, const double* d_records,
@@ -4648,13 +4796,12 @@ static mops_status sample_check(const char* who, const mops_mesh* mesh, const mo
     return MOPS_OK;
 }
 
-// One launch of the sampling kernel for checked arguments; `slot` = sample_slot(step)
-static mops_status sample_launch(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
-                                 const mops_traj_cfg* cfg, const mops_particles* p, int64_t step, int64_t slot,
-                                 int32_t n_attr, const double* const* d_fa, const double* const* d_ba, double* d_slab,
-                                 int64_t attr_stride, hipStream_t s) {
-    if (p->n == 0) return MOPS_OK;
-    SampleArgs sa{};
+// The sampling kernels' arguments but the step and the output slot, for checked arguments
+static mops_status sample_args(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                               const mops_traj_cfg* cfg, const mops_particles* p, int32_t n_attr,
+                               const double* const* d_fa, const double* const* d_ba, int64_t attr_stride,
+                               SampleArgs* out) {
+    SampleArgs& sa = *out;
     TrajArgs& a = sa.t;
     a.cellrec = mesh->d_cellrec; a.cxyz = mesh->d_cxyz; a.vxyz = mesh->d_vxyz;
     a.C = (int)mesh->C; a.V = (int)mesh->V; a.L = mesh->L;
@@ -4671,14 +4818,25 @@ static mops_status sample_launch(const mops_mesh* mesh, const mops_field* front,
     MOPS_TRY(alpha_table(mesh, a.n_steps, &a.alpha_tab));  // the table the trajectory launches read (or the division)
     a.px = p->d_x; a.py = p->d_y; a.pz = p->d_z; a.depth = p->d_depth; a.cell = p->d_cell; a.death = p->d_death_step;
     a.n = p->n;
-    a.step_begin = step; a.step_end = step + 1;
     a.delta_t = ((cfg->direction == MOPS_FORWARD) ? 1 : -1) * (int)cfg->delta_t;
     a.dalpha = (double)a.delta_t / (double)cfg->simulation_duration;
     sa.vold = mesh->d_vold;
     sa.n_attr = n_attr;
     for (int k = 0; k < n_attr; ++k) { sa.af[k] = d_fa[k]; sa.ab[k] = d_ba[k]; }
-    sa.out = d_slab + slot * n_attr * attr_stride;
     sa.stride = attr_stride;
+    return MOPS_OK;
+}
+
+// One launch of the sampling kernel for checked arguments; `slot` = sample_slot(step)
+static mops_status sample_launch(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                 const mops_traj_cfg* cfg, const mops_particles* p, int64_t step, int64_t slot,
+                                 int32_t n_attr, const double* const* d_fa, const double* const* d_ba, double* d_slab,
+                                 int64_t attr_stride, hipStream_t s) {
+    if (p->n == 0) return MOPS_OK;
+    SampleArgs sa{};
+    MOPS_TRY(sample_args(mesh, front, back, cfg, p, n_attr, d_fa, d_ba, attr_stride, &sa));
+    sa.t.step_begin = step; sa.t.step_end = step + 1;
+    sa.out = d_slab + slot * n_attr * attr_stride;
     const bool euler = (cfg->method == MOPS_EULER);
     const unsigned g = (unsigned)((p->n + 255) / 256);
     switch (mesh->maxv) {
@@ -4746,6 +4904,114 @@ mops_status mops_traj_advance_sampled(const mops_mesh* mesh, const mops_field* f
         }
     }
     return mops_traj_advance(mesh, front, back, cfg, p, cur, se, d_records, record_stride, stream);
+}
+
+int64_t mops_traj_capture_bytes(int64_t stride, int64_t slots) {
+    if (stride < 0 || slots < 0) return -1;
+    if (stride == 0 || slots == 0) return 0;
+    if (stride > INT64_MAX / 32 / slots) return -1;
+    return 32 * stride * slots;  // x, y, z (double), depth (float), cell (int) per particle and slot
+}
+
+// A launch's window holds at most this many slots (the batched sampler's blockIdx.y)
+constexpr int64_t kCapWindowMax = 65535;
+
+int64_t mops_traj_capture_plan(const mops_traj_cfg* cfg, int64_t step_begin, int64_t step_end, int64_t capture_slots,
+                               int64_t* out_bounds, int64_t cap) {
+    if (!cfg || cfg->delta_t <= 0 || cfg->record_t <= 0 || cfg->simulation_duration <= 0 || capture_slots < 0 ||
+        cap < 0 || (cap > 0 && !out_bounds)) {
+        (void)fail(MOPS_ERR_INVALID, "mops_traj_capture_plan: invalid argument");
+        return -1;
+    }
+    const int64_t K = mops_traj_num_records(cfg), n_steps = mops_traj_num_steps(cfg), ri = cfg->record_t / cfg->delta_t;
+    if (K <= 0 || n_steps <= 0) {
+        (void)fail(MOPS_ERR_INVALID, "invalid integration steps");
+        return -1;
+    }
+    const int64_t sb = std::max<int64_t>(step_begin, 0), se = std::min<int64_t>(step_end, n_steps);
+    const int64_t W = std::min(capture_slots, kCapWindowMax);
+    int64_t count = 0, cur = sb;
+    while (cur < se) {
+        // the (W + 1)-th sample step after cur begins the next launch; sample steps past step 0 are m ri - 1, m <= K
+        int64_t end = se;
+        if (ri > 0) {
+            const int64_t m = (cur + 1) / ri + 1 + W;  // (cur + 1) / ri + 1: the first m with m ri - 1 > cur
+            if (m <= K && m * ri - 1 < se) end = m * ri - 1;
+        }
+        if (count < cap) out_bounds[count] = end;
+        ++count;
+        cur = end;
+    }
+    return count;
+}
+
+mops_status mops_traj_advance_captured(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                       const mops_traj_cfg* cfg, const mops_particles* p, int64_t step_begin,
+                                       int64_t step_end, double* d_records, int64_t record_stride, int32_t n_attr,
+                                       const double* const* d_front_attrs, const double* const* d_back_attrs,
+                                       double* d_attr_records, int64_t attr_stride, void* d_capture,
+                                       int64_t capture_slots, void* stream) {
+    MOPS_TRY(sample_check("mops_traj_advance_captured", mesh, front, back, cfg, p, n_attr, d_front_attrs, d_back_attrs,
+                          d_attr_records, attr_stride));
+    if (record_stride < p->n) return fail(MOPS_ERR_INVALID, "record_stride < n");
+    if (capture_slots < 0) return fail(MOPS_ERR_INVALID, "mops_traj_advance_captured: capture_slots < 0");
+    if (capture_slots > 0 && !d_capture && p->n > 0)
+        return fail(MOPS_ERR_INVALID, "mops_traj_advance_captured: null capture slab");
+    if (mops_traj_capture_bytes(p->n, capture_slots) < 0)
+        return fail(MOPS_ERR_INVALID, "mops_traj_advance_captured: capture slab size overflows");
+    if (capture_slots == 0 || mesh->maxv != 7)  // the split path: no CAP instantiations past maxEdges 7
+        return mops_traj_advance_sampled(mesh, front, back, cfg, p, step_begin, step_end, d_records, record_stride,
+                                         n_attr, d_front_attrs, d_back_attrs, d_attr_records, attr_stride, stream);
+    if (p->n == 0) return MOPS_OK;
+    if (!d_records) return fail(MOPS_ERR_INVALID, "mops_traj_advance_captured: null device pointer");
+    const int64_t K = mops_traj_num_records(cfg), n_steps = mops_traj_num_steps(cfg), ri = cfg->record_t / cfg->delta_t;
+    const int64_t sb = std::max<int64_t>(step_begin, 0), se = std::min<int64_t>(step_end, n_steps);
+    if (sb >= se) return MOPS_OK;
+    const int64_t nl = mops_traj_capture_plan(cfg, sb, se, capture_slots, nullptr, 0);
+    if (nl < 0) return MOPS_ERR_INVALID;
+    std::vector<int64_t> ends((size_t)nl);
+    (void)mops_traj_capture_plan(cfg, sb, se, capture_slots, ends.data(), nl);
+    hipStream_t s = (hipStream_t)stream;
+    const bool euler = (cfg->method == MOPS_EULER);
+    const CapPlanes planes = cap_planes(static_cast<char*>(d_capture), p->n, capture_slots);
+    int64_t cur = sb;
+    for (int64_t i = 0; i < nl; ++i) {
+        const int64_t end = ends[(size_t)i];
+        // the launch's interior sample steps m ri - 1 in (cur, end): slots first .. first + nwin - 1
+        int64_t first = 0, nwin = 0;
+        if (ri > 0) {
+            const int64_t m0 = (cur + 1) / ri + 1;                  // the first m with m ri - 1 > cur
+            const int64_t m1 = std::min<int64_t>(K, end / ri);      // the last m with m ri - 1 < end
+            first = m0 - 1;
+            nwin = std::max<int64_t>(0, m1 - m0 + 1);
+        }
+        if (nwin > capture_slots) return fail(MOPS_ERR_INVALID,"mops_traj_advance_captured: window overflow");
+        if (nwin > 0)  // mark: cell = -1 in the window's slots
+            HIP_TRY(hipMemsetAsync(planes.cell, 0xff, (size_t)(nwin * p->n) * sizeof(int), s));
+        const int64_t slot = sample_slot(cur, ri, K, n_steps);
+        if (slot >= 0)  // the launch's first step, from the particle state
+            MOPS_TRY(sample_launch(mesh, front, back, cfg, p, cur, slot, n_attr, d_front_attrs, d_back_attrs,
+                                   d_attr_records, attr_stride, s));
+        if (nwin == 0) {
+            MOPS_TRY(mops_traj_advance(mesh, front, back, cfg, p, cur, end, d_records, record_stride, stream));
+        } else {
+            const CapWindow cw{static_cast<char*>(d_capture), p->n, (int)first, (int)capture_slots};
+            MOPS_TRY(traj_advance_impl(mesh, front, back, cfg, p, cur, end, d_records, record_stride, stream, &cw));
+            CapSampleArgs cs{};
+            MOPS_TRY(sample_args(mesh, front, back, cfg, p, n_attr, d_front_attrs, d_back_attrs, attr_stride, &cs.s));
+            cs.s.out = d_attr_records;
+            cs.cap = static_cast<const char*>(d_capture);
+            cs.cap_stride = p->n;
+            cs.cap_first = (int)first; cs.cap_slots = (int)capture_slots; cs.n_win = (int)nwin;
+            cs.ri = (int)ri;
+            const dim3 g((unsigned)((p->n + 255) / 256), (unsigned)nwin);
+            if (euler) traj_sample_captured_kernel<7, true><<<g, 256, 0, s>>>(cs);
+            else traj_sample_captured_kernel<7, false><<<g, 256, 0, s>>>(cs);
+            HIP_TRY(hipGetLastError());
+        }
+        cur = end;
+    }
+    return MOPS_OK;
 }
 
 mops_status mops_traj_finalize_attrs(int64_t n, int64_t K, const double* d_seeds, const double* d_records,

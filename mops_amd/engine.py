@@ -291,11 +291,15 @@ class ParticleSet:
     """
 
     def __init__(self, mesh: DeviceMesh, seeds_xyz, depth: float | np.ndarray, cfg: TrajectoryConfig, device=None,
-                 cells=None, use_order: bool = True, record_stride: int | None = None, n_attr: int = 0):
+                 cells=None, use_order: bool = True, record_stride: int | None = None, n_attr: int = 0,
+                 capture_slots: int = 0):
         """``record_stride``: columns of the [K][6][stride] record slab (default n); a multi-GPU
         shard pads it to the largest shard so every rank's slab has one shape
         (distributed.RecordGather).  ``n_attr`` (pathlines, at most 4): also keep a zero-filled
-        [K][n_attr][stride] attribute slab, which ``advance(..., attrs=...)`` samples into."""
+        [K][n_attr][stride] attribute slab, which ``advance(..., attrs=...)`` samples into.
+        ``capture_slots`` > 0 (with ``n_attr``): also a capture slab of that many window slots (32 B per
+        particle and slot, mops_traj_capture_bytes); ``advance(attrs=)`` then runs one trajectory launch per
+        window instead of one per sample step (mops_traj_advance_captured), with the same bytes."""
         import torch
         self.use_order = use_order
         self.torch = torch
@@ -330,6 +334,15 @@ class ParticleSet:
             raise ValueError(f"n_attr must be 0..{MAX_SAMPLE_ATTRS}")
         self.attr_records = None if self.n_attr == 0 else torch.zeros(
             (max(self.K, 1), self.n_attr, self.rec_stride), dtype=torch.float64, device=dev)
+        self.capture_slots = int(capture_slots)
+        if self.capture_slots < 0 or (self.capture_slots > 0 and self.n_attr == 0):
+            raise ValueError("capture_slots must be >= 0 and needs n_attr > 0")
+        self.capture = None
+        if self.capture_slots > 0:
+            nb = int(L.load().mops_traj_capture_bytes(self.n, self.capture_slots))
+            if nb < 0:
+                raise ValueError("capture slab size overflows")
+            self.capture = torch.empty((max(nb, 1),), dtype=torch.uint8, device=dev)
         self.order = torch.empty((self.n,), dtype=torch.int32, device=dev)
         # slot -> particle index: with use_order the state is kept PHYSICALLY in
         # locality order (state loads/stores and record stores coalesce);
@@ -359,10 +372,11 @@ class ParticleSet:
 
     _STATE = (("x", 8), ("y", 8), ("z", 8), ("depth", 4), ("cell", 4), ("death", 4), ("ids", 4), ("seeds", 24))
 
-    def _apply_order(self, order, lo: int, hi: int, stream, record_slots: int):
+    def _apply_order(self, order, lo: int, hi: int, stream, record_slots: int, attr_slots: int | None = None):
         """Permute slots [lo, hi) of the SoA state, seeds, slot ids and the first ``record_slots`` record
-        slots by ``order`` (local indices) with one mops_permute_arrays launch into the spare buffers;
-        the whole set swaps buffers, a sub-range is copied back with a second launch."""
+        slots (and the first ``attr_slots`` attribute slots, default the same count) by ``order`` (local
+        indices) with one mops_permute_arrays launch into the spare buffers; the whole set swaps buffers, a
+        sub-range is copied back with a second launch."""
         torch = self.torch
         n = hi - lo
         if n <= 0:
@@ -372,12 +386,17 @@ class ParticleSet:
         else:
             s = stream if stream is not None else torch.cuda.current_stream(self.seeds.device)
         names = [(k, e) for k, e in self._STATE] + ([("records", 8)] if record_slots > 0 else [])
-        if record_slots > 0 and self.attr_records is not None:
+        if attr_slots is None:
+            attr_slots = record_slots
+        elif self.attr_records is not None:
+            attr_slots = min(int(attr_slots), self.attr_records.shape[0])
+        if attr_slots > 0 and self.attr_records is not None:
             names.append(("attr_records", 8))  # (attribute slot k is written at the steps that write record slot k)
         with torch.cuda.stream(s):
             for k, _ in names:
                 if k not in self._spare:  # (allocated on first use, then kept)
-                    self._spare[k] = torch.empty_like(getattr(self, k))
+                    # (the attribute slab's second buffer is zero-filled like the first, see compact)
+                    self._spare[k] = (torch.zeros_like if k == "attr_records" else torch.empty_like)(getattr(self, k))
 
         def desc(src, dst, name, eb):
             if name == "records":
@@ -385,7 +404,7 @@ class ParticleSet:
                                    self.rec_stride)
             if name == "attr_records":
                 return L.PermArray(src.data_ptr() + 8 * lo, dst.data_ptr() + 8 * lo, 8,
-                                   int(record_slots) * self.n_attr, self.rec_stride)
+                                   int(attr_slots) * self.n_attr, self.rec_stride)
             return L.PermArray(src.data_ptr() + eb * lo, dst.data_ptr() + eb * lo, eb, 1, n)
 
         lib = L.load()
@@ -407,7 +426,7 @@ class ParticleSet:
         out[self.ids.long()] = t
         return out
 
-    def compact(self, lo: int, hi: int, stream, records_written: int):
+    def compact(self, lo: int, hi: int, stream, records_written: int, attr_slots_written: int | None = None):
         """Dead-particle compaction of slots [lo, hi) on ``stream`` (mops_order_particles_live):
         live particles in the Morton order of their current cell first, dead ones after them, so
         the next launches run full waves of live lanes and all-dead waves exit at once.  The SoA
@@ -416,9 +435,17 @@ class ParticleSet:
         (mops_records_clear_dead: they hold no samples, the live particles' ones are written by
         the next launches).  Results are unchanged (every particle is independent, finalize
         writes each slot's line at its id).  Re-entrant across disjoint ranges on different
-        streams (each range has its own scratch)."""
+        streams (each range has its own scratch).
+
+        A set with an attribute slab needs ``attr_slots_written``: the first that many attribute slots move
+        with their particles (at a step boundary s0 the records' count, min(K, s0 // period + 1)).  The
+        attribute slab needs no clearing pass: it is zero-filled at ``reset`` / ``reseed`` and a dead lane
+        writes nothing, so every slot not yet written is zero in every column, wherever a particle lands.
+        That holds for the permutation's second buffer too, which becomes the slab when the whole set is
+        compacted: it is allocated zero-filled and zero-filled again at ``reset`` / ``reseed``, and between
+        those only slots below a written count -- which every later permutation overwrites -- are stored to it."""
         torch = self.torch
-        if self.attr_records is not None:
+        if self.attr_records is not None and attr_slots_written is None:
             raise ValueError("compact: not supported for a particle set with an attribute slab")
         n = hi - lo
         if n <= 1:
@@ -444,7 +471,8 @@ class ParticleSet:
                                               C.c_void_p(scratch.data_ptr()), scratch.numel(), _stream_handle(s)),
                 "mops_order_particles_live")
         kw = min(int(records_written), self.records.shape[0])
-        self._apply_order(self.order, lo, hi, s, kw)
+        self._apply_order(self.order, lo, hi, s, kw,
+                          None if self.attr_records is None else max(0, int(attr_slots_written)))
         L.check(lib.mops_records_clear_dead(n, C.c_void_p(self._n_live[key].data_ptr()), kw, self.K,
                                             C.c_void_p(self.records.data_ptr() + 8 * lo), self.rec_stride,
                                             _stream_handle(s)), "mops_records_clear_dead")
@@ -467,6 +495,16 @@ class ParticleSet:
         old, self.records = self.records, slab
         return old
 
+    def swap_attr_records(self, slab):
+        """``swap_records`` for the attribute slab [K][n_attr][stride] (a chain's deferred assembly); the
+        installed slab must be zero-filled, as ``reseed`` leaves it."""
+        if self.attr_records is None:
+            raise ValueError("swap_attr_records: the particle set has no attribute slab")
+        if tuple(slab.shape) != tuple(self.attr_records.shape) or slab.dtype != self.attr_records.dtype:
+            raise ValueError("attribute slab shape/dtype mismatch")
+        old, self.attr_records = self.attr_records, slab
+        return old
+
     def reset(self, depth=None):
         self.x.copy_(self.seeds[:, 0]); self.y.copy_(self.seeds[:, 1]); self.z.copy_(self.seeds[:, 2])
         if depth is not None:
@@ -475,6 +513,8 @@ class ParticleSet:
         self._written = False  # (records: every slot is rewritten by the launches from step 0)
         if self.attr_records is not None:
             self.attr_records.zero_()  # (a particle that never reaches a slot leaves its zero there)
+            if "attr_records" in self._spare:
+                self._spare["attr_records"].zero_()  # (the slab after the next whole-set permutation)
 
     def reseed(self, seeds, depth, stream=None, hint_cells: bool = False):
         """Start a new run from device-resident seeds [n,3] (f64) and depth (scalar
@@ -500,6 +540,8 @@ class ParticleSet:
         self._written = False
         if self.attr_records is not None:
             self.attr_records.zero_()
+            if "attr_records" in self._spare:
+                self._spare["attr_records"].zero_()
         self.mesh.locate(self.seeds.data_ptr(), self.cell.data_ptr(), self.n, stream=h,
                          d_hint=None if hint is None else hint.data_ptr())
         self.reorder(stream=h)
@@ -520,11 +562,7 @@ class ParticleSet:
             if self.attr_records is None or len(attrs[0]) != self.n_attr:
                 raise ValueError("advance: attrs needs a particle set created with n_attr = the number of attributes")
             fa, ba = _attr_ptr_lists(self.mesh, list(attrs[0]), list(attrs[1]))
-            st = L.load().mops_traj_advance_sampled(
-                self.mesh.handle, front.handle, None if back is None else back.handle, C.byref(self._c), C.byref(p),
-                int(step_begin), int(step_end), C.c_void_p(self.records.data_ptr()), self.rec_stride, self.n_attr, fa,
-                ba, C.c_void_p(self.attr_records.data_ptr()), self.rec_stride, _stream_handle(stream))
-            L.check(st, "mops_traj_advance_sampled")
+            self._advance_attrs(front, back, p, 0, int(step_begin), int(step_end), fa, ba, stream)
             self._written = True
             return
         st = L.load().mops_traj_advance(self.mesh.handle, front.handle, None if back is None else back.handle,
@@ -532,6 +570,26 @@ class ParticleSet:
                                         C.c_void_p(self.records.data_ptr()), self.rec_stride, _stream_handle(stream))
         L.check(st, "mops_traj_advance")
         self._written = True
+
+    def _advance_attrs(self, front, back, p, lo: int, step_begin: int, step_end: int, fa, ba, stream):
+        """The sampled advance of the slots ``p`` describes, which begin at slot ``lo``: through the capture
+        slab when the set has one (mops_traj_advance_captured; the part's own piece of it, 32 B x
+        capture_slots per slot), else with a launch boundary per sample step (mops_traj_advance_sampled)."""
+        lib = L.load()
+        bh = None if back is None else back.handle
+        rec = C.c_void_p(self.records.data_ptr() + 8 * lo)
+        slab = C.c_void_p(self.attr_records.data_ptr() + 8 * lo)
+        if self.capture is not None:
+            L.check(lib.mops_traj_advance_captured(
+                self.mesh.handle, front.handle, bh, C.byref(self._c), C.byref(p), step_begin, step_end, rec,
+                self.rec_stride, self.n_attr, fa, ba, slab, self.rec_stride,
+                C.c_void_p(self.capture.data_ptr() + 32 * self.capture_slots * lo), self.capture_slots,
+                _stream_handle(stream)), "mops_traj_advance_captured")
+        else:
+            L.check(lib.mops_traj_advance_sampled(
+                self.mesh.handle, front.handle, bh, C.byref(self._c), C.byref(p), step_begin, step_end, rec,
+                self.rec_stride, self.n_attr, fa, ba, slab, self.rec_stride, _stream_handle(stream)),
+                "mops_traj_advance_sampled")
 
     def _sub_particles(self, lo: int, hi: int, live_count=None) -> L.Particles:
         """Slots [lo, hi) as a launch argument; ``live_count``: the range's device live count after a
@@ -543,7 +601,8 @@ class ParticleSet:
                            None if live_count is None else live_count.data_ptr())
 
     def advance_pipelined(self, front: DeviceField, back: DeviceField | None, step_begin: int, step_end: int,
-                          streams, chunks: int, timing=None, compact: bool = False, compact_priority: bool = False):
+                          streams, chunks: int, timing=None, compact: bool = False, compact_priority: bool = False,
+                          attrs=None):
         """``advance`` split into len(streams) contiguous particle parts (whole waves), each on its own
         stream, and ``chunks`` step ranges per part, enqueued chunk-major.
 
@@ -557,10 +616,18 @@ class ParticleSet:
         ``compact``: before every chunk but the first, each part is re-sorted on its own stream
         with its dead particles last (``compact``): RK4 kills particles at cell crossings
         (quirk Q1, half of them in a day at config 2), and a wave keeps its slots until its
-        last live lane finishes."""
+        last live lane finishes.  ``attrs`` (as ``advance``; required for a set with an attribute slab):
+        each part runs the sampled advance on its own stream, into its columns of the attribute slab and
+        its own piece of the capture slab; a compaction moves the attribute slots written so far."""
         torch = self.torch
-        if self.attr_records is not None:
+        if self.attr_records is not None and attrs is None:
             raise ValueError("advance_pipelined: not supported for a particle set with an attribute slab")
+        fa = ba = None
+        if attrs is not None:
+            if self.attr_records is None or len(attrs[0]) != self.n_attr:
+                raise ValueError("advance_pipelined: attrs needs a particle set created with n_attr = the number "
+                                 "of attributes")
+            fa, ba = _attr_ptr_lists(self.mesh, list(attrs[0]), list(attrs[1]))
         nparts = max(1, len(streams))
         pb = self.part_bounds(nparts)
         span = int(step_end) - int(step_begin)
@@ -587,19 +654,24 @@ class ParticleSet:
                     if compact_priority:
                         hp = self._hp_streams[k]
                         hp.wait_stream(st)
-                        self.compact(lo, hi, hp, records_written=nrec)
+                        self.compact(lo, hi, hp, records_written=nrec,
+                                     attr_slots_written=None if attrs is None else nrec)
                         st.wait_stream(hp)
                     else:
-                        self.compact(lo, hi, st, records_written=nrec)
+                        self.compact(lo, hi, st, records_written=nrec,
+                                     attr_slots_written=None if attrs is None else nrec)
                 if timing is not None:
                     e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
                     e0.record(st)
                 p = self._sub_particles(lo, hi, self._n_live.get((lo, hi)) if (compact and t > 0) else None)
-                rc = lib.mops_traj_advance(self.mesh.handle, front.handle, None if back is None else back.handle,
-                                           C.byref(self._c), C.byref(p), tb[t], tb[t + 1],
-                                           C.c_void_p(self.records.data_ptr() + 8 * lo), self.rec_stride,
-                                           _stream_handle(st))
-                L.check(rc, "mops_traj_advance")
+                if attrs is not None:
+                    self._advance_attrs(front, back, p, lo, tb[t], tb[t + 1], fa, ba, st)
+                else:
+                    rc = lib.mops_traj_advance(self.mesh.handle, front.handle, None if back is None else back.handle,
+                                               C.byref(self._c), C.byref(p), tb[t], tb[t + 1],
+                                               C.c_void_p(self.records.data_ptr() + 8 * lo), self.rec_stride,
+                                               _stream_handle(st))
+                    L.check(rc, "mops_traj_advance")
                 if timing is not None:
                     e1.record(st)
                     timing.append((e0, e1))

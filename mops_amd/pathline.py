@@ -132,12 +132,16 @@ class MOPSPathline:
             raise RuntimeError("follow_last=True but last_pts is None")
         return self._last_pt.copy()
 
-    def run(self, method: str = "rk4", delta_minutes: int = 1, record_every_minutes: int = 6) -> list:
+    def run(self, method: str = "rk4", delta_minutes: int = 1, record_every_minutes: int = 6,
+            sample_attributes: bool = False) -> list:
         """All month pairs as one device-resident chain; the per-pair lines concatenated (later pairs
         without their first sample), pyMOPSAPI.py:1396-1531.  Returns list[dict] with lineID, points
-        (M, 3), velocity (M, 3), temperature (M,), salinity (M,), lastPoint (3,)."""
+        (M, 3), velocity (M, 3), temperature (M,), salinity (M,), lastPoint (3,).
+        ``sample_attributes``: temperature / salinity are the snapshot files' fields of those names sampled
+        along each line (PathlineChain.run(attrs=True)) instead of the reference's velocity x / y (quirk Q9);
+        a name the files do not carry stays zeros."""
         from .chain import PathlineChain
-        from .engine import DeviceField, DeviceMesh
+        from .engine import DeviceField, DeviceMesh, cell_to_vertex_attr
         from .mpas import MPASOReader, mesh_from_reader, snapshot_from_reader
         if self.pairs is None:
             raise RuntimeError("call set_time(...) before run()")
@@ -151,9 +155,16 @@ class MOPSPathline:
             first = MPASOReader.readSolData(self.yaml_path, dates[0], 0)
             self._mesh = DeviceMesh.from_mesh(mesh_from_reader(self._grid, first.mVertLevels))
 
+        cell_attrs = {}  # snapshot -> its file's cell attributes, from make_field's read to make_attrs
+
         def make_field(i, stream):  # snapshot i read from its file and derived on the device
             sol = MPASOReader.readSolData(self.yaml_path, dates[i], 0)
+            if sample_attributes:
+                cell_attrs[i] = {k: v for k, v in sol.attributes.items() if k in ("temperature", "salinity") and v.size}
             return DeviceField.from_snapshot(self._mesh, snapshot_from_reader(sol, timestep_id=i), stream=stream)
+
+        def make_attrs(i, stream):  # (called right after make_field(i), on the same stream)
+            return {k: cell_to_vertex_attr(self._mesh, v) for k, v in cell_attrs.pop(i).items()}
 
         seeds = self._seeds()
         pdep = None
@@ -161,13 +172,14 @@ class MOPSPathline:
             pdep = self._particle_depths
             if self._follow_last and not self._first_round:  # :1465-1469
                 pdep = np.clip(EARTH_RADIUS_M - np.linalg.norm(seeds, axis=1), 0.0, None).astype(np.float32)
-        chain = PathlineChain(self._mesh, make_field, len(dates), timestamps=stamps, device=self.device)
+        chain = PathlineChain(self._mesh, make_field, len(dates), timestamps=stamps, device=self.device,
+                              make_attrs=make_attrs if sample_attributes else None)
         res = chain.run(seeds, depth=self._depth, particle_depths=pdep,
                         method=L.MOPS_RK4 if method.lower() == "rk4" else L.MOPS_EULER,
                         delta_t=int(delta_minutes) * self._one_min,
                         record_t=int(record_every_minutes) * self._one_min,
                         direction=L.MOPS_FORWARD if self.direction == "forward" else L.MOPS_BACKWARD,
-                        follow_last=self._follow_last)
+                        follow_last=self._follow_last, attrs=bool(sample_attributes))
         out = {k: res[k].cpu().numpy() for k in ("points", "velocity", "temperature", "salinity", "lastPoint")}
         self._last_pt = out["lastPoint"].astype(float, copy=True)
         if self._particle_depths is not None:  # :1491-1495
