@@ -145,6 +145,13 @@ struct TrajectorySettings {
     // current_attrs, MPASOVisualizerKernels.cpp:1288-1324) and fills TrajectoryLine::temperature / salinity with
     // the attributes of those names (zeros for a name that is not sampled).  MOPS_RunStreamLine ignores it.
     bool sampleAttributes = false;
+    // This engine's extension (default: the reference's RK4, quirk Q1, in which a stage point across a cell edge
+    // fails IsInMesh and kills the particle).  True, with methodType kRK4: MOPS_RunPathLine locates each of RK4
+    // stages 2-4 by the step's own one-hop walk from the step's cell and evaluates it in the cell found
+    // (MOPS_RK4_RELOCATE, mops_traj.h); a particle whose stages never leave its cell gets the same bytes.  With
+    // kEuler it has no effect (Euler has no stages).  MOPS_RunStreamLine with it and kRK4, and MOPS_RunPathLine
+    // with it, kRK4 and sampleAttributes, follow the reference's error convention: Error() and an empty list.
+    bool relocateStages = false;
 };
 
 struct SamplingSettings {

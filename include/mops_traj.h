@@ -41,7 +41,14 @@ typedef enum {
 
 /* CalcDirection / CalcMethodType (src/Core/MPASOVisualizer.h:14-15) */
 enum { MOPS_FORWARD = 0, MOPS_BACKWARD = 1 };
-enum { MOPS_RK4 = 0, MOPS_EULER = 1 };
+/* MOPS_RK4_RELOCATE: this engine's extension, the opt-out of quirk Q1 (pathlines only).  The pathline RK4 with each of
+   stages 2-4 located by the step's own one-hop walk from the step's cell -- over its neighbours in cellsOnCell order,
+   then the cell itself; strict <, first minimum -- and evaluated in the cell found, instead of in the step's start
+   cell, where a stage point across a cell edge fails IsInMesh and kills the particle.  The particle's own cell does
+   not move with a stage; a stage that fails in its own cell still kills the particle at that step.  A particle whose
+   stages never leave its cell gets the same bytes as under MOPS_RK4.  A streamline run (back == NULL) and every
+   attribute sampling entry return MOPS_ERR_UNSUPPORTED with it.  Any other value than these three runs as MOPS_RK4. */
+enum { MOPS_RK4 = 0, MOPS_EULER = 1, MOPS_RK4_RELOCATE = 2 };
 
 typedef struct mops_mesh mops_mesh;    /* device-resident mesh (opaque) */
 typedef struct mops_field mops_field;  /* device-resident derived snapshot (opaque) */

@@ -38,6 +38,7 @@ EXPORTED = (
 MOPS_OK, MOPS_ERR_INVALID, MOPS_ERR_HIP, MOPS_ERR_UNSUPPORTED = 0, -1, -2, -3
 MOPS_FORWARD, MOPS_BACKWARD = 0, 1
 MOPS_RK4, MOPS_EULER = 0, 1
+MOPS_RK4_RELOCATE = 2  # pathline RK4 with each stage located in its own cell (the opt-out of quirk Q1; mops_traj.h)
 MOPS_LAYER_REFERENCE, MOPS_LAYER_BRACKET = 0, 1
 
 

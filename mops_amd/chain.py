@@ -173,8 +173,10 @@ class PathlineChain:
         collector) is refused with it.
         ``compact``: dead-particle compaction (ParticleSet.compact) between ``compact_chunks`` launches per
         pair -- live particles re-sorted to the front in locality order, the launch spread over them only;
-        None = on for RK4, whose stages must stay in the step's start cell (quirk Q1: a particle dies at its
-        first cell crossing, ~0.8 per particle-day at config 3).  Result-invariant.
+        None = on for MOPS_RK4 only, whose stages must stay in the step's start cell (quirk Q1: a particle
+        dies at its first cell crossing, ~0.8 per particle-day at config 3), and off for Euler and for
+        MOPS_RK4_RELOCATE, which locates each stage in its own cell and so loses particles as rarely as Euler.
+        Result-invariant.
         ``on_lines(p, lines, ids)``: a writer hook instead of concatenating the lines in HBM (the reference
         caller's lines_acc, pyMOPSAPI.py:1497-1518): each pair's lines are assembled in chunks of
         ``lines_chunk`` particle slots (default all) and handed over as device tensors {points, velocity,
@@ -196,6 +198,8 @@ class PathlineChain:
         0 = a launch boundary at every sample step.  Results are the same bytes for every value.  With
         ``attrs`` False nothing changes: no ``attributes`` key, and temperature / salinity keep quirk Q9."""
         import torch
+        if attrs and int(method) == L.MOPS_RK4_RELOCATE:
+            raise ValueError("attrs: attributes are not sampled with MOPS_RK4_RELOCATE")
         if attrs and self.make_attrs is None:
             raise ValueError("attrs=True needs a chain created with make_attrs")
         if attrs and on_pair is not None and getattr(on_pair, "reads_records", False):

@@ -111,13 +111,24 @@ std::vector<TrajectoryLine> run(TrajectorySettings* config, std::vector<Cartesia
         Error("[%s] invalid trajectory settings", stage);  // :666-669
         return {};
     }
+    // TrajectorySettings::relocateStages (with kRK4 only: Euler has no stages)
+    const bool relocate = config->relocateStages && config->methodType == CalcMethodType::kRK4;
+    if (relocate && !pathline) {
+        Error("[%s] relocateStages is for pathlines only", stage);
+        return {};
+    }
+    if (relocate && config->sampleAttributes) {
+        Error("[%s] sampleAttributes is not supported with relocateStages", stage);
+        return {};
+    }
     const int64_t n = (int64_t)pts.size();
     const bool per_particle = config->hasPerParticleDepths() && config->particle_depths.size() == pts.size();
     std::vector<float> depths(pts.size(), config->depth);  // BuildEffectiveDepths (TrajectoryCommon.h:29-41)
     if (per_particle) depths = config->particle_depths;
     mops_traj_cfg cfg{(int64_t)config->deltaT, (int64_t)config->simulationDuration, (int64_t)config->recordT,
                       config->directionType == CalcDirection::kForward ? MOPS_FORWARD : MOPS_BACKWARD,
-                      config->methodType == CalcMethodType::kEuler ? MOPS_EULER : MOPS_RK4};
+                      config->methodType == CalcMethodType::kEuler ? MOPS_EULER
+                                                                   : (relocate ? MOPS_RK4_RELOCATE : MOPS_RK4)};
     const int64_t K = mops_traj_num_records(&cfg), steps = mops_traj_num_steps(&cfg);
     std::vector<TrajectoryLine> lines((size_t)n);
     for (int64_t i = 0; i < n; ++i) {  // InitTrajectoryLines (:43-55)

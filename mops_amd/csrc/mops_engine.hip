@@ -766,6 +766,12 @@ __device__ __forceinline__ int nverts(const Cell<MAXV>& c) { return NV > 0 ? NV 
 // 12 / 20) trajectory kernels.  With a set of its own the sampling kernel leaves every trajectory kernel's
 // device code as it was profiled (tools/asm_compare.py).
 constexpr int kNvSample = -1;
+// ... and NV = kNvReloc likewise for the relocating RK4 kernel (traj_rk4_reloc_kernel); the brackets' TAG is -NV, so
+// the two sets do not meet there either.  dev::walk has a TAG for the same reason: as one more caller of walk<7> that
+// kernel moved 8 SGPR spills in the capture variant of the plain pathline Euler kernel (found by giving it a copy of
+// one shared helper at a time); with walk<MAXV, 1> every existing kernel's resource report is the parent's (DESIGN
+// section 3.15).
+constexpr int kNvReloc = -2;
 
 template <int MAXV, int NV>
 __device__ __forceinline__ bool weights_finite(const Cell<MAXV>& c, const double* w) {
@@ -1122,7 +1128,7 @@ __device__ __forceinline__ int bracket_mono(const Cell<MAXV>& c, const double* w
 __device__ unsigned long long g_prof[16];
 #endif
 
-template <int MAXV>
+template <int MAXV, int TAG = 0>  // (TAG: instantiations of the relocating RK4 kernel's own, see kNvReloc)
 __device__ __forceinline__ int walk(Cell<MAXV>& c, int cell, double x, double y, double z,
                                     const int* __restrict__ cellrec, const double4* __restrict__ cxyz, int C) {
     MOPS_CNT(4, 1);
@@ -1391,9 +1397,9 @@ __device__ __forceinline__ int layer_eval(const Cell<MAXV>& c, const double* w, 
     MOPS_CNT(6, 1);
     double zdn, zup;
     int layer = -2;
-    if (km >= 1) layer = bracket_mono<MAXV, PATH, (NV < 0)>(c, w, f.zt, L, km, d, hint, zdn, zup);
+    if (km >= 1) layer = bracket_mono<MAXV, PATH, (NV < 0 ? -NV : 0)>(c, w, f.zt, L, km, d, hint, zdn, zup);
     if (layer == -2) {
-        layer = bracket_scan<MAXV, PATH, (NV < 0)>(c, w, f.zt, L, d, zdn, zup);
+        layer = bracket_scan<MAXV, PATH, (NV < 0 ? -NV : 0)>(c, w, f.zt, L, d, zdn, zup);
         hint = layer;
     }
     if (layer < 0) return -1;
@@ -2217,6 +2223,194 @@ traj_kernel(std::conditional_t<CAP, TrajArgsCap, TrajArgs> a) {
     } else {
         if (died >= 0 || step_end == (int)a.n_steps) dev::clear_records(a.rec, a.rec_stride, pid, (rec_k == 0 && rec0) ? 1 : rec_k, a.K);
     }
+}
+
+// ===========================================================================
+// pathline RK4 with stage relocation (MOPS_RK4_RELOCATE)
+// ===========================================================================
+// The opt-out of quirk Q1.  Kernel::PathLine's RK4 (MPASOVisualizerKernels.cpp:1329-1483) evaluates stages 2-4 in
+// the step's start cell, so a stage point across a cell edge fails IsInMesh and the particle dies.  Here each of
+// those stages is first located by the step's own one-hop walk (:1361-1381) -- always from the step's cell, over its
+// candidate list (the neighbours in cellsOnCell order, then the cell; strict <, first minimum, ids outside [0, C)
+// skipped) -- and evaluated in the cell found: IsInMesh, Wachspress, both columns, the velocities and w.  A stage
+// that fails there (two hops away, land, a degenerate layer) kills the particle at that step.  The particle's own
+// cell does not move with a stage; everything else is traj_kernel's pathline RK4 step, expression for expression.
+//
+// One lane per particle, no tile, no hand-off, no capture, no LDS: the polygon is re-read per evaluation and the
+// edge normals are computed per evaluation (load_cell<MAXV, false, false>, as the attribute sampler).  Two stencils
+// are live: `c`, the step's cell, and `cs`, the cell the current stage is evaluated in (a register copy of c while
+// the stage stays, else loaded; kept across stages and steps while its id matches).
+//
+// Stay anchor.  The stage walks run on `c` itself and may move its anchor: dev::walk / dev::nbr_stay write the
+// anchor only when they KEEP c, and then the ball they leave holds "the argmin over c's candidate list is c" for
+// every point inside it -- the statement does not care whether its centre was a step or a stage position.  So the
+// step's anchor stays valid, and a stage ball (centred ahead of the particle) serves the next steps' points too.  A
+// walk that leaves c returns before it touches the anchor.
+#ifndef MOPS_NBR_RELOC
+#define MOPS_NBR_RELOC 1  // dev::nbr_stay before a walk (MAXV 7), for the step and the stage points
+#endif
+template <int MAXV>
+struct RelocWaves {
+    static constexpr int value = MAXV <= 7 ? 2 : 1;  // (as the plain RK4 kernels; the resource report: DESIGN 3.15)
+};
+
+namespace dev {
+// The cell of point (x, y, z) by the one-hop walk from `cell`, whose stencil is c: the stay ball, then the
+// neighbour table, then the walk itself -- the first two are exact shortcuts of the third (dev::walk, dev::nbr_stay)
+template <int MAXV>
+__device__ __forceinline__ int relocate(Cell<MAXV>& c, int cell, double x, double y, double z, const TrajArgs& a) {
+    const double ex = x - c.cx, ey = y - c.cy, ez = z - c.cz;
+    if (ex * ex + ey * ey + ez * ez < c.rs2) return cell;
+    if constexpr (MOPS_NBR_TEST && MOPS_NBR_RELOC && MAXV == 7) {
+        if (nbr_stay<MAXV>(c, cell, x, y, z, a.nbr)) return cell;
+    }
+    return walk<MAXV, 1>(c, cell, x, y, z, a.cellrec, a.cxyz, a.C);  // (its own instantiation: see kNvReloc)
+}
+}  // namespace dev
+
+template <int MAXV>
+__global__ void __launch_bounds__(kTrajBlock, (RelocWaves<MAXV>::value)) traj_rk4_reloc_kernel(TrajArgs a) {
+    // the XCD block remap over the live slots (traj_kernel)
+    unsigned nblk = gridDim.x;
+    int64_t n = a.n;
+    if (a.n_live) {
+        const int64_t nl = *a.n_live;
+        n = nl < n ? nl : n;
+        nblk = (unsigned)((n + blockDim.x - 1) / blockDim.x);
+    }
+    const unsigned b = blockIdx.x;
+    if (b >= nblk) return;
+    const unsigned xcd = b % 8u, q = nblk / 8u, r8 = nblk % 8u;
+    const unsigned blk = (xcd < r8 ? xcd * (q + 1u) : r8 * (q + 1u) + (xcd - r8) * q) + b / 8u;
+    const int64_t slot = (int64_t)blk * blockDim.x + threadIdx.x;
+    if (slot >= n) return;
+    const int64_t pid = a.order ? (int64_t)a.order[slot] : slot;
+    const int sb = (int)a.step_begin, step_end = (int)a.step_end;  // (32-bit in here: mops_traj_advance checks)
+    if (a.death[pid] >= 0) {  // the reference's lambda has returned
+        if (a.step_begin == 0) dev::clear_records(a.rec, a.rec_stride, pid, 0, a.K);
+        return;
+    }
+    double x = a.px[pid], y = a.py[pid], z = a.pz[pid];
+    float dep = a.depth[pid];
+    int cell = a.cell[pid];
+    int died = -1;
+    int hint0 = -1, hint1 = -1;  // previous layer per field (speed only)
+    dev::Cell<MAXV> c, cs;
+    c.id = -1; c.nv = 0; c.V = a.V; c.cpolyr = a.cpolyr; c.crank = a.crank; c.C = (uint32_t)a.C;
+    c.nrm = nullptr; c.lds_n = false;
+    cs = c;
+    const int C = a.C;
+    const int rec_period = (int)a.rec_period;
+    uint32_t rec_next = ~(uint32_t)0;
+    int rec_k = 0;
+    bool rec0 = sb > 0;  // record 0's step-0 part (seed position, zero velocity) written
+    if (rec_period > 0) {
+        rec_k = sb / rec_period;
+        rec_next = (uint32_t)(rec_k + 1) * (uint32_t)rec_period - 1u;
+    }
+    constexpr int GR = PairGroup<true, false>::value;
+    const double dt = (double)a.delta_t;
+    for (int step = sb; step < step_end; ++step) {
+        if (step == 0) {  // first_loop (:1351-1360)
+            if (cell < 0 || cell >= C) { died = 0; break; }
+            dev::load_cell<MAXV, false, false>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly);
+            double* r0 = a.rec;
+            r0[0 * a.rec_stride + pid] = x;
+            r0[1 * a.rec_stride + pid] = y;
+            r0[2 * a.rec_stride + pid] = z;
+            r0[3 * a.rec_stride + pid] = 0.0;  // (first_vel below, once step 0 evaluates)
+            r0[4 * a.rec_stride + pid] = 0.0;
+            r0[5 * a.rec_stride + pid] = 0.0;
+            rec0 = true;
+        } else {  // one-hop nearest-centre walk (:1361-1381)
+            if (cell < 0 || cell >= C) { died = step; break; }
+            if (c.id != cell) dev::load_cell<MAXV, false, false>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly);
+            cell = dev::relocate<MAXV>(c, cell, x, y, z, a);
+            if (c.id != cell) {
+                if (cs.id == cell) c = cs;  // (the cell a stage was evaluated in: its anchor is load_cell's)
+                else dev::load_cell<MAXV, false, false>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly);
+            }
+        }
+        const double d = -1.0 * (double)dep;
+        const double r = dev::len3(x, y, z);
+        const double a1 = a.alpha_tab ? a.alpha_tab[step] : (double)step / (double)a.n_steps;  // (the same bits)
+        const double a2 = dev::dclamp(a1 + 0.5 * a.dalpha, 0.0, 1.0), a4 = dev::dclamp(a1 + a.dalpha, 0.0, 1.0);
+        // The four stages, one evaluation in a loop, each in `cs`: stage 1 at the position in the step's cell,
+        // stages 2-3 half a step along the previous stage's velocity, stage 4 a whole step, each in its own cell;
+        // the stage velocities summed as they come in the reference's association ((s1 + 2 s2) + 2 s3) + s4
+        // (:1430-1432), as traj_kernel
+        double hx = 0, hy = 0, hz = 0, wv = 0;
+        double sx = 0, sy = 0, sz = 0, sw = 0;
+        double qx = x, qy = y, qz = z;
+        bool ok = true;
+#pragma unroll 1
+        for (int st = 0; st < 4; ++st) {
+            int sc = cell;
+            if (st > 0) {
+                dev::advect((unsigned)step, x, y, z, sx, sy, sz, st == 3 ? dt : dt * 0.5, qx, qy, qz);
+                sc = dev::relocate<MAXV>(c, cell, qx, qy, qz, a);
+            }
+            if (cs.id != sc) {
+                if (sc == cell) cs = c;
+                else dev::load_cell<MAXV, false, false>(cs, sc, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly);
+            }
+            const double as = st == 0 ? a1 : (st == 3 ? a4 : a2);
+            // (the general vertex count in instantiations of this kernel's own, dev::kNvReloc: the lanes of a wave
+            // sit in different stage cells, and the trajectory kernels' instantiations stay theirs alone)
+            ok = dev::eval_path<MAXV, GR, dev::kNvReloc>(cs, a.L, a.V, a.f0, a.f1, qx, qy, qz, d, as, hint0, hint1, sx, sy,
+                                                         sz, sw);
+            if (!ok) break;
+            if (st == 0) { hx = sx; hy = sy; hz = sz; wv = sw; }
+            else if (st < 3) { hx = hx + sx * 2.0; hy = hy + sy * 2.0; hz = hz + sz * 2.0; wv = wv + 2.0 * sw; }
+            else { hx = (hx + sx) / 6.0; hy = (hy + sy) / 6.0; hz = (hz + sz) / 6.0; wv = (wv + sw) / 6.0; }
+        }
+        if (!ok) { died = step; break; }
+        double nx, ny, nz;
+        const double tx = x + hx * dt, ty = y + hy * dt, tz = z + hz * dt;
+        const double tl = dev::len3(tx, ty, tz);
+        if (tl > 1e-12) {
+            dev::xdiv_norm3(tx, ty, tz, tl, nx, ny, nz);
+            nx *= r; ny *= r; nz *= r;
+        }
+        else { nx = x; ny = y; nz = z; }
+        // vertical update (:1458-1467)
+        const double old_depth = (double)dep;
+        double nd = old_depth - wv * (double)a.delta_t;
+        nd = dev::dmax(0.0, nd);
+        const double r_new = dev::dmax(1.0, r + wv * (double)a.delta_t);
+        dep = (float)nd;
+        const double nl = dev::len3(nx, ny, nz);
+        if (nl > 1e-12) {
+            dev::xdiv_norm3(nx, ny, nz, nl, nx, ny, nz);
+            nx *= r_new; ny *= r_new; nz *= r_new;
+        }
+        if (step == 0) {  // first_vel
+            a.rec[3 * a.rec_stride + pid] = hx;
+            a.rec[4 * a.rec_stride + pid] = hy;
+            a.rec[5 * a.rec_stride + pid] = hz;
+        }
+        x = nx; y = ny; z = nz;
+        if ((uint32_t)step == rec_next) {  // (step + 1) % rec_period == 0, record k = (step + 1) / rec_period - 1
+            const int k = rec_k;
+            rec_next += (uint32_t)rec_period;
+            ++rec_k;
+            if (k < (int)a.K) {
+                double* rk = a.rec + (int64_t)k * 6 * a.rec_stride;
+                rk[0 * a.rec_stride + pid] = x;
+                rk[1 * a.rec_stride + pid] = y;
+                rk[2 * a.rec_stride + pid] = z;
+                rk[3 * a.rec_stride + pid] = hx;
+                rk[4 * a.rec_stride + pid] = hy;
+                rk[5 * a.rec_stride + pid] = hz;
+            }
+        }
+    }
+    a.px[pid] = x; a.py[pid] = y; a.pz[pid] = z;
+    a.depth[pid] = dep;
+    a.cell[pid] = cell;
+    if (died >= 0) a.death[pid] = died;
+    // slots never sampled: after a death (traj_kernel)
+    if (died >= 0 || step_end == (int)a.n_steps) dev::clear_records(a.rec, a.rec_stride, pid, (rec_k == 0 && rec0) ? 1 : rec_k, a.K);
 }
 
 // ===========================================================================
@@ -3769,6 +3963,21 @@ void launch_traj(const TrajArgs& a, bool path, bool euler, hipStream_t s) {
     }
 }
 
+// MOPS_RK4_RELOCATE: the per-lane relocating kernel (pathlines only; no cooperative selection, no hand-off)
+static mops_status launch_traj_reloc(int maxv, const TrajArgs& a, hipStream_t s) {
+    const unsigned g = (unsigned)((a.n + kTrajBlock - 1) / kTrajBlock);
+    switch (maxv) {
+        case 7: traj_rk4_reloc_kernel<7><<<g, kTrajBlock, 0, s>>>(a); break;
+#if !defined(MOPS_ONLY7)
+        case 12: traj_rk4_reloc_kernel<12><<<g, kTrajBlock, 0, s>>>(a); break;
+        default: traj_rk4_reloc_kernel<20><<<g, kTrajBlock, 0, s>>>(a); break;
+#else
+        default: return fail(MOPS_ERR_UNSUPPORTED, "experiment build: MAXV 7 only");
+#endif
+    }
+    return MOPS_OK;
+}
+
 // launch_traj's pathline MAXV 7 branch with the CAP instantiations (a.cap set; mops_traj_advance_captured)
 static void launch_traj_cap(const TrajArgsCap& a, bool euler, hipStream_t s) {
     const unsigned g = (unsigned)((a.n + kTrajBlock - 1) / kTrajBlock);
@@ -4645,6 +4854,8 @@ static mops_status traj_advance_impl(const mops_mesh* mesh, const mops_field* fr
                                      int64_t step_end, double* d_records, int64_t record_stride, void* stream,
                                      const CapWindow* cw) {
     if (!mesh || !front || !cfg || !p) return fail(MOPS_ERR_INVALID, "mops_traj_advance: invalid inputs");
+    if (cfg->method == MOPS_RK4_RELOCATE && !back)  // (never silently the plain RK4)
+        return fail(MOPS_ERR_UNSUPPORTED, "mops_traj_advance: MOPS_RK4_RELOCATE is for pathlines only (back == NULL)");
     if (cfg->delta_t <= 0 || cfg->record_t <= 0 || cfg->simulation_duration <= 0)
         return fail(MOPS_ERR_INVALID, "invalid trajectory settings");  // :666-669
     const int64_t K = mops_traj_num_records(cfg), n_steps = mops_traj_num_steps(cfg);
@@ -4694,6 +4905,14 @@ static mops_status traj_advance_impl(const mops_mesh* mesh, const mops_field* fr
     const bool euler = (cfg->method == MOPS_EULER);
     hipStream_t s = (hipStream_t)stream;
     a.coop_sel = nullptr;
+    if (cfg->method == MOPS_RK4_RELOCATE) {  // (back != NULL: checked above)
+        if (cw) return fail(MOPS_ERR_UNSUPPORTED, "mops_traj_advance: no capture with MOPS_RK4_RELOCATE");
+        a.handoff = 0;
+        a.cap = nullptr; a.cap_stride = 0; a.cap_first = 0; a.cap_slots = 0;
+        MOPS_TRY(launch_traj_reloc(mesh->maxv, a, s));
+        HIP_TRY(hipGetLastError());
+        return MOPS_OK;
+    }
     if ((euler ? MOPS_COOP_PE : MOPS_COOP_PR) && back && mesh->maxv == 7 && !p->d_order) {
         int* sel = nullptr;
         MOPS_TRY(coop_flag(mesh, s, &sel));
@@ -4777,6 +4996,8 @@ static mops_status sample_check(const char* who, const mops_mesh* mesh, const mo
     const std::string w(who);
     if (!mesh || !front || !cfg || !p) return fail(MOPS_ERR_INVALID, w + ": invalid inputs");
     if (!back) return fail(MOPS_ERR_UNSUPPORTED, w + ": attributes are sampled along pathlines only (back == NULL)");
+    if (cfg->method == MOPS_RK4_RELOCATE)  // (the samplers evaluate every stage in the step's cell)
+        return fail(MOPS_ERR_UNSUPPORTED, w + ": attributes are not sampled with MOPS_RK4_RELOCATE");
     if (cfg->delta_t <= 0 || cfg->record_t <= 0 || cfg->simulation_duration <= 0)
         return fail(MOPS_ERR_INVALID, "invalid trajectory settings");
     const int64_t K = mops_traj_num_records(cfg), n_steps = mops_traj_num_steps(cfg);
@@ -5077,8 +5298,12 @@ static mops_status run_trajectories_impl(const mops_mesh* mesh, const mops_field
                                          const double* const* d_fa, const double* const* d_ba, double* h_attr_lines,
                                          void* stream) {
     if (!mesh || !front || !cfg) return fail(MOPS_ERR_INVALID, "invalid inputs");  // :659-662
+    if (cfg->method == MOPS_RK4_RELOCATE && !back)  // (never silently the plain RK4)
+        return fail(MOPS_ERR_UNSUPPORTED, "mops_run_trajectories: MOPS_RK4_RELOCATE is for pathlines only (back == NULL)");
     if (n_attr != 0) {
         if (!back) return fail(MOPS_ERR_UNSUPPORTED, "mops_run_pathline_attrs: attributes are sampled along pathlines only (back == NULL)");
+        if (cfg->method == MOPS_RK4_RELOCATE)
+            return fail(MOPS_ERR_UNSUPPORTED, "mops_run_pathline_attrs: attributes are not sampled with MOPS_RK4_RELOCATE");
         if (n_attr < 1 || n_attr > MOPS_MAX_SAMPLE_ATTRS || !d_fa || !d_ba || !h_attr_lines)
             return fail(MOPS_ERR_INVALID, "mops_run_pathline_attrs: n_attr must be 1.." +
                                               std::to_string(MOPS_MAX_SAMPLE_ATTRS) + " with its arrays and output");

@@ -42,7 +42,7 @@ class TrajectoryConfig:
     recordT: int = 3600
     depth: float = 0.0
     direction: int = L.MOPS_FORWARD
-    method: int = L.MOPS_EULER          # reference default (MPASOVisualizer.h:99)
+    method: int = L.MOPS_EULER          # reference default (MPASOVisualizer.h:99); L.MOPS_RK4_RELOCATE: pathlines only
 
     def ctype(self) -> L.TrajCfg:
         return L.TrajCfg(int(self.deltaT), int(self.simulationDuration), int(self.recordT), int(self.direction),
@@ -243,6 +243,7 @@ def run_trajectories(mesh: DeviceMesh, front: DeviceField, back: DeviceField | N
     cl = np.full(n, -1, dtype=np.int32) if cells is None else np.ascontiguousarray(cells, dtype=np.int32).copy()
     c = cfg.ctype()
     if attrs is not None:
+        _refuse_attrs_relocate(cfg, "run_trajectories")
         names = list(attrs)
         fa, ba = _attr_ptr_lists(mesh, [attrs[k][0] for k in names], [attrs[k][1] for k in names])
         lines = np.zeros((len(names), n, P))
@@ -269,6 +270,13 @@ def run_trajectories(mesh: DeviceMesh, front: DeviceField, back: DeviceField | N
 
 
 MAX_SAMPLE_ATTRS = 4  # MOPS_MAX_SAMPLE_ATTRS
+
+
+def _refuse_attrs_relocate(cfg: TrajectoryConfig, who: str):
+    """Attribute sampling evaluates every RK4 stage in the step's cell: refused with MOPS_RK4_RELOCATE, before
+    any launch (the C entries return MOPS_ERR_UNSUPPORTED)."""
+    if int(cfg.method) == L.MOPS_RK4_RELOCATE:
+        raise ValueError(f"{who}: attrs are not sampled with method MOPS_RK4_RELOCATE")
 
 
 def _attr_ptr_lists(mesh: DeviceMesh, front_list, back_list):
@@ -559,6 +567,7 @@ class ParticleSet:
         records, depths and death steps are those of the plain call."""
         p = self.particles() if live_count is None else self._sub_particles(0, self.n, live_count)
         if attrs is not None:
+            _refuse_attrs_relocate(self.cfg, "advance")
             if self.attr_records is None or len(attrs[0]) != self.n_attr:
                 raise ValueError("advance: attrs needs a particle set created with n_attr = the number of attributes")
             fa, ba = _attr_ptr_lists(self.mesh, list(attrs[0]), list(attrs[1]))
@@ -624,6 +633,7 @@ class ParticleSet:
             raise ValueError("advance_pipelined: not supported for a particle set with an attribute slab")
         fa = ba = None
         if attrs is not None:
+            _refuse_attrs_relocate(self.cfg, "advance_pipelined")
             if self.attr_records is None or len(attrs[0]) != self.n_attr:
                 raise ValueError("advance_pipelined: attrs needs a particle set created with n_attr = the number "
                                  "of attributes")

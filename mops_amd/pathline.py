@@ -139,8 +139,14 @@ class MOPSPathline:
         (M, 3), velocity (M, 3), temperature (M,), salinity (M,), lastPoint (3,).
         ``sample_attributes``: temperature / salinity are the snapshot files' fields of those names sampled
         along each line (PathlineChain.run(attrs=True)) instead of the reference's velocity x / y (quirk Q9);
-        a name the files do not carry stays zeros."""
+        a name the files do not carry stays zeros.
+        ``method``: "rk4" (the reference's, quirk Q1 included), "rk4_relocate" (this engine's RK4 that locates
+        each stage in its own cell, MOPS_RK4_RELOCATE: particles survive cell crossings; not with
+        ``sample_attributes``); any other string means Euler, as in the reference's caller."""
         from .chain import PathlineChain
+        meth = {"rk4": L.MOPS_RK4, "rk4_relocate": L.MOPS_RK4_RELOCATE}.get(method.lower(), L.MOPS_EULER)
+        if meth == L.MOPS_RK4_RELOCATE and sample_attributes:
+            raise ValueError('sample_attributes is not supported with method="rk4_relocate"')
         from .engine import DeviceField, DeviceMesh, cell_to_vertex_attr
         from .mpas import MPASOReader, mesh_from_reader, snapshot_from_reader
         if self.pairs is None:
@@ -175,7 +181,7 @@ class MOPSPathline:
         chain = PathlineChain(self._mesh, make_field, len(dates), timestamps=stamps, device=self.device,
                               make_attrs=make_attrs if sample_attributes else None)
         res = chain.run(seeds, depth=self._depth, particle_depths=pdep,
-                        method=L.MOPS_RK4 if method.lower() == "rk4" else L.MOPS_EULER,
+                        method=meth,
                         delta_t=int(delta_minutes) * self._one_min,
                         record_t=int(record_every_minutes) * self._one_min,
                         direction=L.MOPS_FORWARD if self.direction == "forward" else L.MOPS_BACKWARD,

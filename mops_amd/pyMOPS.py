@@ -276,6 +276,12 @@ class TrajectorySettings:
         # this engine's extension: MOPS_RunPathLine samples the first two attribute names, in sorted order, that
         # both active solutions carry, and returns them as temperature / salinity BY NAME (see MOPS_RunPathLine)
         self.sampleAttributes = False
+        # this engine's extension, the opt-out of quirk Q1: with methodType kRK4, MOPS_RunPathLine locates each RK4
+        # stage in its own cell (MOPS_RK4_RELOCATE, include/mops_traj.h) instead of evaluating it in the step's start
+        # cell, where a stage across a cell edge kills the particle.  No effect with kEuler (no stages).
+        # MOPS_RunStreamLine with it and kRK4, and MOPS_RunPathLine with it, kRK4 and sampleAttributes: Error() and
+        # an empty list.
+        self.relocateStages = False
 
     def hasPerParticleDepths(self) -> bool:
         return len(self.particle_depths) > 0
@@ -520,9 +526,18 @@ def _run(config: TrajectorySettings, sample_points_np, pathline: bool, stage: st
     if config.hasPerParticleDepths() and len(config.particle_depths) == len(seeds):
         depths = np.asarray(config.particle_depths, dtype=np.float32)
     eff = depths if depths is not None else np.full(len(seeds), np.float32(config.depth), dtype=np.float32)
+    method = int(config.methodType)
+    if getattr(config, "relocateStages", False) and method == int(CalcMethodType.kRK4):
+        if not pathline:
+            _error(f"[{stage}] relocateStages is for pathlines only")
+            return None, seeds, None
+        if getattr(config, "sampleAttributes", False):
+            _error(f"[{stage}] sampleAttributes is not supported with relocateStages")
+            return None, seeds, None
+        method = _L.MOPS_RK4_RELOCATE
     cfg = _E.TrajectoryConfig(deltaT=int(config.deltaT), simulationDuration=int(config.simulationDuration),
                               recordT=int(config.recordT), depth=float(np.float32(config.depth)),
-                              direction=int(config.directionType), method=int(config.methodType))
+                              direction=int(config.directionType), method=method)
     if cfg.n_records <= 0 or cfg.n_steps <= 0:
         _error(f"[{stage}] invalid integration steps")  # seed-only lines (:709-712)
         return "seed_only", seeds, eff
