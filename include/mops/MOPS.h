@@ -239,6 +239,16 @@ std::vector<TrajectoryLine> MOPS_RunPathLine(TrajectorySettings* config, std::ve
 // MOPSApp::runRemapping (MOPSApp.cpp:171-196): the fixed-depth images of the active front solution --
 // image 0 the ENU velocity, image 1 the first two double attributes when there are at least two
 std::vector<ImageBuffer<double>> MOPS_RunRemapping(VisualizationSettings* config);
+// Extension (the reference's only plot helper for lines is matplotlib, tutorial/pyMOPSAPI.py:132-289): the
+// particle density map of `lines` (what MOPS_RunStreamLine / MOPS_RunPathLine return) on the window config
+// gives -- imageSize, LatRange, LonRange -- binned on the GPU (mops_density_accumulate, mops_traj.h): every
+// point of every line lands in the pixel MOPS_RunRemapping's image has at its lat / lon.  One image
+// {count, mean, sum} (alpha 1), NaN where no sample fell, usable with SaveToPNG and SaveVTI.  value: ""
+// (count only), "speed" (|velocity|), "temperature" or "salinity" (the lines' vectors of that name).
+// Invalid inputs (null config, image size below 1, unknown value, empty or non-finite ranges, a longitude
+// range above 360): Error() and an empty image.
+ImageBuffer<double> MOPS_RunDensity(const std::vector<TrajectoryLine>& lines, VisualizationSettings* config,
+                                    const std::string& value = "");
 void MOPS_GenerateSamplePoints(SamplingSettings* config, std::vector<CartesianCoord>& sample_points);
 
 // SaveToPNG (src/Common/ImageBuffer.hpp:91-136) for the double image (the one instantiation the reference

@@ -571,6 +571,81 @@ mops_status mops_colormap_rgba8(const double* d_image, int32_t width, int32_t he
 mops_status mops_colormap_image(const double* h_image, int32_t width, int32_t height, int32_t channel_mask,
                                 uint8_t* h_rgba, float* h_minmax, void* stream);
 
+/* ---- particle density maps ------------------------------------------------ */
+
+/* How many trajectory samples fell into each lat / lon pixel of a window, and
+ * the sum of a value over them (no reference counterpart: its Vis_PathLines,
+ * tutorial/pyMOPSAPI.py:132-289, draws one matplotlib line per trajectory).
+ *
+ * A density accumulator belongs to a window: width, height, min_lat, max_lat,
+ * min_lon, max_lon of a mops_remap_cfg (the other members are ignored).  It is
+ * [height][width][2] 64-bit integers {count, qsum}, zeroed by the caller.
+ *
+ * A point (x, y, z) with r = sqrt(x*x + y*y + z*z) is skipped when a
+ * coordinate is not finite or r == 0 (the zero-filled record slots of a dead
+ * particle).  Otherwise
+ *   lat = asin(clamp(z / r, -1, 1)) * (180 / pi),  lon = atan2(y, x) * (180 / pi)
+ * (mops_lines_geo's expressions), lon -= 360 * floor((lon - min_lon) / 360)
+ * (so windows given as [-180, 180], [0, 360] or across the date line all
+ * work), and the pixel is the reference's inverse pixel map
+ * (GeoConverter.hpp:78-79, convertDegreeLatLonToPixel):
+ *   fr = (max_lat - lat) / (max_lat - min_lat) * height
+ *   fc = (lon - min_lon) / (max_lon - min_lon) * width
+ * The point is inside iff 0 <= fr < height and 0 <= fc < width; its pixel is
+ * (floor(fr), floor(fc)).  This inverts the remapping's pixel -> lat / lon
+ * map, so a density image overlays a mops_remap_fixed_depth image of the same
+ * settings.
+ *
+ * Value kinds: MOPS_DENSITY_COUNT -- no value, count += 1;
+ * MOPS_DENSITY_SPEED -- v = sqrt(vx*vx + vy*vy + vz*vz) of the velocity found
+ * at components 3..5 of the point's strides; MOPS_DENSITY_VALUES -- v read
+ * from d_values.  With a value, a non-finite v or |v| >= 2^38 skips the point
+ * entirely; otherwise q = llrint(v * 2^24) (ties to even) and the pixel gets
+ * count += 1, qsum += q.  Fixed point because integer sums are exact and order
+ * independent: the accumulator is the same bytes for every particle order,
+ * launch split, reorder and compaction, like every other result of this
+ * engine.  The resolution is 2^-24 (6e-8) in the value's unit.  qsum does not
+ * overflow while count * |v| < 2^39 per pixel (|q| <= 2^62 per point, so a
+ * single point always fits); past that bound it wraps. */
+enum { MOPS_DENSITY_COUNT = 0, MOPS_DENSITY_SPEED = 1, MOPS_DENSITY_VALUES = 2 };
+
+/* Bytes of a width x height accumulator (16 per pixel), or -1 for a size
+ * below 1 or width * height >= 2^31.  Host only. */
+int64_t mops_density_bytes(int32_t width, int32_t height);
+
+/* Bins points (k, i), k in [k_begin, k_end), i in [0, n): component c of
+ * point (k, i) is d_points[k*sk + i*si + c*sc].  A record slab [K][6][stride]
+ * is sk = 6*stride, si = 1, sc = stride (columns n .. stride-1, shard padding,
+ * are never read); a line array [n][P][3] is sk = 3, si = 3*P, sc = 1.
+ * d_seeds (optional, [n][3]) is one more point per particle, binned by a
+ * MOPS_DENSITY_COUNT call only: a seed carries no value, so a map of another
+ * kind leaves it out and its mean stays the mean of the sampled values (a
+ * chain passes the seeds for its first pair only, so no pair's first sample
+ * is counted twice).  MOPS_DENSITY_VALUES reads the value of point (k, i) at
+ * d_values[k*vk + i*vi] (row a of an attribute slab [K][n_attr][stride]:
+ * d_values = slab + a*stride, vk = n_attr*stride, vi = 1).  One lane per
+ * particle walks its records, keeps {pixel, count, qsum} in registers while
+ * the pixel stays the same and adds them to d_accum with 64-bit integer
+ * atomics when it changes.  Enqueues on `stream` and does not synchronise.
+ * MOPS_ERR_INVALID before any device work for a null cfg, d_points or
+ * d_accum, width or height < 1, width * height >= 2^31, non-finite or empty
+ * lat / lon ranges, max_lon - min_lon > 360, a negative n or k_begin, a bad
+ * kind, or MOPS_DENSITY_VALUES without d_values; MOPS_OK without a launch for
+ * n == 0 or k_end <= k_begin. */
+mops_status mops_density_accumulate(const mops_remap_cfg* cfg, int64_t n, int64_t k_begin, int64_t k_end,
+                                    const double* d_points, int64_t sk, int64_t si, int64_t sc,
+                                    const double* d_seeds, int32_t value_kind, const double* d_values, int64_t vk,
+                                    int64_t vi, void* d_accum, void* stream);
+
+/* An accumulator as an [height][width][4] float64 image (16-byte aligned):
+ * {count, mean = (qsum / 2^24) / count, qsum / 2^24, 1}.  With nan_empty != 0
+ * channels 0-2 of a pixel without samples are NaN, so mops_colormap_rgba8 /
+ * SaveToPNG leave it transparent; otherwise channels 0 and 2 are 0 there and
+ * the mean is NaN.  Enqueues on `stream` and does not synchronise; argument
+ * checks as mops_density_accumulate's for cfg, d_accum and d_image. */
+mops_status mops_density_image(const mops_remap_cfg* cfg, const void* d_accum, int32_t nan_empty, double* d_image,
+                               void* stream);
+
 /* Identity of the engine build: a hash of the engine's sources, headers,
  * compiler flags and ROCm version, stamped at compile time (no reference
  * counterpart).  The Python loader refuses a library whose id differs from

@@ -27,6 +27,7 @@ EXPORTED = (
     "mops_remove_nan_lines", "mops_remove_nan_ragged", "mops_run_trajectories", "mops_build_id",
     "mops_remap_num_images", "mops_remap_tables", "mops_remap_fixed_depth", "mops_remap_fixed_latitude",
     "mops_remap_fixed_layer", "mops_colormap_rgba8", "mops_colormap_image",
+    "mops_density_bytes", "mops_density_accumulate", "mops_density_image",
     # include/mops_io.h
     "mops_lines_geo", "mops_write_lines_vtp", "mops_write_lines_txt", "mops_write_pathline_binary",
     "mops_write_png_rgba8", "mops_write_images_vti", "mops_write_image_vti",
@@ -40,6 +41,7 @@ MOPS_FORWARD, MOPS_BACKWARD = 0, 1
 MOPS_RK4, MOPS_EULER = 0, 1
 MOPS_RK4_RELOCATE = 2  # pathline RK4 with each stage located in its own cell (the opt-out of quirk Q1; mops_traj.h)
 MOPS_LAYER_REFERENCE, MOPS_LAYER_BRACKET = 0, 1
+MOPS_DENSITY_COUNT, MOPS_DENSITY_SPEED, MOPS_DENSITY_VALUES = 0, 1, 2
 
 
 class MeshDesc(C.Structure):
@@ -191,6 +193,10 @@ def load(path: str | None = None):
     lib.mops_remap_fixed_layer.argtypes = [P, P, P, P, P, P]; lib.mops_remap_fixed_layer.restype = st
     lib.mops_colormap_rgba8.argtypes = [P, I32, I32, I32, P, P, P]; lib.mops_colormap_rgba8.restype = st
     lib.mops_colormap_image.argtypes = [P, I32, I32, I32, P, P, P]; lib.mops_colormap_image.restype = st
+    lib.mops_density_bytes.argtypes = [I32, I32]; lib.mops_density_bytes.restype = I64
+    lib.mops_density_accumulate.argtypes = [P, I64, I64, I64, P, I64, I64, I64, P, I32, P, I64, I64, P, P]
+    lib.mops_density_accumulate.restype = st
+    lib.mops_density_image.argtypes = [P, P, I32, P, P]; lib.mops_density_image.restype = st
     lib.mops_write_png_rgba8.argtypes = [C.c_char_p, I32, I32, P]; lib.mops_write_png_rgba8.restype = st
     lib.mops_write_images_vti.argtypes = [C.c_char_p, I32, I32, I32, P, P, P, P, I32]
     lib.mops_write_images_vti.restype = st

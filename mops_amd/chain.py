@@ -31,7 +31,8 @@ from datetime import datetime
 import numpy as np
 
 from . import _lib as L
-from .engine import MAX_SAMPLE_ATTRS, DeviceField, DeviceMesh, ParticleSet, TrajectoryConfig, cell_to_vertex_attr
+from .engine import (MAX_SAMPLE_ATTRS, DensityMap, DeviceField, DeviceMesh, ParticleSet, TrajectoryConfig,
+                     cell_to_vertex_attr)
 
 EARTH_RADIUS_M = 6_371_000.0  # pyMOPSAPI.py:46
 REORDER_SECONDS = 3 * 86400  # default launch length of long pairs (simulated time), see PathlineChain.run
@@ -150,7 +151,7 @@ class PathlineChain:
             compute_stream=None, on_pair=None, timing=None, segment_steps: int = -1, reorder: bool = True,
             record_stride: int | None = None, defer_lines: bool = False, compact: bool | None = None,
             compact_chunks: int = 6, on_lines=None, lines_chunk: int | None = None, attrs: bool = False,
-            capture_slots: int | None = None):
+            capture_slots: int | None = None, density=None):
         """Run all pairs; returns device tensors {points, velocity, temperature,
         salinity, lastPoint, death_step (of the last pair)} when ``keep_lines``,
         else only lastPoint/death_step.  ``on_pair(p, last, ps)`` is called after pair p
@@ -196,8 +197,25 @@ class PathlineChain:
         it.  ``capture_slots``: the window of the capture path (ParticleSet(capture_slots=)); None = the
         default (``DEFAULT_CAPTURE``: the longest pair's record count, one launch per existing boundary, or 0),
         0 = a launch boundary at every sample step.  Results are the same bytes for every value.  With
-        ``attrs`` False nothing changes: no ``attributes`` key, and temperature / salinity keep quirk Q9."""
+        ``attrs`` False nothing changes: no ``attributes`` key, and temperature / salinity keep quirk Q9.
+        ``density``: an engine.DensityMap or a list of them.  After each pair's last launch, on the compute
+        stream and before any slab swap, every map bins that pair's record slots [0, n_records) from the slab
+        (a count map also the seeds of pair 0, so no pair's first sample is counted twice): the whole chain's
+        samples as images, with no line leaving the device.  Works in every mode above (it is a parameter and
+        not an ``on_pair`` collector because an ``on_pair`` that reads the records is refused with ``attrs`` and
+        ``defer_lines``).  A map of an attribute needs ``attrs`` and a sampled name (ValueError before any
+        trajectory launch).  The maps are not reset here; None changes nothing."""
         import torch
+        maps = [] if density is None else (list(density) if isinstance(density, (list, tuple)) else [density])
+        for m in maps:
+            if not isinstance(m, DensityMap):
+                raise ValueError("density: a DensityMap or a list of them")
+            if m.attribute is not None:
+                if not attrs:
+                    raise ValueError(f"density: a map of the attribute {m.attribute!r} needs attrs=True")
+                given = getattr(self.make_attrs, "names", None)
+                if given and m.attribute not in sorted(given)[:MAX_SAMPLE_ATTRS]:
+                    raise ValueError(f"density: the chain samples no attribute {m.attribute!r}")
         if attrs and int(method) == L.MOPS_RK4_RELOCATE:
             raise ValueError("attrs: attributes are not sampled with MOPS_RK4_RELOCATE")
         if attrs and self.make_attrs is None:
@@ -269,6 +287,9 @@ class PathlineChain:
                 del names[MAX_SAMPLE_ATTRS:]
                 if not names or any(k not in attr_t[i] for k in names for i in (0, 1)):
                     raise ValueError("attrs=True: the snapshots share no attribute to sample")
+                for m in maps:
+                    if m.attribute is not None and m.attribute not in names:
+                        raise ValueError(f"density: the chain samples no attribute {m.attribute!r}")
             if overlap and self.n_snapshots > 2 and len(self.make_field.pool) < 1:
                 raise ValueError("overlap_stream needs a third field buffer in make_field.pool (seed the "
                                  "recycler with three fields and release them before the run)")
@@ -358,6 +379,8 @@ class PathlineChain:
                         e1.record(cs)
                         timing.append((e0, e1))
                 lists = None  # (the attribute tensors live as long as their fields, not until the next pair)
+                for m in maps:  # this pair's samples, from the slab the launches just wrote
+                    m.accumulate(ps, n_records=cfg.n_records, seeds=(p == 0), names=names, stream=cs.cuda_stream)
                 if defer_lines:
                     last = ps.last_points(stream=cs.cuda_stream)
                     done_ev = torch.cuda.Event()

@@ -492,6 +492,75 @@ std::vector<ImageBuffer<double>> MOPS_RunRemapping(VisualizationSettings* config
     return img_vec;
 }
 
+ImageBuffer<double> MOPS_RunDensity(const std::vector<TrajectoryLine>& lines, VisualizationSettings* config,
+                                    const std::string& value) {
+    ScopedTimer t("GPUKernel::Density", "GPUKernel");
+    const int W = config ? (int)config->imageSize.x : 0, H = config ? (int)config->imageSize.y : 0;
+    const int kind = value.empty() ? MOPS_DENSITY_COUNT : value == "speed" ? MOPS_DENSITY_SPEED : MOPS_DENSITY_VALUES;
+    if (config == nullptr || W <= 0 || H <= 0 ||
+        (kind == MOPS_DENSITY_VALUES && value != "temperature" && value != "salinity")) {
+        Error("[MI355X::Density] invalid inputs");
+        return ImageBuffer<double>(W > 0 ? W : 0, H > 0 ? H : 0);
+    }
+    mops_remap_cfg cfg{};
+    cfg.width = W; cfg.height = H;
+    cfg.min_lat = config->LatRange.x; cfg.max_lat = config->LatRange.y;
+    cfg.min_lon = config->LonRange.x; cfg.max_lon = config->LonRange.y;
+    const int64_t acc_bytes = mops_density_bytes(W, H);
+    ImageBuffer<double> img(W, H);
+    if (acc_bytes < 0) {
+        Error("[MI355X::Density] invalid image size");
+        return ImageBuffer<double>();
+    }
+    // lines [n][P][C] (C = 6 with the velocity behind the point for "speed"), shorter lines padded with NaN
+    // points, which the binning skips; values [n][P]
+    const size_t n = lines.size();
+    size_t P = 0;
+    for (const auto& ln : lines) P = std::max(P, ln.points.size());
+    const size_t C = kind == MOPS_DENSITY_SPEED ? 6 : 3;
+    const double nan = std::nan("");
+    std::vector<double> pts(n * P * C, nan), val(kind == MOPS_DENSITY_VALUES ? n * P : 0, nan);
+    for (size_t i = 0; i < n; ++i) {
+        const auto& ln = lines[i];
+        const auto& v = value == "temperature" ? ln.temperature : ln.salinity;
+        for (size_t k = 0; k < ln.points.size(); ++k) {
+            double* o = &pts[(i * P + k) * C];
+            std::memcpy(o, &ln.points[k], 3 * sizeof(double));
+            if (kind == MOPS_DENSITY_SPEED && k < ln.velocity.size()) std::memcpy(o + 3, &ln.velocity[k], 3 * sizeof(double));
+            if (kind == MOPS_DENSITY_VALUES && k < v.size()) val[i * P + k] = v[k];
+        }
+    }
+    struct DevBuf {
+        void* p = nullptr;
+        ~DevBuf() { (void)hipFree(p); }
+    } buf;
+    auto hip = [](hipError_t e, const char* what) {
+        if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+    };
+    // one allocation: image | accumulator | points | values
+    const size_t px = (size_t)W * H * 4;
+    hip(hipMalloc(&buf.p, px * sizeof(double) + (size_t)acc_bytes + (pts.size() + val.size() + 1) * sizeof(double)),
+        "MOPS_RunDensity: hipMalloc");
+    double* d_img = static_cast<double*>(buf.p);
+    void* d_acc = d_img + px;
+    double* d_pts = d_img + px + (size_t)acc_bytes / sizeof(double);
+    double* d_val = d_pts + pts.size();
+    hip(hipMemset(d_acc, 0, (size_t)acc_bytes), "MOPS_RunDensity: hipMemset");
+    if (!pts.empty()) hip(hipMemcpy(d_pts, pts.data(), pts.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy points");
+    if (!val.empty()) hip(hipMemcpy(d_val, val.data(), val.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy values");
+    mops_status st = mops_density_accumulate(&cfg, (int64_t)n, 0, (int64_t)P, d_pts, (int64_t)C, (int64_t)(C * P), 1, nullptr,
+                                             kind, kind == MOPS_DENSITY_VALUES ? d_val : nullptr, 1, (int64_t)P, d_acc,
+                                             nullptr);
+    if (st == MOPS_OK) st = mops_density_image(&cfg, d_acc, 1, d_img, nullptr);
+    if (st == MOPS_ERR_INVALID) {  // (the window: an empty or non-finite range)
+        Error("[MI355X::Density] %s", mops_last_error());
+        return ImageBuffer<double>();
+    }
+    check(st, "mops_density_accumulate");
+    hip(hipMemcpy(img.mPixels.data(), d_img, px * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy image");
+    return img;
+}
+
 void MPASOVisualizer::VisualizeFixedLayer(VisualizationSettings* config, ImageBuffer<double>* img) {
     ScopedTimer t("GPUKernel::FixedLayer", "GPUKernel");
     if (config == nullptr || img == nullptr || g_app.mesh == nullptr || g_app.front == nullptr) {  // :143-146

@@ -957,3 +957,111 @@ def colormap_rgba(image_cuda, channels=(0, 1, 2), return_minmax: bool = False, s
         L.check(L.load().mops_colormap_rgba8(C.c_void_p(t.data_ptr()), wid, hgt, mask, C.c_void_p(out.data_ptr()),
                                              _ptr(mm), _stream_handle(h)), "mops_colormap_rgba8")
     return (out, mm[channels]) if return_minmax else out
+
+
+DENSITY_KINDS = {None: L.MOPS_DENSITY_COUNT, "speed": L.MOPS_DENSITY_SPEED}
+
+
+class DensityMap:
+    """A particle density map (mops_density_accumulate, include/mops_traj.h): how many trajectory samples fell
+    into each lat / lon pixel of a ``width`` x ``height`` window, and the fixed-point sum of a value over them.
+
+    ``value``: None (count only), "speed" (the record's |velocity|) or an attribute name (the matching row of
+    a ParticleSet's attribute slab; ``names`` of the sampled attributes are given to ``accumulate``).
+    ``accum`` is the raw int64 CUDA tensor [height, width, 2] = {count, qsum}: integer sums, so the same bytes
+    for every particle order and launch split.  ``image()`` turns it into an [height, width, 4] float64 image
+    {count, mean, sum, 1} for ``colormap_rgba`` and the PNG / VTI writers."""
+
+    def __init__(self, width: int, height: int, lat_range, lon_range, value: str | None = None, device=None):
+        import torch
+        if value is not None and not isinstance(value, str):
+            raise ValueError("DensityMap: value must be None, 'speed' or an attribute name")
+        width, height = int(width), int(height)
+        lat, lon = (float(lat_range[0]), float(lat_range[1])), (float(lon_range[0]), float(lon_range[1]))
+        if width < 1 or height < 1 or width * height >= 2 ** 31:
+            raise ValueError(f"invalid image size {width} x {height}")
+        if not (np.isfinite(lat).all() and np.isfinite(lon).all() and lat[1] > lat[0] and lon[1] > lon[0]
+                and lon[1] - lon[0] <= 360.0):
+            raise ValueError(f"invalid latitude / longitude range {lat} / {lon}")
+        self.torch = torch
+        self.width, self.height, self.lat_range, self.lon_range, self.value = width, height, lat, lon, value
+        self.kind = DENSITY_KINDS.get(value, L.MOPS_DENSITY_VALUES)
+        self.cfg = _remap_cfg(width, height, lat, lon)
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.accum = torch.zeros((height, width, 2), dtype=torch.int64, device=self.device)
+
+    @property
+    def attribute(self):
+        """The attribute name this map averages, or None for a count or speed map."""
+        return self.value if self.kind == L.MOPS_DENSITY_VALUES else None
+
+    def reset(self):
+        self.accum.zero_()
+
+    def _stream(self, stream):
+        return stream if stream is not None else self.torch.cuda.current_stream(self.device).cuda_stream
+
+    def _call(self, n, k0, k1, points_ptr, sk, si, sc, seeds_ptr, values_ptr, vk, vi, stream):
+        with self.torch.cuda.device(self.device):
+            L.check(L.load().mops_density_accumulate(
+                C.byref(self.cfg), int(n), int(k0), int(k1), C.c_void_p(points_ptr), int(sk), int(si), int(sc),
+                None if seeds_ptr is None else C.c_void_p(seeds_ptr), self.kind,
+                None if values_ptr is None else C.c_void_p(values_ptr), int(vk), int(vi),
+                C.c_void_p(self.accum.data_ptr()), _stream_handle(self._stream(stream))), "mops_density_accumulate")
+
+    def accumulate(self, ps: "ParticleSet", n_records: int | None = None, seeds: bool = False, names=None,
+                   record_range=None, stream=None):
+        """Bin record slots [0, n_records) (default ``ps.K``; or ``record_range`` = (k_begin, k_end)) of every
+        particle of ``ps`` from its record slab, on ``stream`` (default torch's current one), without a host
+        synchronisation.  ``seeds``: also the particles' seeds (count maps only: a seed carries no value).
+        A map of an attribute reads that attribute's row of ``ps.attr_records``: ``names`` lists the sampled
+        attributes in slab order (PathlineChain passes its own; default salinity, temperature -- std::map
+        order -- cut to ``ps.n_attr``)."""
+        k0, k1 = (0, ps.K if n_records is None else int(n_records)) if record_range is None else map(int, record_range)
+        if k0 < 0 or k1 > ps.records.shape[0]:
+            raise ValueError(f"record range [{k0}, {k1}) outside the slab's {ps.records.shape[0]} slots")
+        vptr, vk = None, 0
+        if self.kind == L.MOPS_DENSITY_VALUES:
+            names = list(names) if names is not None else ["salinity", "temperature"][:ps.n_attr]
+            if ps.attr_records is None or self.value not in names or names.index(self.value) >= ps.n_attr:
+                raise ValueError(f"DensityMap: the particle set samples no attribute {self.value!r}")
+            vptr = ps.attr_records.data_ptr() + 8 * names.index(self.value) * ps.rec_stride
+            vk = ps.n_attr * ps.rec_stride
+        self._call(ps.n, k0, k1, ps.records.data_ptr(), 6 * ps.rec_stride, 1, ps.rec_stride,
+                   ps.seeds.data_ptr() if seeds else None, vptr, vk, 1, stream)
+
+    def accumulate_lines(self, points, values=None):
+        """Bin every point of [n, P, 3] lines (CUDA tensor or host array) on torch's current stream; ``values``
+        [n, P] for a map of an attribute, velocities [n, P, 3] for a speed map."""
+        torch = self.torch
+        pts = torch.as_tensor(points, dtype=torch.float64).to(self.device).contiguous()
+        if pts.dim() != 3 or pts.shape[2] != 3:
+            raise ValueError("accumulate_lines: points must be [n, P, 3]")
+        n, P = int(pts.shape[0]), int(pts.shape[1])
+        if self.kind == L.MOPS_DENSITY_COUNT:
+            self._call(n, 0, P, pts.data_ptr(), 3, 3 * P, 1, None, None, 0, 0, None)
+            return
+        if values is None:
+            raise ValueError("accumulate_lines: this map needs values")
+        val = torch.as_tensor(values, dtype=torch.float64).to(self.device).contiguous()
+        if self.kind == L.MOPS_DENSITY_SPEED:
+            if tuple(val.shape) != (n, P, 3):
+                raise ValueError("accumulate_lines: a speed map needs velocities [n, P, 3]")
+            both = torch.cat([pts, val], dim=2).contiguous()  # [n][P][6]: the velocity at components 3..5
+            self._call(n, 0, P, both.data_ptr(), 6, 6 * P, 1, None, None, 0, 0, None)
+            return
+        if tuple(val.shape) != (n, P):
+            raise ValueError("accumulate_lines: values must be [n, P]")
+        self._call(n, 0, P, pts.data_ptr(), 3, 3 * P, 1, None, val.data_ptr(), 1, P, None)
+
+    def image(self, nan_empty: bool = True, stream=None):
+        """The accumulator as a float64 CUDA image [height, width, 4] = {count, mean, sum, 1}
+        (mops_density_image); ``nan_empty``: pixels without samples are NaN in channels 0-2 (transparent in
+        ``colormap_rgba``), else count and sum are 0 there and only the mean is NaN."""
+        torch = self.torch
+        with torch.cuda.device(self.device):
+            img = torch.empty((self.height, self.width, 4), dtype=torch.float64, device=self.device)
+            L.check(L.load().mops_density_image(C.byref(self.cfg), C.c_void_p(self.accum.data_ptr()),
+                                                1 if nan_empty else 0, C.c_void_p(img.data_ptr()),
+                                                _stream_handle(self._stream(stream))), "mops_density_image")
+        return img

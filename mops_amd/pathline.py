@@ -133,7 +133,7 @@ class MOPSPathline:
         return self._last_pt.copy()
 
     def run(self, method: str = "rk4", delta_minutes: int = 1, record_every_minutes: int = 6,
-            sample_attributes: bool = False) -> list:
+            sample_attributes: bool = False, density=None) -> list:
         """All month pairs as one device-resident chain; the per-pair lines concatenated (later pairs
         without their first sample), pyMOPSAPI.py:1396-1531.  Returns list[dict] with lineID, points
         (M, 3), velocity (M, 3), temperature (M,), salinity (M,), lastPoint (3,).
@@ -142,7 +142,9 @@ class MOPSPathline:
         a name the files do not carry stays zeros.
         ``method``: "rk4" (the reference's, quirk Q1 included), "rk4_relocate" (this engine's RK4 that locates
         each stage in its own cell, MOPS_RK4_RELOCATE: particles survive cell crossings; not with
-        ``sample_attributes``); any other string means Euler, as in the reference's caller."""
+        ``sample_attributes``); any other string means Euler, as in the reference's caller.
+        ``density``: an engine.DensityMap or a list of them, filled with every pair's samples on the device
+        (PathlineChain.run(density=...)); a map of "temperature" / "salinity" needs ``sample_attributes``."""
         from .chain import PathlineChain
         meth = {"rk4": L.MOPS_RK4, "rk4_relocate": L.MOPS_RK4_RELOCATE}.get(method.lower(), L.MOPS_EULER)
         if meth == L.MOPS_RK4_RELOCATE and sample_attributes:
@@ -185,7 +187,7 @@ class MOPSPathline:
                         delta_t=int(delta_minutes) * self._one_min,
                         record_t=int(record_every_minutes) * self._one_min,
                         direction=L.MOPS_FORWARD if self.direction == "forward" else L.MOPS_BACKWARD,
-                        follow_last=self._follow_last, attrs=bool(sample_attributes))
+                        follow_last=self._follow_last, attrs=bool(sample_attributes), density=density)
         out = {k: res[k].cpu().numpy() for k in ("points", "velocity", "temperature", "salinity", "lastPoint")}
         self._last_pt = out["lastPoint"].astype(float, copy=True)
         if self._particle_depths is not None:  # :1491-1495

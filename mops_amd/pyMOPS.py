@@ -22,6 +22,8 @@ and, beyond the pybind module, the image output of the reference's C++ side:
     SaveVTI(images, config, names, outputName) VTKFileManager::SaveVTI (src/IO/VTKFileManager.hpp:25-138)
     MOPS_RunRemappingFixedLayer(config)        extension: Kernel::VisualizeFixedLayer, which MOPS_RunRemapping
                                                never reaches (MOPSApp.cpp:192)
+    MOPS_RunDensity(lines, config, value=None) extension: the particle density map of returned lines,
+                                               (H, W, 4) float64 {count, mean, sum, 1}
 
 Every trajectory and every image goes through the HIP engine
 (``engine.run_trajectories`` / ``engine.remap_fixed_depth`` /
@@ -639,6 +641,44 @@ def MOPS_RunRemappingFixedLayer(config: VisualizationSettings):
         image = _E.remap_fixed_layer(_app.mesh, _app.front, w, h, config.LatRange, config.LonRange,
                                      float(config.FixedLayer))
         return image.cpu().numpy()
+
+
+def MOPS_RunDensity(lines, config: VisualizationSettings, value=None):
+    """Extension (the reference's own plot helper, Vis_PathLines in tutorial/pyMOPSAPI.py:132-289, draws one
+    matplotlib line per trajectory): the particle density map of ``lines`` -- the list[dict] MOPS_RunStreamLine /
+    MOPS_RunPathLine return -- on the window ``config`` gives (imageSize, LatRange, LonRange), binned on the
+    GPU (engine.DensityMap): one [H, W, 4] float64 array {count, mean, sum, 1} with NaN where no sample fell,
+    usable with SaveToPNG and SaveVTI as MOPS_RunRemapping's images are.  Every point of every line is binned;
+    ``value``: None (count only), "speed" (|velocity|), "temperature" or "salinity" (the lines' entries of
+    that name).  Invalid inputs: Error() and an empty image, as MOPS_RunReGrid."""
+    with _Timer("GPUKernel::Density", "GPUKernel"):
+        w, h = (int(config.imageSize[0]), int(config.imageSize[1])) if config is not None else (0, 0)
+        key = {None: None, "": None, "speed": "velocity", "temperature": "temperature", "salinity": "salinity"}
+        lines = list(lines) if lines is not None else None
+        if (config is None or lines is None or w <= 0 or h <= 0 or value not in key
+                or any("points" not in ln or (key[value] is not None and key[value] not in ln) for ln in lines)):
+            _error("[MI355X::Density] invalid inputs")
+            return np.zeros((max(h, 0), max(w, 0), 4))
+        try:
+            dmap = _E.DensityMap(w, h, config.LatRange, config.LonRange, value=value or None)
+        except ValueError as e:
+            _error(f"[MI355X::Density] {e}")
+            return np.zeros((h, w, 4))
+        n = len(lines)
+        P = max([np.asarray(ln["points"]).reshape(-1, 3).shape[0] for ln in lines], default=0)
+        if n and P:
+            # lines of unequal length are padded with NaN points, which the binning skips
+            pts = np.full((n, P, 3), np.nan)
+            val = None if key[value] is None else np.full((n, P, 3) if value == "speed" else (n, P), np.nan)
+            for i, ln in enumerate(lines):
+                q = np.asarray(ln["points"], dtype=np.float64).reshape(-1, 3)
+                pts[i, :q.shape[0]] = q
+                if val is not None:
+                    v = np.asarray(ln[key[value]], dtype=np.float64).reshape((-1, 3) if value == "speed" else (-1,))
+                    m = min(q.shape[0], v.shape[0])
+                    val[i, :m] = v[:m]
+            dmap.accumulate_lines(pts, val)
+        return dmap.image(nan_empty=True).cpu().numpy()
 
 
 def SaveToPNG(image, filename: str, channel: int = 3) -> bool:
