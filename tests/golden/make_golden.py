@@ -10,7 +10,8 @@
    (test/test_gaussian.cpp:9-27): x = {4.75, 0.5, 6.0}, tol 1e-6.
 3. oracle_small.npz -- outputs of the CPU oracle on a small synthetic case
    (regression vectors for the oracle and the GPU engine; NOT a reference
-   pin -- the reference cannot be built here).
+   pin -- that is reference_pin.npz, which make_reference_pin.py records
+   from the reference's compiled CPU kernels).
 
 Run: python tests/golden/make_golden.py
 """

@@ -1,0 +1,488 @@
+"""Cases for the reference pin: the files the compiled reference driver (oracle/ref/ref_driver.cpp) reads and
+writes, the catalogue of cases shared by tests/test_reference_pin.py, tests/test_reference_pin_gpu.py and
+tests/golden/make_reference_pin.py, and the digests stored in tests/golden/reference_pin.npz.
+
+TEST INFRASTRUCTURE ONLY: the product never imports this module.
+
+Container format (both directions, little-endian): ``MOPSREF1``, u32 count, then per array u32 name length,
+name, u32 dtype (0 f64, 1 i64, 2 f32, 3 i32), u32 ndim, u64 dims[ndim], raw data.
+"""
+import collections
+import functools
+import hashlib
+import json
+import os
+import struct
+import subprocess
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DRIVER = os.path.join(ROOT, "oracle", "_ref", "mops_ref_driver")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_pin.npz")
+MAGIC = b"MOPSREF1"
+_DTYPES = {0: np.dtype("<f8"), 1: np.dtype("<i8"), 2: np.dtype("<f4"), 3: np.dtype("<i4")}
+_CODES = {v: k for k, v in _DTYPES.items()}
+OPS = dict(preprocess=0, locate=1, streamline=2, pathline=3, fixed_depth=4, fixed_latitude=5, fixed_layer=6,
+           remove_nan=7)
+
+
+# ---- files ------------------------------------------------------------------------------------------------
+def write_bag(path, arrays):
+    with open(path, "wb") as f:
+        f.write(MAGIC + struct.pack("<I", len(arrays)))
+        for name, a in arrays.items():
+            a = np.ascontiguousarray(a)
+            a = a.astype(a.dtype.newbyteorder("<"), copy=False)
+            nm = name.encode()
+            f.write(struct.pack("<I", len(nm)) + nm + struct.pack("<II", _CODES[a.dtype], a.ndim))
+            f.write(struct.pack(f"<{a.ndim}Q", *a.shape))
+            f.write(a.tobytes())
+
+
+def read_bag(path):
+    out = {}
+    with open(path, "rb") as f:
+        buf = f.read()
+    assert buf[:8] == MAGIC, "not a driver file"
+    (count,), o = struct.unpack_from("<I", buf, 8), 12
+    for _ in range(count):
+        (ln,) = struct.unpack_from("<I", buf, o); o += 4
+        name = buf[o:o + ln].decode(); o += ln
+        code, ndim = struct.unpack_from("<II", buf, o); o += 8
+        dims = struct.unpack_from(f"<{ndim}Q", buf, o); o += 8 * ndim
+        dt = _DTYPES[code]
+        n = int(np.prod(dims, dtype=np.int64)) if ndim else 1
+        out[name] = np.frombuffer(buf, dtype=dt, count=n, offset=o).reshape(dims).copy(); o += n * dt.itemsize
+    assert o == len(buf), "trailing bytes in driver file"
+    return out
+
+
+def _i64(a):
+    return np.ascontiguousarray(np.asarray(a).astype(np.int64))
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def mesh_arrays(mesh):
+    a = {"mesh/cellCoord": _f64(mesh.cellCoord).reshape(-1, 3), "mesh/vertexCoord": _f64(mesh.vertexCoord).reshape(-1, 3),
+         "mesh/nEdgesOnCell": _i64(mesh.nEdgesOnCell), "mesh/verticesOnCell": _i64(mesh.verticesOnCell),
+         "mesh/cellsOnCell": _i64(mesh.cellsOnCell), "mesh/cellsOnVertex": _i64(mesh.cellsOnVertex),
+         "mesh/refBottomDepth": _f64(mesh.refBottomDepth),
+         "mesh/sizes": np.array([mesh.maxEdges, mesh.nVertLevels], dtype=np.int64)}
+    if mesh.edgesOnCell is not None:
+        a.update({"mesh/edgesOnCell": _i64(mesh.edgesOnCell), "mesh/cellsOnEdge": _i64(mesh.cellsOnEdge),
+                  "mesh/edgeCoord": _f64(mesh.edgeCoord).reshape(-1, 3)})
+    return a
+
+
+def snapshot_arrays(snap, prefix, attributes=None):
+    a = {prefix + k: _f64(getattr(snap, k)) for k in ("layerThickness", "bottomDepth", "zonalVelocity",
+                                                      "meridionalVelocity", "vertVelocityTop")}
+    for name in (sorted(snap.attributes) if attributes is None else attributes):
+        a[prefix + "attr/" + name] = _f64(snap.attributes[name])
+    return a
+
+
+def op_arrays(k, op):
+    """One operation's arrays: ``op`` is a dict with "op" (a key of OPS) and that operation's inputs."""
+    p = f"op{k}/"
+    a = {p + "op": np.array([OPS[op["op"]]], dtype=np.int64)}
+    kind = op["op"]
+    if kind == "locate":
+        a[p + "points"] = _f64(op["points"]).reshape(-1, 3)
+    elif kind in ("streamline", "pathline"):
+        a[p + "seeds"] = _f64(op["seeds"]).reshape(-1, 3)
+        a[p + "settings"] = np.array([op["delta_t"], op["duration"], op["record_t"], int(op["backward"]),
+                                      int(op["euler"])], dtype=np.int64)
+        a[p + "depth"] = np.array([op.get("depth", 0.0)], dtype=np.float32)
+        if op.get("depths") is not None:
+            a[p + "particle_depths"] = np.ascontiguousarray(op["depths"], dtype=np.float32)
+    elif kind in ("fixed_depth", "fixed_latitude", "fixed_layer"):
+        (lat, lon) = op["window"]
+        a[p + "size"] = np.array([op["width"], op["height"]], dtype=np.int64)
+        a[p + "window"] = np.array([lat[0], lat[1], lon[0], lon[1]], dtype=np.float64)
+        a[p + "value"] = np.array([op["value"]], dtype=np.float64)
+    elif kind == "remove_nan":
+        lines = op["lines"]
+        a[p + "counts"] = np.array([[len(l[k]) for k in ("points", "velocity", "temperature", "salinity")]
+                                    for l in lines], dtype=np.int64).reshape(-1, 4)
+        a[p + "lineID"] = np.array([l["lineID"] for l in lines], dtype=np.int64)
+        for k, w in (("points", 3), ("velocity", 3)):
+            a[p + k] = np.concatenate([_f64(l[k]).reshape(-1, w) for l in lines]).reshape(-1, w)
+        for k in ("temperature", "salinity"):
+            a[p + k] = np.concatenate([_f64(l[k]).reshape(-1) for l in lines])
+    return a
+
+
+def run_driver(driver, mesh, snaps, ops, attributes=None):
+    """Run the compiled reference on one mesh (None for mesh-free operations), its snapshots and ``ops``;
+    returns one dict of output arrays per operation."""
+    arrays = {"n_ops": np.array([len(ops)], dtype=np.int64)}
+    if mesh is not None:
+        arrays.update(mesh_arrays(mesh))
+        for k, s in enumerate(snaps):
+            arrays.update(snapshot_arrays(s, f"s{k}/", attributes))
+    for k, op in enumerate(ops):
+        arrays.update(op_arrays(k, op))
+    with tempfile.TemporaryDirectory(prefix="mops_ref_") as tmp:
+        case, result = os.path.join(tmp, "case.bin"), os.path.join(tmp, "result.bin")
+        write_bag(case, arrays)
+        r = subprocess.run([driver, case, result, tmp], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
+        assert r.returncode == 0, f"reference driver failed ({r.returncode}): {r.stderr[-2000:]}"
+        bag = read_bag(result)
+    out = []
+    for k in range(len(ops)):
+        p = f"op{k}/"
+        out.append({n[len(p):]: v for n, v in bag.items() if n.startswith(p)})
+    return out
+
+
+def lines_from_result(res):
+    """The driver's ragged TrajectoryLine fields as rectangular arrays (every line of one run has the same
+    number of points after the reference's RemoveNaNTrajectoriesAndReindex; asserted)."""
+    counts = res["counts"]
+    n = counts.shape[0]
+    assert n > 0 and (counts == counts[0, 0]).all(), "lines of unequal length"
+    P = int(counts[0, 0])
+    assert np.array_equal(res["lineID"], np.arange(n)), "lineID is not the line order"
+    return dict(points=res["points"].reshape(n, P, 3), velocity=res["velocity"].reshape(n, P, 3),
+                temperature=res["temperature"].reshape(n, P), salinity=res["salinity"].reshape(n, P),
+                lastPoint=res["lastPoint"].reshape(n, 3), depth=res["depth"].reshape(n),
+                cells=res["cells"].astype(np.int64))
+
+
+# ---- the catalogue ----------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def world(key):
+    """(mesh, snapshot 0, snapshot 1) of one catalogue mesh, built from mops_amd.synth with fixed seeds."""
+    from mops_amd import synth
+    if key in ("small", "small_z"):
+        mesh = synth.make_mesh(16, n_levels=10) if key == "small" else world("small")[0]
+        topo = "sigma" if key == "small" else "zlevel"
+    elif key == "hept":
+        mesh, topo = synth.make_mesh(16, n_levels=10, flips=40), "sigma"
+    elif key == "edges10":
+        mesh, topo = synth.make_mesh(16, n_levels=10, max_edges=10), "sigma"
+    else:
+        raise KeyError(key)
+    return (mesh, synth.make_snapshot(mesh, timestep=0, phase=0.0, topography=topo),
+            synth.make_snapshot(mesh, timestep=1, phase=0.35, topography=topo))
+
+
+WORLDS = ("small", "small_z", "hept", "edges10")
+Traj = collections.namedtuple("Traj", "world pathline euler backward seeds depth depths delta_t duration record_t")
+
+
+def dense_seeds(mesh, zlevel):
+    """The seeds and depths of test_gpu_parity.test_pathline_cooperative_waves: 14 cells with 45..58 particles
+    each at one or two depths, and 37 band seeds, some of them on land."""
+    from mops_amd import synth
+    rng = np.random.default_rng(41)
+    cc = np.asarray(mesh.cellCoord, dtype=np.float64).reshape(-1, 3)
+    cells = rng.choice(mesh.nCells, 14, replace=False)
+    seeds, depths = [], []
+    for j, c in enumerate(cells):
+        k = 45 + j
+        u = cc[c] / np.linalg.norm(cc[c])
+        jit = rng.normal(size=(k, 3)) * 2.0e4
+        p = u + (jit - np.outer(jit @ u, u)) / 6.371e6
+        seeds.append(p / np.linalg.norm(p, axis=1, keepdims=True) * 6.37101e6)
+        d = np.full(k, 300.0) if j < 7 else np.where(np.arange(k) % 2 == 0, 300.0, 1100.0)
+        if zlevel:
+            d = np.where(np.arange(k) % 3 == 0, 1450.0 + 10.0 * j, d)
+        depths.append(d)
+    seeds.append(synth.uniform_band_seeds(400, seed=3)[:37]); depths.append(np.full(37, 500.0))
+    return np.concatenate(seeds), np.concatenate(depths).astype(np.float32)
+
+
+def edge_seeds(mesh, count=100):
+    """Seeds that lie, in floating point, exactly on a cell edge's plane: dot(cross(a, b), p) == 0.0 for one
+    edge (a, b) of the seed's own cell and >= 0 for the others, with IsInMesh's operation order.  IsInMesh's
+    `< 0` keeps them inside; a `<= 0` would kill them at step 0.  Candidates are the chord midpoints of each cell's
+    edges (a vertex itself has no Wachspress weights); only seeds whose nearest cell centre is unique and is that cell are kept."""
+    me = mesh.maxEdges
+    voc = np.asarray(mesh.verticesOnCell).reshape(-1, me).astype(np.int64) - 1
+    nv = np.asarray(mesh.nEdgesOnCell).astype(np.int64)
+    vc = np.asarray(mesh.vertexCoord, dtype=np.float64).reshape(-1, 3)
+    cc = np.asarray(mesh.cellCoord, dtype=np.float64).reshape(-1, 3)
+    out = []
+    for c in range(mesh.nCells):
+        poly = vc[voc[c, :nv[c]]]
+        nxt = np.roll(poly, -1, axis=0)
+        n = np.stack([poly[:, 1] * nxt[:, 2] - poly[:, 2] * nxt[:, 1], poly[:, 2] * nxt[:, 0] - poly[:, 0] * nxt[:, 2],
+                      poly[:, 0] * nxt[:, 1] - poly[:, 1] * nxt[:, 0]], axis=-1)
+        for p in 0.5 * (poly + nxt):
+            d = (n[:, 0] * p[0] + n[:, 1] * p[1]) + n[:, 2] * p[2]
+            if (d >= 0.0).all() and (d == 0.0).any():
+                d2 = np.sort(((cc - p) ** 2).sum(-1))[:2]
+                if d2[1] > d2[0] and ((cc[c] - p) ** 2).sum() == d2[0]:
+                    out.append(p)
+                    break
+        if len(out) == count:
+            break
+    assert len(out) == count, len(out)
+    return np.array(out)
+
+
+@functools.lru_cache(maxsize=None)
+def seed_set(name, world_key):
+    """(seeds [N, 3], per-particle float32 depths or None)."""
+    from mops_amd import synth
+    if name == "band300":       # ~10 % of the band is culled land: those seeds die at step 0
+        return synth.uniform_band_seeds(300, seed=5), None
+    if name == "band300_depths":
+        rng = np.random.default_rng(77)
+        return synth.uniform_band_seeds(300, seed=5), rng.choice([50.0, 300.0, 1100.0, 2500.0], 300).astype(np.float32)
+    if name == "band200":       # test_record_rules_odd_periods
+        return synth.uniform_band_seeds(200, seed=21), None
+    if name == "edge":          # 100 seeds exactly on an edge plane of their cell, and 100 band seeds
+        return np.concatenate([edge_seeds(world(world_key)[0]), synth.uniform_band_seeds(100, seed=5)]), None
+    if name == "dense":
+        return dense_seeds(world(world_key)[0], world_key == "small_z")
+    raise KeyError(name)
+
+
+def _traj_cases():
+    cases = collections.OrderedDict()
+    for kind in ("streamline", "pathline"):
+        for method in ("euler", "rk4"):
+            for direction in ("forward", "backward"):
+                for dep in ("uniform", "depths"):
+                    cases[f"small_{kind}_{method}_{direction}_{dep}"] = Traj(
+                        "small", kind == "pathline", method == "euler", direction == "backward",
+                        "band300" if dep == "uniform" else "band300_depths", 800.0, None, 120, 43200, 3600)
+    cases["zlevel_pathline_euler_dense"] = Traj("small_z", True, True, False, "dense", 0.0, None, 120, 43200, 3600)
+    cases["zlevel_streamline_rk4"] = Traj("small_z", False, False, False, "band300_depths", 0.0, None, 120, 43200, 3600)
+    cases["hept_streamline_euler"] = Traj("hept", False, True, False, "band300", 500.0, None, 120, 43200, 3600)
+    cases["hept_pathline_rk4"] = Traj("hept", True, False, True, "band300_depths", 0.0, None, 120, 43200, 3600)
+    cases["small_edge_streamline_euler"] = Traj("small", False, True, False, "edge", 300.0, None, 120, 43200, 3600)
+    golden = list(cases)
+    cases["edge_pathline_rk4"] = Traj("small", True, False, False, "edge", 300.0, None, 120, 43200, 3600)
+    # recordT no multiple of deltaT (test_record_rules_odd_periods): 24 records over 60 steps
+    cases["odd_streamline"] = Traj("small", False, True, False, "band200", 100.0, None, 120, 7200, 300)
+    cases["odd_pathline"] = Traj("small", True, True, False, "band200", 100.0, None, 120, 7200, 300)
+    cases["dense_pathline_euler"] = Traj("small", True, True, False, "dense", 0.0, None, 120, 43200, 3600)
+    cases["dense_pathline_rk4_backward"] = Traj("small", True, False, True, "dense", 0.0, None, 120, 43200, 3600)
+    cases["edges10_pathline_rk4"] = Traj("edges10", True, False, False, "band300", 300.0, None, 120, 43200, 3600)
+    return cases, golden
+
+
+TRAJ_CASES, GOLDEN_TRAJ = _traj_cases()
+LINE_FIELDS = ("points", "velocity", "temperature", "salinity", "lastPoint", "depth", "cells")
+
+GLOBAL = ((-90.0, 90.0), (-180.0, 180.0))
+BOX = ((-60.0, 60.0), (-170.0, 150.0))
+# tests/test_remap_gpu.py's CASES: (width, height, (lat range, lon range), depth)
+DEPTH_CASES = {
+    "global_800": (48, 24, GLOBAL, 800.0),
+    "box_0": (40, 32, BOX, 0.0),
+    "box_2500": (40, 32, BOX, 2500.0),
+    "odd_300": (37, 23, ((-75.0, 80.0), (-180.0, 175.0)), 300.0),
+}
+# test_remap_gpu.test_fixed_latitude_bit_exact's image, and a second latitude on a window of another size
+LATITUDE_CASES = {"lat_20": (36, 20, (-170.0, 150.0), 20.0), "lat_m35": (29, 17, (-180.0, 175.0), -35.0)}
+# tests/test_image_gpu.py: FixedLayer -> the layer ClampLayer gives with 10 levels, on two of the windows
+LAYERS = ((0, 0), (4, 4), (2.9, 2), (-3, 0), (99, 9))
+LAYER_WINDOWS = ("global_800", "box_0")
+# Fixed depth has no golden image: the compiled reference leaves those images unwritten (see
+# test_reference_pin.test_fixed_depth_reference_cpu_path_writes_no_pixel); its cell map is pinned with fixed_layer's.
+GOLDEN_IMAGES = {"latitude_lat_20": ("fixed_latitude", "lat_20"), "layer_box_0_4": ("fixed_layer", ("box_0", 4))}
+GOLDEN_WORLDS = ("small", "small_z", "hept")
+
+
+def traj_op(name):
+    c = TRAJ_CASES[name]
+    seeds, depths = seed_set(c.seeds, c.world)
+    return dict(op="pathline" if c.pathline else "streamline", seeds=seeds, depth=c.depth, depths=depths,
+                delta_t=c.delta_t, duration=c.duration, record_t=c.record_t, backward=c.backward, euler=c.euler)
+
+
+def image_op(kind, key):
+    if kind == "fixed_depth":
+        w, h, win, depth = DEPTH_CASES[key]
+        return dict(op=kind, width=w, height=h, window=win, value=depth)
+    if kind == "fixed_latitude":
+        w, h, lon, lat = LATITUDE_CASES[key]
+        return dict(op=kind, width=w, height=h, window=((0.0, 0.0), lon), value=lat)
+    win_key, layer = key
+    w, h, win, _ = DEPTH_CASES[win_key]
+    return dict(op=kind, width=w, height=h, window=win, value=float(layer))
+
+
+# ---- the oracle and the Python restatements on the same cases ---------------------------------------------
+@functools.lru_cache(maxsize=None)
+def oracle_fields(world_key):
+    from oracle import oracle as O
+    mesh, s0, s1 = world(world_key)
+    return O.preprocess(mesh, s0), O.preprocess(mesh, s1)
+
+
+def oracle_lines(name):
+    """oracle.run + oracle.finalize_lines on one trajectory case, in lines_from_result's layout."""
+    from oracle import oracle as O
+    c = TRAJ_CASES[name]
+    mesh = world(c.world)[0]
+    r0, r1 = oracle_fields(c.world)
+    seeds, depths = seed_set(c.seeds, c.world)
+    cells = O.knn(mesh, seeds)
+    ref = O.run(mesh, r0, r1 if c.pathline else None, seeds, depth=c.depth, depths=depths, delta_t=c.delta_t,
+                duration=c.duration, record_t=c.record_t, euler=c.euler, backward=c.backward, cells=cells)
+    assert ref is not None, name
+    out = {k: ref[k] for k in ("points", "velocity", "temperature", "salinity", "lastPoint")}
+    out["depth"] = ref["init_depth"].astype(np.float64)
+    out["cells"] = cells.astype(np.int64)
+    return out
+
+
+def restated_image(kind, key):
+    """The Python restatement (remap_reference / image_reference) of one image case: (images [n, H, W, 4],
+    cells or None)."""
+    import image_reference as IR
+    import remap_reference as RR
+    from oracle import oracle as O
+    mesh = world("small")[0]
+    derived = oracle_fields("small")[0]
+    if kind == "fixed_depth":
+        w, h, (lat, lon), depth = DEPTH_CASES[key]
+        cells = O.knn(mesh, RR.depth_positions(w, h, lat, lon))
+        return RR.fixed_depth(mesh, derived, w, h, lat, lon, depth, cells, layer_rule="reference")["images"], \
+            cells.astype(np.int64).reshape(h, w)
+    if kind == "fixed_latitude":
+        w, h, lon, lat = LATITUDE_CASES[key]
+        cells = O.knn(mesh, RR.latitude_positions(w, lon, lat))
+        drange = (float(mesh.refBottomDepth[0]), float(mesh.refBottomDepth[-1]))
+        return RR.fixed_latitude(mesh, derived, w, h, lon, lat, drange, cells)["image"][None], None
+    win_key, layer = key
+    w, h, (lat, lon), _ = DEPTH_CASES[win_key]
+    cells = O.knn(mesh, RR.depth_positions(w, h, lat, lon))
+    return IR.fixed_layer(mesh, derived, w, h, lat, lon, layer, cells)["image"][None], \
+        cells.astype(np.int64).reshape(h, w)
+
+
+# ---- outcomes and digests ---------------------------------------------------------------------------------
+def expected_records(c):
+    """How many record slots a particle that lives to the end writes, from the settings alone: a pathline
+    records every recordT // deltaT steps, a streamline when its run time is a multiple of recordT."""
+    n_steps, K = c.duration // c.delta_t, c.duration // c.record_t
+    if c.pathline:
+        interval = c.record_t // c.delta_t
+        hits = sum(1 for s in range(n_steps) if interval > 0 and (s + 1) % interval == 0)
+    else:
+        hits = sum(1 for s in range(n_steps) if ((s + 1) * c.delta_t) % c.record_t == 0)
+    return min(hits, K)
+
+
+def line_outcome(name, lines):
+    """(dead, alive) from one run's lines alone: a particle that died leaves its remaining record slots
+    unwritten (the origin), so it has fewer points off the origin than a particle that lived to the end."""
+    want = expected_records(TRAJ_CASES[name])
+    assert want >= 2, "a single record cannot tell a particle that died from one that lived"
+    written = (np.linalg.norm(lines["points"][:, 1:], axis=-1) > 0.0).sum(axis=1)
+    assert (written <= want).all(), (name, int(written.max()), want)
+    alive = int((written == want).sum())
+    return int(written.size) - alive, alive
+
+
+def pixel_outcome(images):
+    """(finite, NaN) pixels of image 0."""
+    nan = int(np.isnan(images[0][..., 0]).sum())
+    return int(images[0][..., 0].size) - nan, nan
+
+
+def digest(a):
+    a = np.ascontiguousarray(a)
+    return hashlib.sha256(a.astype(a.dtype.newbyteorder("<"), copy=False).tobytes()).hexdigest()
+
+
+def golden_entries(case, arrays, outcome):
+    """One case's record: per array its SHA-256, shape and dtype, its first 4 lines (rows) raw, and the outcome
+    counts.  ``pack_golden`` turns the records of all cases into the npz entries."""
+    rec = {"outcome": [int(x) for x in outcome], "arrays": {}, "samples": {}}
+    for k, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        rec["arrays"][k] = {"sha256": digest(a), "shape": list(a.shape), "dtype": a.dtype.str}
+        rec["samples"][k] = sample(k, a)
+    return {case: rec}
+
+
+def pack_golden(records):
+    """npz entries: ``meta`` (JSON: per case the outcome and per array digest, shape, dtype and the sample's
+    shape and offset) and ``samples`` (all stored lines, as the bytes of their own dtypes, back to back)."""
+    meta, blob = {}, bytearray()
+    for case in sorted(records):
+        rec = records[case]
+        meta[case] = {"outcome": rec["outcome"], "arrays": {}}
+        for k in sorted(rec["arrays"]):
+            smp = rec["samples"][k]
+            smp = smp.astype(smp.dtype.newbyteorder("<"), copy=False)
+            meta[case]["arrays"][k] = dict(rec["arrays"][k], sample_shape=list(smp.shape), sample_offset=len(blob))
+            blob += smp.tobytes()
+    return {"meta": np.array(json.dumps(meta, sort_keys=True)), "samples": np.frombuffer(bytes(blob), dtype=np.uint8)}
+
+
+class Golden:
+    """tests/golden/reference_pin.npz, read back."""
+
+    def __init__(self, path=None):
+        with np.load(GOLDEN if path is None else path) as z:
+            self.meta = json.loads(str(z["meta"]))
+            self.blob = z["samples"].tobytes()
+
+    def cases(self):
+        return sorted(self.meta)
+
+    def keys(self, case):
+        return sorted(self.meta[case]["arrays"])
+
+    def outcome(self, case):
+        return tuple(self.meta[case]["outcome"])
+
+    def sha256(self, case, key):
+        return self.meta[case]["arrays"][key]["sha256"]
+
+    def stored_sample(self, case, key):
+        m = self.meta[case]["arrays"][key]
+        n = int(np.prod(m["sample_shape"], dtype=np.int64))
+        return np.frombuffer(self.blob, dtype=np.dtype(m["dtype"]), count=n, offset=m["sample_offset"]).reshape(
+            m["sample_shape"])
+
+
+def sample(key, a):
+    """The first 4 lines of a trajectory field, or the first 4 rows of image 0."""
+    return np.ascontiguousarray(a[0, :4] if key == "images" else a[:4])
+
+
+def describe_mismatch(golden, case, key, got):
+    """Why ``got`` does not hash to the golden: shape / dtype, or the first differing stored line (row)."""
+    got = np.ascontiguousarray(got)
+    m = golden.meta[case]["arrays"][key]
+    if list(got.shape) != m["shape"] or got.dtype.str != m["dtype"]:
+        return f"{case} {key}: shape / dtype {got.shape} {got.dtype.str}, golden {m['shape']} {m['dtype']}"
+    want, have = golden.stored_sample(case, key), sample(key, got)
+    for i in range(want.shape[0]):
+        if not np.array_equal(want[i], have[i], equal_nan=want.dtype.kind == "f"):
+            bad = np.argwhere(~((want[i] == have[i]) | ((want[i] != want[i]) & (have[i] != have[i]))))[0]
+            j = tuple(int(x) for x in bad)
+            return f"{case} {key}: first differing stored line {i} at {j}: got {have[i][j]!r}, golden {want[i][j]!r}"
+    return f"{case} {key}: the stored lines agree; the difference lies beyond them"
+
+
+def reference_golden(driver):
+    """The entries of reference_pin.npz, from the compiled reference."""
+    entries = {}
+    for wk in GOLDEN_WORLDS:
+        names = [n for n in GOLDEN_TRAJ if TRAJ_CASES[n].world == wk]
+        images = list(GOLDEN_IMAGES.items()) if wk == "small" else []
+        mesh, s0, s1 = world(wk)
+        res = run_driver(driver, mesh, (s0, s1), [traj_op(n) for n in names] + [image_op(*v) for _, v in images])
+        for n, r in zip(names, res):
+            lines = lines_from_result(r)
+            entries.update(golden_entries(n, {k: lines[k] for k in LINE_FIELDS}, line_outcome(n, lines)))
+        for (n, _), r in zip(images, res[len(names):]):
+            arrays = {k: r[k] for k in ("images", "cells") if k in r}
+            entries.update(golden_entries(n, arrays, pixel_outcome(r["images"])))
+    return pack_golden(entries)

@@ -1,0 +1,266 @@
+"""The oracle (oracle/mops_oracle.c) and the Python restatements (remap_reference.py, image_reference.py) against
+the reference's own CPU kernels, compiled unchanged by oracle/ref/Makefile into oracle/_ref/mops_ref_driver.
+
+Every live comparison is on bytes (np.array_equal with equal_nan, plus equal NaN and zero patterns): both sides
+are x86-64 doubles without contraction and call the same libm.  Where neither the driver nor the reference's
+sources are present those comparisons skip; the golden checks at the end always run and pin the oracle and the
+restatements to digests recorded from the compiled reference (tests/golden/reference_pin.npz).
+
+One operation is not pinned: Kernel::VisualizeFixedDepth.  Its CPU path hands each image's std::vector to
+SetPixel by value, so the compiled reference writes every pixel into a temporary and returns the images as it
+got them (test_fixed_depth_reference_cpu_path_writes_no_pixel); only its cell map can be compared.
+"""
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ref_case as RC  # noqa: E402
+
+
+def _same(a, b, what):
+    a, b = np.asarray(a), np.asarray(b)
+    assert a.shape == b.shape and a.dtype == b.dtype, (what, a.shape, b.shape, a.dtype, b.dtype)
+    if a.dtype.kind == "f":
+        assert np.array_equal(np.isnan(a), np.isnan(b)), f"{what}: NaN pattern"
+        assert np.array_equal(a == 0, b == 0), f"{what}: zero pattern"
+        assert np.array_equal(np.signbit(a), np.signbit(b)), f"{what}: sign pattern"
+    if not np.array_equal(a, b, equal_nan=a.dtype.kind == "f"):
+        bad = np.argwhere(~((a == b) | ((a != a) & (b != b))))
+        j = tuple(int(x) for x in bad[0])
+        raise AssertionError(f"{what}: {len(bad)} of {a.size} values differ, first at {j}: {a[j]!r} != {b[j]!r}")
+
+
+@pytest.fixture(scope="module")
+def driver():
+    import __graft_entry__ as g
+    built = g.build_reference()   # raises where the reference is present and does not compile
+    if built is None and not os.path.exists(RC.DRIVER):
+        pytest.skip("neither oracle/_ref/mops_ref_driver nor the reference's sources ($REF) are present")
+    return RC.DRIVER
+
+
+@pytest.fixture(scope="module")
+def oracle(oracle_lib):
+    return oracle_lib
+
+
+def _locate_sets(mesh):
+    """3000 band seeds up to 89 degrees, a 21 x 21 lattice and 50 exact cell centres."""
+    from mops_amd import synth
+    lattice = synth.lattice_seeds(22, 22, (-84.0, 84.0), (-180.0, 180.0))[:21 * 21]  # exclusive upper bounds
+    assert lattice.shape == (21 * 21, 3)
+    cc = np.asarray(mesh.cellCoord, dtype=np.float64).reshape(-1, 3)
+    centres = cc[np.random.default_rng(9).choice(mesh.nCells, 50, replace=False)]
+    return {"band": synth.uniform_band_seeds(3000, seed=31, max_abs_lat=89.0), "lattice": lattice, "centres": centres}
+
+
+@pytest.fixture(scope="module")
+def runs(driver):
+    """One driver run per catalogue mesh with everything asked of it; results by name."""
+    out = {}
+    for wk in RC.WORLDS:
+        mesh, s0, s1 = RC.world(wk)
+        names = [n for n, c in RC.TRAJ_CASES.items() if c.world == wk]
+        ops = [dict(op="preprocess")] + [RC.traj_op(n) for n in names]
+        keys = [("preprocess", wk)] + [("traj", n) for n in names]
+        if wk == "small":
+            for k, pts in _locate_sets(mesh).items():
+                ops.append(dict(op="locate", points=pts)); keys.append(("locate", k))
+            for k in RC.DEPTH_CASES:
+                ops.append(RC.image_op("fixed_depth", k)); keys.append(("fixed_depth", k))
+            for k in RC.LATITUDE_CASES:
+                ops.append(RC.image_op("fixed_latitude", k)); keys.append(("fixed_latitude", k))
+            for win in RC.LAYER_WINDOWS:
+                for value, _ in RC.LAYERS:
+                    ops.append(RC.image_op("fixed_layer", (win, value))); keys.append(("fixed_layer", (win, value)))
+        out.update(zip(keys, RC.run_driver(driver, mesh, (s0, s1), ops)))
+    return out
+
+
+def _report(capsys, text):
+    with capsys.disabled():
+        print("\n    [reference pin] " + text, end="")
+
+
+# ---- preprocess -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("wk", RC.WORLDS)
+def test_preprocess_matches_compiled_reference(runs, oracle, wk):
+    """MOPSApp::addSol's derived fields, through MPASOSolution's own calc* members, against oracle.preprocess:
+    vertex zTop, vertex velocity, vertex vertical velocity, both cell-to-vertex attributes, and the two
+    cell-centre fields they are made from, for both snapshots."""
+    res = runs[("preprocess", wk)]
+    for p, d in zip(("s0/", "s1/"), RC.oracle_fields(wk)):
+        assert np.isfinite(res[p + "vertex_vel"]).all() and np.any(res[p + "vertex_vel"] != 0)
+        for k in ("vertex_ztop", "vertex_vel", "vertex_w", "cell_ztop", "cell_vel"):
+            _same(res[p + k].reshape(-1), getattr(d, k).reshape(-1), f"{wk} {p}{k}")
+        assert sorted(d.attrs) == ["salinity", "temperature"]
+        for k in d.attrs:
+            _same(res[p + "vertex_attr/" + k].reshape(-1), d.attrs[k].reshape(-1), f"{wk} {p}attr {k}")
+
+
+# ---- locate -----------------------------------------------------------------------------------------------
+def test_locate_matches_compiled_reference(runs, oracle):
+    """calcInWhichCells (the reference's own KD-tree) against oracle.knn on queries that have, by brute force
+    in numpy, one nearest centre each -- so equality is demanded of every query."""
+    mesh = RC.world("small")[0]
+    cc = np.asarray(mesh.cellCoord, dtype=np.float64).reshape(-1, 3)
+    for k, pts in _locate_sets(mesh).items():
+        d2 = ((pts[:, None, :] - cc[None, :, :]) ** 2).sum(-1)
+        two = np.partition(d2, 1, axis=1)[:, :2]
+        assert (two[:, 1] > two[:, 0]).all(), f"{k}: a query with two equidistant nearest centres"
+        got = runs[("locate", k)]["cells"]
+        assert got.shape == (len(pts),)
+        _same(got, d2.argmin(axis=1).astype(np.int64), f"locate {k}: reference against brute force")
+        _same(got, oracle.knn(mesh, pts).astype(np.int64), f"locate {k}")
+
+
+# ---- trajectories -----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(RC.TRAJ_CASES))
+def test_trajectories_match_compiled_reference(runs, oracle, capsys, name):
+    """Kernel::StreamLine / PathLine (seeds located by calcInWhichCells, lines finalised by the kernel itself)
+    against oracle.run + oracle.finalize_lines: every field, the line count and the line order."""
+    ref = RC.lines_from_result(runs[("traj", name)])
+    c = RC.TRAJ_CASES[name]
+    n = len(RC.seed_set(c.seeds, c.world)[0])
+    assert ref["points"].shape == (n, c.duration // c.record_t + 1, 3)
+    dead, alive = RC.line_outcome(name, ref)
+    _report(capsys, f"{name}: {alive} of {n} particles live ({100.0 * alive / n:.1f} %)")
+    assert dead >= 1 and alive > n // 2, (name, dead, alive)
+    got = RC.oracle_lines(name)
+    for k in RC.LINE_FIELDS:
+        _same(got[k], ref[k], f"{name} {k}")
+
+
+def test_seeds_on_an_edge_plane_stay_inside(runs):
+    """IsInMesh rejects only `dot < 0`: most of the 100 seeds with a dot of exactly 0.0 live on past
+    step 0 in the compiled reference, so a `<=` in a restatement or in the engine shows."""
+    ref = RC.lines_from_result(runs[("traj", "small_edge_streamline_euler")])
+    written = (np.linalg.norm(ref["points"][:100, 1:], axis=-1) > 0.0).sum(axis=1)
+    assert (written >= 2).sum() > 50, written
+
+
+# ---- remapping --------------------------------------------------------------------------------------------
+def _assert_coverage(images):
+    """test_remap_gpu._assert_coverage's condition on the reference's own image: at least 40 % finite and at
+    least 5 % NaN pixels."""
+    finite, nan = RC.pixel_outcome(images)
+    assert finite >= 0.4 * (finite + nan) and nan >= 0.05 * (finite + nan), (finite, nan)
+    return finite, nan
+
+
+@pytest.mark.parametrize("key", sorted(RC.DEPTH_CASES))
+def test_fixed_depth_cell_map_matches_compiled_reference(runs, oracle, key):
+    """TBBKernel::SearchKDTree over the four fixed-depth windows against oracle.knn on the restated pixel
+    positions (the cell map is all of VisualizeFixedDepth that the compiled reference yields, see below)."""
+    _, cells = RC.restated_image("fixed_depth", key)
+    _same(runs[("fixed_depth", key)]["cells"], cells, f"fixed depth {key} cell map")
+
+
+def test_fixed_depth_reference_cpu_path_writes_no_pixel(runs):
+    """The finding that keeps fixed depth out of the pin.  The CPU VisualizeFixedDepth passes
+    ``img_vec[k].mPixels`` (a std::vector) to ``SetPixel(Accessor img_acc, ...)``, which takes it by value: every
+    pixel goes into a copy and the caller's images come back as MOPSApp::runRemapping made them, all zero, alpha
+    included.  remap_reference.fixed_depth restates the per-pixel arithmetic as the reference's GPU back ends
+    (whose accessors are handles) store it, and therefore cannot be compared here.  Should the reference ever
+    write these images, this test fails and the comparison belongs with the others in this file."""
+    for key in RC.DEPTH_CASES:
+        images = runs[("fixed_depth", key)]["images"]
+        w, h, _, _ = RC.DEPTH_CASES[key]
+        assert images.shape == (2, h, w, 4)   # 1 + ceil(2 / 3) images for two attributes
+        assert not images.any(), key
+        restated, _ = RC.restated_image("fixed_depth", key)
+        assert restated.shape == images.shape and np.all(restated[..., 3] == 1.0)
+
+
+@pytest.mark.parametrize("key", sorted(RC.LATITUDE_CASES))
+def test_fixed_latitude_matches_compiled_reference(runs, oracle, capsys, key):
+    images = runs[("fixed_latitude", key)]["images"]
+    finite, nan = _assert_coverage(images)
+    _report(capsys, f"fixed latitude {key}: {finite} of {finite + nan} pixels finite")
+    restated, _ = RC.restated_image("fixed_latitude", key)
+    _same(restated, images, f"fixed latitude {key}")
+    assert np.all(images[..., 3] == 1.0)
+
+
+@pytest.mark.parametrize("win", RC.LAYER_WINDOWS)
+def test_fixed_layer_matches_compiled_reference(runs, oracle, capsys, win):
+    """Layers 0, 4 and 9 of 10, a fractional one, and the clamping of -3 and 99."""
+    seen = {}
+    for value, want_layer in RC.LAYERS:
+        res = runs[("fixed_layer", (win, value))]
+        finite, nan = _assert_coverage(res["images"])
+        _report(capsys, f"fixed layer {win} {value}: {finite} of {finite + nan} pixels finite")
+        restated, cells = RC.restated_image("fixed_layer", (win, value))
+        _same(restated, res["images"], f"fixed layer {win} {value}")
+        _same(res["cells"], cells, f"fixed layer {win} {value} cell map")
+        assert np.all(res["images"][..., 3] == 1.0)
+        if want_layer in seen:  # the clamped settings give the clamped layer's image
+            _same(res["images"], seen[want_layer], f"fixed layer {win}: {value} against layer {want_layer}")
+        seen.setdefault(want_layer, res["images"])
+    assert not np.array_equal(seen[0], seen[4], equal_nan=True) and not np.array_equal(seen[4], seen[9], equal_nan=True)
+
+
+# ---- RemoveNaN --------------------------------------------------------------------------------------------
+def _nan_cases():
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "remove_nan_cases.json")
+    return json.load(open(path))["cases"]
+
+
+@pytest.mark.parametrize("case", _nan_cases(), ids=lambda c: c["name"])
+def test_remove_nan_matches_compiled_reference(driver, oracle, case):
+    """RemoveNaNTrajectoriesAndReindex on the four recorded cases: every field of the expected output, the
+    derived ones included, and oracle.remove_nan on the same input."""
+    res = RC.run_driver(driver, None, (), [dict(op="remove_nan", lines=[case["input"]])])[0]
+    want = case["expected"]
+    n = len(want["points"])
+    assert res["counts"].tolist() == [[n, n, n, n]] and res["lineID"].tolist() == [want["lineID"]]
+    for k, shape in (("points", (n, 3)), ("velocity", (n, 3)), ("temperature", (n,)), ("salinity", (n,)),
+                     ("lastPoint", (1, 3))):
+        _same(res[k].reshape(shape), np.asarray(want[k], dtype=np.float64).reshape(shape), f"{case['name']} {k}")
+    inp = case["input"]
+    pts, vel, temp, sal, last = oracle.remove_nan(inp["points"], inp["velocity"], inp["temperature"], inp["salinity"])
+    for k, a in (("points", pts), ("velocity", vel), ("temperature", temp), ("salinity", sal), ("lastPoint", last)):
+        _same(a.reshape(-1), res[k].reshape(-1), f"{case['name']} oracle {k}")
+
+
+# ---- goldens ----------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def golden():
+    return RC.Golden()
+
+
+GOLDEN_CASES = RC.GOLDEN_TRAJ + list(RC.GOLDEN_IMAGES)
+
+
+def test_golden_catalogue(golden):
+    """16 trajectory combinations on the small mesh, two z-level and two heptagon cases, the seeds on edge
+    planes, two images; the file no larger than the largest fixture beside it."""
+    assert golden.cases() == sorted(GOLDEN_CASES) and len(RC.GOLDEN_TRAJ) == 21
+    assert sum(n.startswith("small_") and "_edge_" not in n for n in RC.GOLDEN_TRAJ) == 16
+    assert os.path.getsize(RC.GOLDEN) <= os.path.getsize(os.path.join(os.path.dirname(RC.GOLDEN), "oracle_small.npz"))
+
+
+def test_golden_is_what_the_compiled_reference_gives(driver, golden):
+    """A stale golden or a changed reference: every stored entry regenerated from the driver."""
+    fresh = RC.reference_golden(driver)
+    assert json.loads(str(fresh["meta"])) == golden.meta
+    assert fresh["samples"].tobytes() == golden.blob
+
+
+@pytest.mark.parametrize("case", GOLDEN_CASES)
+def test_oracle_and_restatements_hash_to_the_golden(oracle, golden, case):
+    """Without the reference: the oracle's lines and the restatements' images hash to the recorded digests."""
+    if case in RC.TRAJ_CASES:
+        got = RC.oracle_lines(case)
+        assert RC.line_outcome(case, got) == golden.outcome(case)
+    else:
+        images, cells = RC.restated_image(*RC.GOLDEN_IMAGES[case])
+        got = {"images": images} if cells is None else {"images": images, "cells": cells}
+        assert RC.pixel_outcome(images) == golden.outcome(case)
+    assert sorted(got) == golden.keys(case)
+    for k in sorted(got):
+        assert RC.digest(got[k]) == golden.sha256(case, k), RC.describe_mismatch(golden, case, k, got[k])

@@ -1,0 +1,106 @@
+"""The GPU engine against digests recorded from the compiled reference (tests/golden/reference_pin.npz, written by
+tests/golden/make_reference_pin.py): the golden catalogue of tests/ref_case.py -- 16 trajectory combinations on
+the small mesh, two z-level and two heptagon-mesh cases, the seeds on edge planes, a fixed-latitude and a
+fixed-layer image -- through run_trajectories, remap_fixed_latitude and remap_fixed_layer.  Every output array
+must hash to the recorded SHA-256 and the outcome counts (dead / alive particles, finite / NaN pixels) must be
+the recorded ones.
+
+Nothing here reads the reference or oracle/_ref: the case inputs are regenerated from mops_amd.synth.  On a
+mismatch the message says whether the oracle, run on this machine, still hashes to the golden (if it does not,
+the host libm differs from the recording machine's and the engine is not at fault) and names the first
+differing line among the four stored per array.  Fixed depth has no golden: see tests/test_reference_pin.py.
+"""
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ref_case as RC  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+ENGINE_LINE_FIELDS = ("points", "velocity", "temperature", "salinity", "lastPoint", "cells")
+GOLDEN_CASES = RC.GOLDEN_TRAJ + list(RC.GOLDEN_IMAGES)
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return RC.Golden()
+
+
+@pytest.fixture(scope="module")
+def device(engine_lib, oracle_lib, gpu):
+    """world key -> (device mesh, device field 0, device field 1), uploaded once per mesh."""
+    from mops_amd import engine
+
+    @functools.lru_cache(maxsize=None)
+    def get(wk):
+        mesh, s0, s1 = RC.world(wk)
+        dm = engine.DeviceMesh.from_mesh(mesh)
+        return dm, engine.DeviceField.from_snapshot(dm, s0), engine.DeviceField.from_snapshot(dm, s1)
+    return get
+
+
+def _engine_lines(device, name):
+    from mops_amd.engine import TrajectoryConfig, run_trajectories
+    c = RC.TRAJ_CASES[name]
+    dm, f0, f1 = device(c.world)
+    seeds, depths = RC.seed_set(c.seeds, c.world)
+    cfg = TrajectoryConfig(deltaT=c.delta_t, simulationDuration=c.duration, recordT=c.record_t, depth=c.depth,
+                           method=1 if c.euler else 0, direction=1 if c.backward else 0)
+    got = run_trajectories(dm, f0, f1 if c.pathline else None, cfg, seeds, depths=depths)
+    out = {k: got[k] for k in ENGINE_LINE_FIELDS[:-1]}
+    out["cells"] = got["cells"].astype(np.int64)
+    return out
+
+
+def _engine_image(device, kind, key):
+    from mops_amd import engine
+    dm, f0, _ = device("small")
+    mesh = RC.world("small")[0]
+    if kind == "fixed_latitude":
+        w, h, lon, lat = RC.LATITUDE_CASES[key]
+        drange = (float(mesh.refBottomDepth[0]), float(mesh.refBottomDepth[-1]))
+        return {"images": engine.remap_fixed_latitude(dm, f0, w, h, lon, lat, drange).cpu().numpy()[None]}
+    win_key, layer = key
+    w, h, (lat, lon), _ = RC.DEPTH_CASES[win_key]
+    image, cells = engine.remap_fixed_layer(dm, f0, w, h, lat, lon, layer, return_cells=True)
+    return {"images": image.cpu().numpy()[None], "cells": cells.cpu().numpy().astype(np.int64)}
+
+
+def _host_side(case):
+    """The oracle's (restatement's) arrays for one case, computed on this machine."""
+    if case in RC.TRAJ_CASES:
+        return RC.oracle_lines(case)
+    images, cells = RC.restated_image(*RC.GOLDEN_IMAGES[case])
+    return {"images": images} if cells is None else {"images": images, "cells": cells}
+
+
+def check_against_golden(golden, case, got, outcome):
+    """Digests and outcome counts of ``got`` against the golden, with the diagnosis on a mismatch."""
+    wrong = [k for k in sorted(got) if RC.digest(got[k]) != golden.sha256(case, k)]
+    if wrong or tuple(outcome) != golden.outcome(case):
+        host = _host_side(case)
+        host_ok = all(RC.digest(host[k]) == golden.sha256(case, k) for k in sorted(got))
+        verdict = ("the oracle run on this machine still hashes to the golden: the engine differs from the reference"
+                   if host_ok else
+                   "the oracle run on this machine does NOT hash to the golden either: the host libm differs from "
+                   "the recording machine's, the engine is not at fault")
+        lines = [RC.describe_mismatch(golden, case, k, got[k]) for k in wrong]
+        pytest.fail(f"{case}: outcome {tuple(outcome)} (golden {golden.outcome(case)}); {verdict}\n  " + "\n  ".join(lines))
+
+
+@pytest.mark.parametrize("case", GOLDEN_CASES)
+def test_engine_hashes_to_the_reference_golden(device, golden, case):
+    if case in RC.TRAJ_CASES:
+        got = _engine_lines(device, case)
+        assert set(got) == set(golden.keys(case)) - {"depth"}  # a line's depth is the input, not an engine output
+        outcome = RC.line_outcome(case, got)
+    else:
+        got = _engine_image(device, *RC.GOLDEN_IMAGES[case])
+        assert sorted(got) == golden.keys(case)
+        outcome = RC.pixel_outcome(got["images"])
+    check_against_golden(golden, case, got, outcome)
