@@ -249,6 +249,22 @@ std::vector<ImageBuffer<double>> MOPS_RunRemapping(VisualizationSettings* config
 // range above 360): Error() and an empty image.
 ImageBuffer<double> MOPS_RunDensity(const std::vector<TrajectoryLine>& lines, VisualizationSettings* config,
                                     const std::string& value = "");
+// Extension ("flow-map lattices and FTLE", mops_traj.h): one seed per pixel of config's window -- imageSize,
+// LatRange, LonRange -- row major, (imageSize.y * imageSize.x) points, the positions MOPS_RunRemapping's image
+// has its pixels at, formed on the GPU (mops_flowmap_lattice).  Run them as a pathline or streamline and give
+// the lines, in this order, to MOPS_RunFTLE.  Invalid inputs (null config, image size below 1): Error() and
+// an empty vector.
+std::vector<CartesianCoord> MOPS_LatticeSeeds(VisualizationSettings* config);
+// Extension: the finite-time Lyapunov exponent image of `lines` seeded by MOPS_LatticeSeeds(config) and given
+// in lattice order (lines.size() == imageSize.y * imageSize.x): the flow map is points[0] -> lastPoint of each
+// line.  No death array is passed: a dead line has a zero lastPoint (RemoveNaNTrajectoriesAndReindex), which
+// is not valid; so is a line without points.  One image {ftle, lambda_max, lambda_min} (alpha 1), NaN where a
+// pixel has no valid stencil, usable with SaveToPNG and SaveVTI.  horizon > 0: the integration time in the unit
+// the exponent is wanted per.  Columns wrap iff LonRange.y - LonRange.x == 360.  Invalid inputs (null config,
+// image size below 1, a line count other than the lattice's, horizon <= 0 or not finite): Error() and an empty
+// image.
+ImageBuffer<double> MOPS_RunFTLE(const std::vector<TrajectoryLine>& lines, VisualizationSettings* config,
+                                 double horizon);
 void MOPS_GenerateSamplePoints(SamplingSettings* config, std::vector<CartesianCoord>& sample_points);
 
 // SaveToPNG (src/Common/ImageBuffer.hpp:91-136) for the double image (the one instantiation the reference

@@ -646,6 +646,65 @@ mops_status mops_density_accumulate(const mops_remap_cfg* cfg, int64_t n, int64_
 mops_status mops_density_image(const mops_remap_cfg* cfg, const void* d_accum, int32_t nan_empty, double* d_image,
                                void* stream);
 
+/* ---- flow-map lattices and FTLE ------------------------------------------- */
+
+/* The finite-time Lyapunov exponent of a flow map seeded on an image's pixel
+ * lattice: where the flow pulls neighbouring particles apart (forward run) or
+ * squeezes them together (backward run).  No reference counterpart.
+ *
+ * Lattice.  A window is width, height, min_lat, max_lat, min_lon, max_lon of a
+ * mops_remap_cfg (the other members are ignored).  Seed (i, j) is the
+ * fixed-depth remapping's pixel position with the same bits:
+ *   (R * cos(lat_i) * cos(lon_j), R * cos(lat_i) * sin(lon_j), R * sin(lat_i)),
+ * R = 6371010 (GeoConverter.hpp:107), the cos / sin values from the host
+ * tables of mops_remap_tables(cfg, 0, ...).  Row major, [height*width][3];
+ * row 0 is max_lat and row i - 1 lies north of row i; column j + 1 lies east
+ * of column j.  So an FTLE image overlays a mops_remap_fixed_depth image and
+ * a density image of the same settings.
+ *
+ * Validity.  Particle (i, j) is valid iff its seed and its last point are
+ * finite, both have non-zero length, and death[i*W + j] < 0 when a death
+ * array is given.
+ *
+ * FTLE of pixel (i, j).  FP64 with + - * / sqrt only up to lambda, no
+ * contraction, every dot product summed as (x*x + y*y) + z*z, every length
+ * the sqrt of such a sum:
+ *   1. s = seed / |seed|, u = last / |last|, component-wise.
+ *   2. East pair: jm = j-1 if that column exists and its particle is valid,
+ *      else j; jp = j+1 likewise.  With wrap_lon != 0, j-1 and j+1 are taken
+ *      modulo W.
+ *   3. North pair: im = i-1 and ip = i+1 by the same rule; rows never wrap.
+ *   4. The centre must be valid.  jm == jp or im == ip: the pixel is invalid.
+ *   5. hE = |s[i,jp] - s[i,jm]|, hN = |s[im,j] - s[ip,j]|; either 0: invalid.
+ *   6. a = (u[i,jp] - u[i,jm]) / hE, b = (u[im,j] - u[ip,j]) / hN.
+ *   7. C11 = a.a, C12 = a.b, C22 = b.b (the Cauchy-Green tensor in the
+ *      east / north frame of the seed; the lattice is orthogonal there).
+ *   8. m = 0.5*(C11 + C22), d = 0.5*(C11 - C22), q = sqrt(d*d + C12*C12).
+ *   9. lambda_max = m + q, lambda_min = m - q.
+ *  10. ftle = log(lambda_max) / (2 * horizon); horizon > 0 in the caller's
+ *      unit (the Python layer passes days).
+ * The image is [height][width][4] = {ftle, lambda_max, lambda_min, 1}; an
+ * invalid pixel is {NaN, NaN, NaN, 1}, which mops_colormap_rgba8 leaves
+ * transparent.  The one-sided rule treats image edges, coast and dead
+ * neighbours the same way: the difference is taken over the neighbours that
+ * exist, with the spacing they have. */
+
+/* The lattice's seeds into d_points [height*width][3] (device): the tables of
+ * mops_remap_tables on the host, then the remapping's position kernel.
+ * Synchronises `stream` (the uploaded tables are freed on return).
+ * MOPS_ERR_INVALID, nothing written, for a null pointer, width or height < 1
+ * or width * height >= 2^31. */
+mops_status mops_flowmap_lattice(const mops_remap_cfg* cfg, double* d_points, void* stream);
+
+/* The FTLE image of a flow map: d_seeds and d_last [height*width][3], d_death
+ * [height*width] int32 (NULL = none), all in lattice (seed) order; d_image
+ * [height][width][4] doubles, 16-byte aligned.  One lane per pixel.  Enqueues
+ * on `stream` and does not synchronise.  MOPS_ERR_INVALID, nothing written,
+ * for a null cfg, d_seeds, d_last or d_image, width or height < 1,
+ * width * height >= 2^31, horizon <= 0 or a non-finite horizon. */
+mops_status mops_ftle_image(const mops_remap_cfg* cfg, const double* d_seeds, const double* d_last,
+                            const int32_t* d_death, double horizon, int32_t wrap_lon, double* d_image, void* stream);
+
 /* Identity of the engine build: a hash of the engine's sources, headers,
  * compiler flags and ROCm version, stamped at compile time (no reference
  * counterpart).  The Python loader refuses a library whose id differs from

@@ -28,6 +28,7 @@ EXPORTED = (
     "mops_remap_num_images", "mops_remap_tables", "mops_remap_fixed_depth", "mops_remap_fixed_latitude",
     "mops_remap_fixed_layer", "mops_colormap_rgba8", "mops_colormap_image",
     "mops_density_bytes", "mops_density_accumulate", "mops_density_image",
+    "mops_flowmap_lattice", "mops_ftle_image",
     # include/mops_io.h
     "mops_lines_geo", "mops_write_lines_vtp", "mops_write_lines_txt", "mops_write_pathline_binary",
     "mops_write_png_rgba8", "mops_write_images_vti", "mops_write_image_vti",
@@ -197,6 +198,8 @@ def load(path: str | None = None):
     lib.mops_density_accumulate.argtypes = [P, I64, I64, I64, P, I64, I64, I64, P, I32, P, I64, I64, P, P]
     lib.mops_density_accumulate.restype = st
     lib.mops_density_image.argtypes = [P, P, I32, P, P]; lib.mops_density_image.restype = st
+    lib.mops_flowmap_lattice.argtypes = [P, P, P]; lib.mops_flowmap_lattice.restype = st
+    lib.mops_ftle_image.argtypes = [P, P, P, P, C.c_double, I32, P, P]; lib.mops_ftle_image.restype = st
     lib.mops_write_png_rgba8.argtypes = [C.c_char_p, I32, I32, P]; lib.mops_write_png_rgba8.restype = st
     lib.mops_write_images_vti.argtypes = [C.c_char_p, I32, I32, I32, P, P, P, P, I32]
     lib.mops_write_images_vti.restype = st

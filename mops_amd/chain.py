@@ -633,6 +633,33 @@ class HostLineSink:
                 "chunks": len(self.d2h_events), "pairs": self.pairs}
 
 
+class EverDead:
+    """A ``PathlineChain.run(on_pair=...)`` collector: ``mask`` (bool device tensor [n], seed order) is true for
+    every particle that died in ANY pair so far.
+
+    A chain's ``death_step`` is the last pair's alone, and a particle that died in an earlier pair can come back
+    to life: its ``lastPoint`` -- the next pair's seed -- is its last finite record, or the pre-written seed when
+    the pair holds a single record (quirks Q1, a9), and the next pair integrates it from there.  Its final point
+    is then no image of its first seed under the flow, so a flow-map consumer (``FlowMapLattice.ftle``) must drop
+    it.  Reads ``ps.death`` only, never the records, so no mode of the chain refuses it; it works on torch's
+    current stream, which is the chain's compute stream unless ``compute_stream`` is given (then run the chain
+    inside ``torch.cuda.stream(compute_stream)``)."""
+
+    def __init__(self):
+        self.mask = None
+        self.pairs = 0
+
+    def __call__(self, p: int, last, ps):
+        dead = ps.original(ps.death) >= 0
+        self.mask = dead if self.mask is None else (self.mask | dead)
+        self.pairs += 1
+
+    def death(self):
+        """The mask as an int32 death array for ``FlowMapLattice.ftle``: 0 where ever dead, else -1."""
+        import torch
+        return torch.where(self.mask, 0, -1).to(torch.int32)
+
+
 def cu_split_streams(device, side_cus: int):
     """(compute, side): two HIP streams that partition the device's CUs
     (hipExtStreamCreateWithCUMask), ``side_cus`` of them for the side stream.

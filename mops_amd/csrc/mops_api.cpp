@@ -561,6 +561,73 @@ ImageBuffer<double> MOPS_RunDensity(const std::vector<TrajectoryLine>& lines, Vi
     return img;
 }
 
+std::vector<CartesianCoord> MOPS_LatticeSeeds(VisualizationSettings* config) {
+    ScopedTimer t("GPUKernel::LatticeSeeds", "GPUKernel");
+    const int W = config ? (int)config->imageSize.x : 0, H = config ? (int)config->imageSize.y : 0;
+    if (config == nullptr || W <= 0 || H <= 0 || (int64_t)W * H >= (1LL << 31)) {
+        Error("[MI355X::LatticeSeeds] invalid inputs");
+        return {};
+    }
+    mops_remap_cfg cfg{};
+    cfg.width = W; cfg.height = H;
+    cfg.min_lat = config->LatRange.x; cfg.max_lat = config->LatRange.y;
+    cfg.min_lon = config->LonRange.x; cfg.max_lon = config->LonRange.y;
+    static_assert(sizeof(CartesianCoord) == 3 * sizeof(double), "CartesianCoord is three doubles");
+    std::vector<CartesianCoord> seeds((size_t)W * H);
+    struct DevBuf {
+        void* p = nullptr;
+        ~DevBuf() { (void)hipFree(p); }
+    } buf;
+    auto hip = [](hipError_t e, const char* what) {
+        if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+    };
+    hip(hipMalloc(&buf.p, seeds.size() * sizeof(CartesianCoord)), "MOPS_LatticeSeeds: hipMalloc");
+    check(mops_flowmap_lattice(&cfg, static_cast<double*>(buf.p), nullptr), "mops_flowmap_lattice");
+    hip(hipMemcpy(seeds.data(), buf.p, seeds.size() * sizeof(CartesianCoord), hipMemcpyDeviceToHost), "hipMemcpy seeds");
+    return seeds;
+}
+
+ImageBuffer<double> MOPS_RunFTLE(const std::vector<TrajectoryLine>& lines, VisualizationSettings* config,
+                                 double horizon) {
+    ScopedTimer t("GPUKernel::FTLE", "GPUKernel");
+    const int W = config ? (int)config->imageSize.x : 0, H = config ? (int)config->imageSize.y : 0;
+    if (config == nullptr || W <= 0 || H <= 0 || (int64_t)W * H >= (1LL << 31) || lines.size() != (size_t)W * H ||
+        !std::isfinite(horizon) || !(horizon > 0.0)) {
+        Error("[MI355X::FTLE] invalid inputs");
+        return ImageBuffer<double>();
+    }
+    mops_remap_cfg cfg{};
+    cfg.width = W; cfg.height = H;
+    cfg.min_lat = config->LatRange.x; cfg.max_lat = config->LatRange.y;
+    cfg.min_lon = config->LonRange.x; cfg.max_lon = config->LonRange.y;
+    const int wrap = (config->LonRange.y - config->LonRange.x == 360.0) ? 1 : 0;
+    // seeds | last points, [n][3] each; a line without points keeps zeros, which are not valid
+    const size_t n = lines.size();
+    std::vector<double> host(6 * n, 0.0);
+    for (size_t i = 0; i < n; ++i) {
+        if (lines[i].points.empty()) continue;
+        std::memcpy(&host[3 * i], &lines[i].points[0], 3 * sizeof(double));
+        std::memcpy(&host[3 * (n + i)], &lines[i].lastPoint, 3 * sizeof(double));
+    }
+    struct DevBuf {
+        void* p = nullptr;
+        ~DevBuf() { (void)hipFree(p); }
+    } buf;
+    auto hip = [](hipError_t e, const char* what) {
+        if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+    };
+    // one allocation: image | seeds | last points
+    const size_t px = n * 4;
+    hip(hipMalloc(&buf.p, (px + host.size()) * sizeof(double)), "MOPS_RunFTLE: hipMalloc");
+    double* d_img = static_cast<double*>(buf.p);
+    double* d_seeds = d_img + px;
+    hip(hipMemcpy(d_seeds, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy lines");
+    check(mops_ftle_image(&cfg, d_seeds, d_seeds + 3 * n, nullptr, horizon, wrap, d_img, nullptr), "mops_ftle_image");
+    ImageBuffer<double> img(W, H);
+    hip(hipMemcpy(img.mPixels.data(), d_img, px * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy image");
+    return img;
+}
+
 void MPASOVisualizer::VisualizeFixedLayer(VisualizationSettings* config, ImageBuffer<double>* img) {
     ScopedTimer t("GPUKernel::FixedLayer", "GPUKernel");
     if (config == nullptr || img == nullptr || g_app.mesh == nullptr || g_app.front == nullptr) {  // :143-146

@@ -1065,3 +1065,72 @@ class DensityMap:
                                                 1 if nan_empty else 0, C.c_void_p(img.data_ptr()),
                                                 _stream_handle(self._stream(stream))), "mops_density_image")
         return img
+
+
+class FlowMapLattice:
+    """One particle per pixel of a ``width`` x ``height`` lat / lon window, and the FTLE image of their flow map
+    ("flow-map lattices and FTLE", include/mops_traj.h).
+
+    ``seeds`` is the float64 CUDA tensor [height * width, 3] of the fixed-depth remapping's pixel positions, row
+    major, row 0 at ``lat_range[1]`` (mops_flowmap_lattice: formed on the device, never on the host), so the image
+    overlays a ``remap_fixed_depth`` image and a ``DensityMap`` image of the same window.  ``wrap_lon``: the window
+    spans the whole circle (``lon_range[1] - lon_range[0] == 360.0``), so columns 0 and width - 1 are neighbours.
+    ``ftle`` turns the particles' last points (seed order) into a float64 CUDA image [height, width, 4] =
+    {ftle, lambda_max, lambda_min, 1}, NaN where a pixel has no valid stencil, for ``colormap_rgba`` and the PNG /
+    VTI writers."""
+
+    def __init__(self, width: int, height: int, lat_range, lon_range, device=None):
+        import torch
+        width, height = int(width), int(height)
+        lat, lon = (float(lat_range[0]), float(lat_range[1])), (float(lon_range[0]), float(lon_range[1]))
+        if width < 1 or height < 1 or width * height >= 2 ** 31:
+            raise ValueError(f"invalid image size {width} x {height}")
+        if not (np.isfinite(lat).all() and np.isfinite(lon).all()):
+            raise ValueError(f"invalid latitude / longitude range {lat} / {lon}")
+        self.torch = torch
+        self.width, self.height, self.lat_range, self.lon_range = width, height, lat, lon
+        self.n = width * height
+        self.wrap_lon = lon[1] - lon[0] == 360.0
+        self.cfg = _remap_cfg(width, height, lat, lon)
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        with torch.cuda.device(self.device):
+            self.seeds = torch.empty((self.n, 3), dtype=torch.float64, device=self.device)
+            L.check(L.load().mops_flowmap_lattice(C.byref(self.cfg), C.c_void_p(self.seeds.data_ptr()),
+                                                  _stream_handle(self._stream(None))), "mops_flowmap_lattice")
+
+    def _stream(self, stream):
+        return stream if stream is not None else self.torch.cuda.current_stream(self.device).cuda_stream
+
+    def ftle(self, last_points, death=None, horizon: float = 1.0, stream=None):
+        """The FTLE image (mops_ftle_image) of ``last_points`` [height * width, 3] in seed order (CUDA tensor or
+        host array); ``death`` [height * width] int32, >= 0 where the particle died (None: a particle counts as
+        dead only through a zero or non-finite last point); ``horizon`` > 0, the integration time in the unit the
+        exponent is wanted per (days throughout the Python layer).  On ``stream`` (default torch's current one),
+        without a host synchronisation."""
+        torch = self.torch
+        horizon = float(horizon)
+        if not (np.isfinite(horizon) and horizon > 0.0):
+            raise ValueError("ftle: the horizon must be finite and positive")
+        last = torch.as_tensor(last_points, dtype=torch.float64).to(self.device).contiguous()
+        if last.numel() != 3 * self.n:
+            raise ValueError(f"ftle: last_points must be [{self.n}, 3]")
+        if death is not None:
+            death = torch.as_tensor(death).to(device=self.device, dtype=torch.int32).contiguous()
+            if death.numel() != self.n:
+                raise ValueError(f"ftle: death must be [{self.n}]")
+        with torch.cuda.device(self.device):
+            img = torch.empty((self.height, self.width, 4), dtype=torch.float64, device=self.device)
+            L.check(L.load().mops_ftle_image(C.byref(self.cfg), C.c_void_p(self.seeds.data_ptr()),
+                                             C.c_void_p(last.data_ptr()),
+                                             None if death is None else C.c_void_p(death.data_ptr()), horizon,
+                                             1 if self.wrap_lon else 0, C.c_void_p(img.data_ptr()),
+                                             _stream_handle(self._stream(stream))), "mops_ftle_image")
+        return img
+
+    def ftle_from(self, ps: "ParticleSet", horizon: float, stream=None):
+        """The FTLE image of a ParticleSet seeded with ``seeds``: its ``last_points()`` and its death steps back
+        in seed order."""
+        if ps.n != self.n:
+            raise ValueError("ftle_from: the particle set is not this lattice's")
+        h = self._stream(stream)
+        return self.ftle(ps.last_points(stream=h), ps.original(ps.death), horizon, stream=h)

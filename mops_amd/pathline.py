@@ -132,29 +132,14 @@ class MOPSPathline:
             raise RuntimeError("follow_last=True but last_pts is None")
         return self._last_pt.copy()
 
-    def run(self, method: str = "rk4", delta_minutes: int = 1, record_every_minutes: int = 6,
-            sample_attributes: bool = False, density=None) -> list:
-        """All month pairs as one device-resident chain; the per-pair lines concatenated (later pairs
-        without their first sample), pyMOPSAPI.py:1396-1531.  Returns list[dict] with lineID, points
-        (M, 3), velocity (M, 3), temperature (M,), salinity (M,), lastPoint (3,).
-        ``sample_attributes``: temperature / salinity are the snapshot files' fields of those names sampled
-        along each line (PathlineChain.run(attrs=True)) instead of the reference's velocity x / y (quirk Q9);
-        a name the files do not carry stays zeros.
-        ``method``: "rk4" (the reference's, quirk Q1 included), "rk4_relocate" (this engine's RK4 that locates
-        each stage in its own cell, MOPS_RK4_RELOCATE: particles survive cell crossings; not with
-        ``sample_attributes``); any other string means Euler, as in the reference's caller.
-        ``density``: an engine.DensityMap or a list of them, filled with every pair's samples on the device
-        (PathlineChain.run(density=...)); a map of "temperature" / "salinity" needs ``sample_attributes``."""
+    def _make_chain(self, sample_attributes: bool = False):
+        """The PathlineChain over the month pairs' snapshots: timestamps read ahead, the mesh uploaded at the
+        first call, each snapshot read from its file and derived on the device when its pair needs it."""
         from .chain import PathlineChain
-        meth = {"rk4": L.MOPS_RK4, "rk4_relocate": L.MOPS_RK4_RELOCATE}.get(method.lower(), L.MOPS_EULER)
-        if meth == L.MOPS_RK4_RELOCATE and sample_attributes:
-            raise ValueError('sample_attributes is not supported with method="rk4_relocate"')
         from .engine import DeviceField, DeviceMesh, cell_to_vertex_attr
         from .mpas import MPASOReader, mesh_from_reader, snapshot_from_reader
         if self.pairs is None:
             raise RuntimeError("call set_time(...) before run()")
-        if self._depth is None:
-            raise RuntimeError("call set_seed(...) before run()")
         if self._grid is None:
             raise RuntimeError("call init(...) before run()")
         dates = [a for a, _ in self.pairs] + [self.pairs[-1][1]]
@@ -174,14 +159,38 @@ class MOPSPathline:
         def make_attrs(i, stream):  # (called right after make_field(i), on the same stream)
             return {k: cell_to_vertex_attr(self._mesh, v) for k, v in cell_attrs.pop(i).items()}
 
+        return PathlineChain(self._mesh, make_field, len(dates), timestamps=stamps, device=self.device,
+                             make_attrs=make_attrs if sample_attributes else None)
+
+    def run(self, method: str = "rk4", delta_minutes: int = 1, record_every_minutes: int = 6,
+            sample_attributes: bool = False, density=None) -> list:
+        """All month pairs as one device-resident chain; the per-pair lines concatenated (later pairs
+        without their first sample), pyMOPSAPI.py:1396-1531.  Returns list[dict] with lineID, points
+        (M, 3), velocity (M, 3), temperature (M,), salinity (M,), lastPoint (3,).
+        ``sample_attributes``: temperature / salinity are the snapshot files' fields of those names sampled
+        along each line (PathlineChain.run(attrs=True)) instead of the reference's velocity x / y (quirk Q9);
+        a name the files do not carry stays zeros.
+        ``method``: "rk4" (the reference's, quirk Q1 included), "rk4_relocate" (this engine's RK4 that locates
+        each stage in its own cell, MOPS_RK4_RELOCATE: particles survive cell crossings; not with
+        ``sample_attributes``); any other string means Euler, as in the reference's caller.
+        ``density``: an engine.DensityMap or a list of them, filled with every pair's samples on the device
+        (PathlineChain.run(density=...)); a map of "temperature" / "salinity" needs ``sample_attributes``."""
+        meth = {"rk4": L.MOPS_RK4, "rk4_relocate": L.MOPS_RK4_RELOCATE}.get(method.lower(), L.MOPS_EULER)
+        if meth == L.MOPS_RK4_RELOCATE and sample_attributes:
+            raise ValueError('sample_attributes is not supported with method="rk4_relocate"')
+        if self.pairs is None:
+            raise RuntimeError("call set_time(...) before run()")
+        if self._depth is None:
+            raise RuntimeError("call set_seed(...) before run()")
+        if self._grid is None:
+            raise RuntimeError("call init(...) before run()")
         seeds = self._seeds()
         pdep = None
         if self._particle_depths is not None:
             pdep = self._particle_depths
             if self._follow_last and not self._first_round:  # :1465-1469
                 pdep = np.clip(EARTH_RADIUS_M - np.linalg.norm(seeds, axis=1), 0.0, None).astype(np.float32)
-        chain = PathlineChain(self._mesh, make_field, len(dates), timestamps=stamps, device=self.device,
-                              make_attrs=make_attrs if sample_attributes else None)
+        chain = self._make_chain(bool(sample_attributes))
         res = chain.run(seeds, depth=self._depth, particle_depths=pdep,
                         method=meth,
                         delta_t=int(delta_minutes) * self._one_min,
@@ -197,3 +206,34 @@ class MOPSPathline:
         return [dict(lineID=i, points=out["points"][i], velocity=out["velocity"][i],
                      temperature=out["temperature"][i], salinity=out["salinity"][i], lastPoint=out["lastPoint"][i])
                 for i in range(out["points"].shape[0])]
+
+    def ftle(self, width: int, height: int, lat_range, lon_range, depth: float, method: str = "rk4_relocate",
+             delta_minutes: int = 1, record_every_minutes: int = 1440, horizon_days: float | None = None):
+        """The FTLE image of the month pairs set by ``set_time``: one particle per pixel of the ``width`` x
+        ``height`` window (engine.FlowMapLattice, seeded on the device: the pixel positions of a
+        ``MOPS_RunRemapping`` image of the same window), integrated at ``depth`` through every pair as one
+        device-resident chain that keeps no lines, and the finite-time Lyapunov exponent of the resulting flow
+        map -- a float64 CUDA tensor [height, width, 4] = {ftle per day, lambda_max, lambda_min, 1}, NaN where a
+        pixel has no valid stencil (land, a particle that died, fewer than two usable neighbours in a
+        direction).  A forward run (``set_time(direction="forward")``) shows where the flow pulls neighbours
+        apart, a backward run the attracting structures.  A particle that died in any pair is dropped
+        (chain.EverDead): one that dies in an early pair is re-seeded from its last record and would otherwise
+        pass for alive.  ``horizon_days``: the time the exponent is divided by (default: the sum of the pair
+        gaps, in days).  ``method``: as ``run``; the default "rk4_relocate" keeps its particles, while the
+        reference's "rk4" kills a particle at its first cell crossing (quirk Q1: two thirds of them within a
+        day at config 3), so its map is mostly NaN -- use it only to reproduce the reference's lines.  Does not
+        touch the state ``run`` keeps between calls (seeds, last points)."""
+        from .chain import EverDead
+        from .engine import FlowMapLattice
+        meth = {"rk4": L.MOPS_RK4, "rk4_relocate": L.MOPS_RK4_RELOCATE}.get(method.lower(), L.MOPS_EULER)
+        chain = self._make_chain(False)
+        if horizon_days is None:
+            horizon_days = sum(chain.gaps) / 86400.0
+        lattice = FlowMapLattice(width, height, lat_range, lon_range, device=self.device)
+        ever = EverDead()
+        res = chain.run(lattice.seeds, depth=float(depth), method=meth,
+                        delta_t=int(delta_minutes) * self._one_min,
+                        record_t=int(record_every_minutes) * self._one_min,
+                        direction=L.MOPS_FORWARD if self.direction == "forward" else L.MOPS_BACKWARD,
+                        follow_last=True, keep_lines=False, on_pair=ever)
+        return lattice.ftle(res["lastPoint"], ever.death(), horizon=float(horizon_days))

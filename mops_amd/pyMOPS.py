@@ -24,6 +24,9 @@ and, beyond the pybind module, the image output of the reference's C++ side:
                                                never reaches (MOPSApp.cpp:192)
     MOPS_RunDensity(lines, config, value=None) extension: the particle density map of returned lines,
                                                (H, W, 4) float64 {count, mean, sum, 1}
+    MOPS_LatticeSeeds(config)                  extension: one seed per pixel of the window, (H*W, 3)
+    MOPS_RunFTLE(lines, config, horizon)       extension: the FTLE image of lines seeded on that lattice,
+                                               (H, W, 4) float64 {ftle, lambda_max, lambda_min, 1}
 
 Every trajectory and every image goes through the HIP engine
 (``engine.run_trajectories`` / ``engine.remap_fixed_depth`` /
@@ -679,6 +682,62 @@ def MOPS_RunDensity(lines, config: VisualizationSettings, value=None):
                     val[i, :m] = v[:m]
             dmap.accumulate_lines(pts, val)
         return dmap.image(nan_empty=True).cpu().numpy()
+
+
+def _lattice(config, who: str):
+    """engine.FlowMapLattice of config's window, or None after Error() for invalid inputs."""
+    w, h = (int(config.imageSize[0]), int(config.imageSize[1])) if config is not None else (0, 0)
+    if config is None or w <= 0 or h <= 0:
+        _error(f"[MI355X::{who}] invalid inputs")
+        return None
+    try:
+        return _E.FlowMapLattice(w, h, config.LatRange, config.LonRange)
+    except ValueError as e:
+        _error(f"[MI355X::{who}] {e}")
+        return None
+
+
+def MOPS_LatticeSeeds(config: VisualizationSettings):
+    """Extension ("flow-map lattices and FTLE", include/mops_traj.h): one seed per pixel of ``config``'s window
+    (imageSize, LatRange, LonRange) as an (H*W, 3) float64 array, row major -- the positions MOPS_RunRemapping's
+    image has its pixels at, formed on the GPU (engine.FlowMapLattice).  Run them with MOPS_RunPathLine /
+    MOPS_RunStreamLine and give the lines, in this order, to MOPS_RunFTLE.  Invalid inputs: Error() and an empty
+    (0, 3) array."""
+    with _Timer("GPUKernel::LatticeSeeds", "GPUKernel"):
+        lat = _lattice(config, "LatticeSeeds")
+        return np.zeros((0, 3)) if lat is None else lat.seeds.cpu().numpy()
+
+
+def MOPS_RunFTLE(lines, config: VisualizationSettings, horizon: float):
+    """Extension: the finite-time Lyapunov exponent image of ``lines`` -- the list[dict] MOPS_RunPathLine /
+    MOPS_RunStreamLine return for the seeds of MOPS_LatticeSeeds(config), in that order -- on the GPU
+    (engine.FlowMapLattice.ftle): the flow map is ``points[0]`` -> ``lastPoint`` of each line.  No death array is
+    passed: a dead line has a zero ``lastPoint``, which is not valid.  One [H, W, 4] float64 array {ftle,
+    lambda_max, lambda_min, 1}, NaN where a pixel has no valid stencil, usable with SaveToPNG and SaveVTI.
+    ``horizon`` > 0: the integration time in the unit the exponent is wanted per.  Invalid inputs (a line count
+    other than H * W, a line without ``points`` / ``lastPoint``, a bad horizon): Error() and an empty image."""
+    with _Timer("GPUKernel::FTLE", "GPUKernel"):
+        lat = _lattice(config, "FTLE")
+        if lat is None:
+            return np.zeros((0, 0, 4))
+        lines = list(lines) if lines is not None else None
+        try:
+            hz = float(horizon)
+        except (TypeError, ValueError):
+            hz = float("nan")
+        if (lines is None or len(lines) != lat.n or not (np.isfinite(hz) and hz > 0.0)
+                or any("points" not in ln or "lastPoint" not in ln for ln in lines)):
+            _error("[MI355X::FTLE] invalid inputs")
+            return np.zeros((0, 0, 4))
+        seeds = np.zeros((lat.n, 3))
+        last = np.zeros((lat.n, 3))
+        for i, ln in enumerate(lines):
+            q = np.asarray(ln["points"], dtype=np.float64).reshape(-1, 3)
+            if q.shape[0]:  # (a line without points keeps zeros, which are not valid)
+                seeds[i] = q[0]
+                last[i] = np.asarray(ln["lastPoint"], dtype=np.float64).reshape(3)
+        lat.seeds.copy_(lat.torch.as_tensor(seeds))  # points[0] of each line (the lattice seed itself, from a run)
+        return lat.ftle(last, None, hz).cpu().numpy()
 
 
 def SaveToPNG(image, filename: str, channel: int = 3) -> bool:
