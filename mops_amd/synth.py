@@ -204,11 +204,23 @@ def _flip_edges(pts, T, n_flips: int, seed: int, max_deg: int):
 
 def make_mesh(n: int, n_levels: int = 60, land: str = "continents", max_edges: int = 7,
               jitter: float = 0.05, seed: int = 7, radius: float = SPHERE_RADIUS,
-              total_depth: float = 4000.0, flips: int = 0, edges: bool = True) -> Mesh:
+              total_depth: float = 4000.0, flips: int = 0, edges: bool = True, triangulation=None) -> Mesh:
     """``flips``: diagonal flips that give the mesh heptagons (and pentagons), see _flip_edges;
-    ``edges``: also build the edge arrays (edgesOnCell, cellsOnEdge, edgeCoord)."""
-    pts, T = geodesic_triangulation(n, jitter=jitter, seed=seed)
-    T = _flip_edges(pts, T, flips, seed + 101, max_edges)
+    ``edges``: also build the edge arrays (edgesOnCell, cellsOnEdge, edgeCoord);
+    ``triangulation``: ``(points [P, 3] on the unit sphere, triangles [T, 3] counter-clockwise from outside)``
+    to take the dual of in place of the geodesic one (``n``, ``jitter``, ``seed`` and ``flips`` are then
+    unused).  A Delaunay triangulation gives a true Voronoi mesh: convex cells of any degree up to
+    ``max_edges`` that contain their own centres, which flipped diagonals do not give."""
+    if triangulation is None:
+        pts, T = geodesic_triangulation(n, jitter=jitter, seed=seed)
+        T = _flip_edges(pts, T, flips, seed + 101, max_edges)
+    else:
+        pts = np.ascontiguousarray(triangulation[0], dtype=np.float64)
+        T = np.ascontiguousarray(triangulation[1]).astype(np.int64)
+        if pts.ndim != 2 or pts.shape[1] != 3 or T.ndim != 2 or T.shape[1] != 3:
+            raise ValueError("triangulation must be (points [P, 3], triangles [T, 3])")
+        if T.min() < 0 or T.max() >= pts.shape[0]:
+            raise ValueError("triangle corner out of range")
     P = pts.shape[0]
     a, b, c = pts[T[:, 0]], pts[T[:, 1]], pts[T[:, 2]]
     cc = np.cross(b - a, c - a)

@@ -3,7 +3,8 @@ __graft_entry__.build_reference() where the reference's sources are present).
 
 The file holds, per case of tests/ref_case.py's golden catalogue (16 trajectory combinations on the small mesh,
 two z-level and two heptagon-mesh cases, one with seeds exactly on edge planes, one fixed-latitude and one
-fixed-layer image) and per output array:
+fixed-layer image; per wheel mesh of tests/wide_case.py four trajectory modes, a fixed-latitude row and a fixed-layer
+window, with one stored line each) and per output array:
 the SHA-256 of the array's bytes, its shape and dtype, its first 4 lines (image rows) raw, and the outcome
 counts (dead / alive particles, finite / NaN pixels).  Case inputs are regenerated from mops_amd.synth with
 fixed seeds and are not stored.  Run:  python tests/golden/make_reference_pin.py

@@ -14,9 +14,13 @@ import json
 import os
 import struct
 import subprocess
+import sys
 import tempfile
 
 import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import wide_case as WC  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVER = os.path.join(ROOT, "oracle", "_ref", "mops_ref_driver")
@@ -160,6 +164,8 @@ def lines_from_result(res):
 def world(key):
     """(mesh, snapshot 0, snapshot 1) of one catalogue mesh, built from mops_amd.synth with fixed seeds."""
     from mops_amd import synth
+    if key in WC.KEYS:     # the wheel meshes, whose cells of 7 to 20 vertices are alive (tests/wide_case.py)
+        return WC.world(key)
     if key in ("small", "small_z"):
         mesh = synth.make_mesh(16, n_levels=10) if key == "small" else world("small")[0]
         topo = "sigma" if key == "small" else "zlevel"
@@ -173,7 +179,7 @@ def world(key):
             synth.make_snapshot(mesh, timestep=1, phase=0.35, topography=topo))
 
 
-WORLDS = ("small", "small_z", "hept", "edges10")
+WORLDS = ("small", "small_z", "hept", "edges10") + WC.KEYS
 Traj = collections.namedtuple("Traj", "world pathline euler backward seeds depth depths delta_t duration record_t")
 
 
@@ -243,6 +249,8 @@ def seed_set(name, world_key):
         return np.concatenate([edge_seeds(world(world_key)[0]), synth.uniform_band_seeds(100, seed=5)]), None
     if name == "dense":
         return dense_seeds(world(world_key)[0], world_key == "small_z")
+    if name == "wide":          # whole waves in hexagons and in wide cells, mixed waves, seeds on wide cells' boundaries
+        return WC.seeds(world_key), None
     raise KeyError(name)
 
 
@@ -268,9 +276,19 @@ def _traj_cases():
     cases["dense_pathline_euler"] = Traj("small", True, True, False, "dense", 0.0, None, 120, 43200, 3600)
     cases["dense_pathline_rk4_backward"] = Traj("small", True, False, True, "dense", 0.0, None, 120, 43200, 3600)
     cases["edges10_pathline_rk4"] = Traj("edges10", True, False, False, "band300", 300.0, None, 120, 43200, 3600)
+    # the wheel meshes: {stream, path} x {Euler, RK4} x {forward, backward} each; four of the eight are golden
+    for key in WC.KEYS:
+        for mode in WC.MODES:
+            pathline, euler, backward = mode
+            name = f"{key}_{WC.mode_name(*mode)}"
+            cases[name] = Traj(key, pathline, euler, backward, "wide", WC.DEPTH, None, *WC.times(euler))
+            if name.endswith(WIDE_GOLDEN_MODES):
+                golden.append(name)
     return cases, golden
 
 
+# every value of each of the three choices twice (the golden file is to stay below oracle_small.npz's size)
+WIDE_GOLDEN_MODES = ("path_euler_forward", "path_rk4_backward", "stream_euler_backward", "stream_rk4_forward")
 TRAJ_CASES, GOLDEN_TRAJ = _traj_cases()
 LINE_FIELDS = ("points", "velocity", "temperature", "salinity", "lastPoint", "depth", "cells")
 
@@ -292,6 +310,14 @@ LAYER_WINDOWS = ("global_800", "box_0")
 # test_reference_pin.test_fixed_depth_reference_cpu_path_writes_no_pixel); its cell map is pinned with fixed_layer's.
 GOLDEN_IMAGES = {"latitude_lat_20": ("fixed_latitude", "lat_20"), "layer_box_0_4": ("fixed_layer", ("box_0", 4))}
 GOLDEN_WORLDS = ("small", "small_z", "hept")
+# the wheel meshes' images: a fixed-latitude row through the centres of a pair of wheels and a fixed-layer image of
+# the window that holds the other wheels, (kind, (world, wide_case row or window))
+WIDE_IMAGES = {f"{key}_{kind}_{name}": ("fixed_" + kind, (key, name))
+               for key in WC.KEYS for kind, name in (("latitude", "lat_0"), ("latitude", "lat_25"), ("latitude", "lat_m35"), ("layer", "pacific"),
+                                                     ("layer", "atlantic"), ("layer", "south"))}
+WIDE_GOLDEN_IMAGES = {n: v for n, v in WIDE_IMAGES.items() if n.endswith(("latitude_lat_0", "layer_south"))}
+# the entries reference_pin.npz had before the wheel meshes: they come first in the file and keep their bytes
+LEGACY_GOLDEN = 23
 
 
 def traj_op(name):
@@ -311,6 +337,24 @@ def image_op(kind, key):
     win_key, layer = key
     w, h, win, _ = DEPTH_CASES[win_key]
     return dict(op=kind, width=w, height=h, window=win, value=float(layer))
+
+
+def wide_image_op(kind, key):
+    world_key, name = key
+    if kind == "fixed_latitude":
+        w, h, lon, lat = WC.LATITUDES[name]
+        return dict(op=kind, width=w, height=h, window=((0.0, 0.0), lon), value=lat)
+    w, h, win = WC.WINDOWS[name]
+    return dict(op=kind, width=w, height=h, window=win, value=float(WC.IMAGE_LAYER))
+
+
+def wide_restated_image(kind, key):
+    """restated_image for a wheel mesh's image case."""
+    world_key, name = key
+    if kind == "fixed_latitude":
+        return WC.restated_latitude(world_key, name)["image"][None], None
+    w, h, _ = WC.WINDOWS[name]
+    return WC.restated_layer(world_key, name)["image"][None], WC.window_cells(world_key, name).astype(np.int64).reshape(h, w)
 
 
 # ---- the oracle and the Python restatements on the same cases ---------------------------------------------
@@ -398,14 +442,14 @@ def digest(a):
     return hashlib.sha256(a.astype(a.dtype.newbyteorder("<"), copy=False).tobytes()).hexdigest()
 
 
-def golden_entries(case, arrays, outcome):
-    """One case's record: per array its SHA-256, shape and dtype, its first 4 lines (rows) raw, and the outcome
-    counts.  ``pack_golden`` turns the records of all cases into the npz entries."""
+def golden_entries(case, arrays, outcome, lines=4):
+    """One case's record: per array its SHA-256, shape and dtype, its first ``lines`` lines (rows) raw, and the
+    outcome counts.  ``pack_golden`` turns the records of all cases into the npz entries."""
     rec = {"outcome": [int(x) for x in outcome], "arrays": {}, "samples": {}}
     for k, a in arrays.items():
         a = np.ascontiguousarray(a)
         rec["arrays"][k] = {"sha256": digest(a), "shape": list(a.shape), "dtype": a.dtype.str}
-        rec["samples"][k] = sample(k, a)
+        rec["samples"][k] = sample(k, a, lines)
     return {case: rec}
 
 
@@ -413,7 +457,8 @@ def pack_golden(records):
     """npz entries: ``meta`` (JSON: per case the outcome and per array digest, shape, dtype and the sample's
     shape and offset) and ``samples`` (all stored lines, as the bytes of their own dtypes, back to back)."""
     meta, blob = {}, bytearray()
-    for case in sorted(records):
+    wide = set(WIDE_GOLDEN_IMAGES) | {n for n in records if n in TRAJ_CASES and TRAJ_CASES[n].world in WC.KEYS}
+    for case in sorted(records, key=lambda c: (c in wide, c)):   # the wheel meshes' entries after all others
         rec = records[case]
         meta[case] = {"outcome": rec["outcome"], "arrays": {}}
         for k in sorted(rec["arrays"]):
@@ -451,9 +496,9 @@ class Golden:
             m["sample_shape"])
 
 
-def sample(key, a):
-    """The first 4 lines of a trajectory field, or the first 4 rows of image 0."""
-    return np.ascontiguousarray(a[0, :4] if key == "images" else a[:4])
+def sample(key, a, lines=4):
+    """The first ``lines`` lines of a trajectory field, or rows of image 0: 4 per entry, 1 for the wheel meshes'."""
+    return np.ascontiguousarray(a[0, :lines] if key == "images" else a[:lines])
 
 
 def describe_mismatch(golden, case, key, got):
@@ -462,7 +507,8 @@ def describe_mismatch(golden, case, key, got):
     m = golden.meta[case]["arrays"][key]
     if list(got.shape) != m["shape"] or got.dtype.str != m["dtype"]:
         return f"{case} {key}: shape / dtype {got.shape} {got.dtype.str}, golden {m['shape']} {m['dtype']}"
-    want, have = golden.stored_sample(case, key), sample(key, got)
+    want = golden.stored_sample(case, key)
+    have = sample(key, got, want.shape[0])
     for i in range(want.shape[0]):
         if not np.array_equal(want[i], have[i], equal_nan=want.dtype.kind == "f"):
             bad = np.argwhere(~((want[i] == have[i]) | ((want[i] != want[i]) & (have[i] != have[i]))))[0]
@@ -475,7 +521,7 @@ def reference_golden(driver):
     """The entries of reference_pin.npz, from the compiled reference."""
     entries = {}
     for wk in GOLDEN_WORLDS:
-        names = [n for n in GOLDEN_TRAJ if TRAJ_CASES[n].world == wk]
+        names = [n for n in GOLDEN_TRAJ if TRAJ_CASES[n].world == wk]  # (none of the wheel meshes')
         images = list(GOLDEN_IMAGES.items()) if wk == "small" else []
         mesh, s0, s1 = world(wk)
         res = run_driver(driver, mesh, (s0, s1), [traj_op(n) for n in names] + [image_op(*v) for _, v in images])
@@ -485,4 +531,15 @@ def reference_golden(driver):
         for (n, _), r in zip(images, res[len(names):]):
             arrays = {k: r[k] for k in ("images", "cells") if k in r}
             entries.update(golden_entries(n, arrays, pixel_outcome(r["images"])))
+    for wk in WC.KEYS:
+        names = [n for n in GOLDEN_TRAJ if TRAJ_CASES[n].world == wk]
+        images = [(n, v) for n, v in WIDE_GOLDEN_IMAGES.items() if v[1][0] == wk]
+        mesh, s0, s1 = world(wk)
+        res = run_driver(driver, mesh, (s0, s1), [traj_op(n) for n in names] + [wide_image_op(*v) for _, v in images])
+        for n, r in zip(names, res):
+            lines = lines_from_result(r)
+            entries.update(golden_entries(n, {k: lines[k] for k in LINE_FIELDS}, line_outcome(n, lines), lines=1))
+        for (n, _), r in zip(images, res[len(names):]):
+            arrays = {k: r[k] for k in ("images", "cells") if k in r}
+            entries.update(golden_entries(n, arrays, pixel_outcome(r["images"]), lines=1))
     return pack_golden(entries)

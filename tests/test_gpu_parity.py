@@ -522,7 +522,8 @@ def test_order_is_permutation_and_result_invariant(gpu, dev_small, small_case):
 @pytest.mark.parametrize("max_edges", [10, 16, 20])
 def test_wide_stencil_instantiations(gpu, engine_lib, oracle_lib, max_edges):
     """maxEdges > 7 selects the MAXV 12 / 20 kernels (no register polygon
-    cache, fewer waves); results must not depend on the padding width."""
+    cache, fewer waves); results must not depend on the padding width.  The mesh is only padded: its cells have 5
+    and 6 vertices.  Cells of 8 to 20 vertices are tests/test_wide_cells_gpu.py's."""
     from mops_amd import synth
     from mops_amd.engine import DeviceField, DeviceMesh, TrajectoryConfig, run_trajectories
     mesh = synth.make_mesh(16, n_levels=10, max_edges=max_edges)
@@ -720,10 +721,11 @@ def test_zlevel_topography_partial_bottom(gpu, engine_lib, oracle_lib, method):
 
 
 def test_heptagon_cells_all_modes(gpu, engine_lib, oracle_lib):
-    """maxEdges 7 with heptagons (diagonal flips): the MAXV 7 kernels keep the IsInMesh
-    normals of polygon slots 0-4 in LDS and compute slots 5-6 per evaluation
-    (MOPS_NRM_SLOTS), so seeds are placed in and around the
-    heptagon (and pentagon) cells; every mode bit-exact against the oracle."""
+    """maxEdges 7 with flipped heptagons (diagonal flips): location in heptagons, their death at step 0, and
+    live pentagons, in every mode bit-exact against the oracle.  The flipped triangulation is not Delaunay: none of
+    the 74 heptagons contains its own centre (tests/test_wide_cells_cpu.py), and all 302 seeds located in one die
+    at step 0 in every mode, as asserted below from the oracle.  No value is computed on seven vertices here; the
+    MAXV 7 kernels' slots 5-6 (MOPS_NRM_SLOTS) on live heptagons are tests/test_wide_cells_gpu.py's."""
     from mops_amd import synth
     from mops_amd.engine import DeviceField, DeviceMesh, TrajectoryConfig, run_trajectories
     mesh = synth.make_mesh(16, n_levels=10, flips=40)
@@ -749,3 +751,6 @@ def test_heptagon_cells_all_modes(gpu, engine_lib, oracle_lib):
             assert_lines_match(got, ref, f"heptagons path={back is not None} method={method}")
             in_hept = np.isin(got["cells"], np.flatnonzero(nv == 7))
             assert in_hept.sum() >= 20
+            in_pent = np.isin(got["cells"], np.flatnonzero(nv == 5))
+            assert int(in_hept.sum()) == 302 and int((ref["death"][in_hept] == 0).sum()) == 302
+            assert int(in_pent.sum()) == 354 and int((ref["death"][in_pent] != 0).sum()) == 353

@@ -6,6 +6,12 @@ are x86-64 doubles without contraction and call the same libm.  Where neither th
 sources are present those comparisons skip; the golden checks at the end always run and pin the oracle and the
 restatements to digests recorded from the compiled reference (tests/golden/reference_pin.npz).
 
+The wheel meshes of tests/wide_case.py (cells of 7 to 20 vertices that contain their own centres, maxEdges 7, 12 and
+20) are pinned like the small mesh: derived fields, location, the eight trajectory modes, fixed-latitude rows through
+wheel centres and fixed-layer images of the wheel windows.  On the flipped-heptagon mesh ("hept") and the padded one
+("edges10") no particle lives in a cell of more than six vertices (tests/test_wide_cells_cpu.py), so those cases
+pin location, death at step 0 and padding only.
+
 One operation is not pinned: Kernel::VisualizeFixedDepth.  Its CPU path hands each image's std::vector to
 SetPixel by value, so the compiled reference writes every pixel into a temporary and returns the images as it
 got them (test_fixed_depth_reference_cpu_path_writes_no_pixel); only its cell map can be compared.
@@ -19,6 +25,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ref_case as RC  # noqa: E402
+import wide_case as WC  # noqa: E402
 
 
 def _same(a, b, what):
@@ -58,6 +65,17 @@ def _locate_sets(mesh):
     return {"band": synth.uniform_band_seeds(3000, seed=31, max_abs_lat=89.0), "lattice": lattice, "centres": centres}
 
 
+def _wide_locate_points(key):
+    """The trajectory seeds without the boundary seeds (a vertex has three nearest centres), the wide cells' centres
+    and the pixel positions of the three windows."""
+    import remap_reference as RR
+    mesh = WC.load_mesh(key)
+    seeds, n_b = WC.seeds(key), len(WC.boundary_seeds(key))
+    cc = np.asarray(mesh.cellCoord, dtype=np.float64).reshape(-1, 3)
+    return np.concatenate([seeds[:len(seeds) - 200 - n_b], seeds[len(seeds) - 200:], cc[WC.degrees(mesh) >= 7]]
+                          + [RR.depth_positions(w, h, lat, lon) for w, h, (lat, lon) in WC.WINDOWS.values()])
+
+
 @pytest.fixture(scope="module")
 def runs(driver):
     """One driver run per catalogue mesh with everything asked of it; results by name."""
@@ -77,6 +95,11 @@ def runs(driver):
             for win in RC.LAYER_WINDOWS:
                 for value, _ in RC.LAYERS:
                     ops.append(RC.image_op("fixed_layer", (win, value))); keys.append(("fixed_layer", (win, value)))
+        if wk in WC.KEYS:
+            ops.append(dict(op="locate", points=_wide_locate_points(wk))); keys.append(("locate", wk))
+            for name, (kind, key) in RC.WIDE_IMAGES.items():
+                if key[0] == wk:
+                    ops.append(RC.wide_image_op(kind, key)); keys.append(("wide_image", name))
         out.update(zip(keys, RC.run_driver(driver, mesh, (s0, s1), ops)))
     return out
 
@@ -116,6 +139,17 @@ def test_locate_matches_compiled_reference(runs, oracle):
         assert got.shape == (len(pts),)
         _same(got, d2.argmin(axis=1).astype(np.int64), f"locate {k}: reference against brute force")
         _same(got, oracle.knn(mesh, pts).astype(np.int64), f"locate {k}")
+
+
+@pytest.mark.parametrize("key", WC.KEYS)
+def test_locate_on_wheel_meshes_matches_compiled_reference(runs, oracle, key):
+    """calcInWhichCells on the wheel meshes, whose ring cells are a quarter of a hexagon across: the trajectory
+    seeds, the wide cells' own centres and every pixel of the three windows."""
+    mesh = WC.load_mesh(key)
+    pts = _wide_locate_points(key)
+    got = runs[("locate", key)]["cells"]
+    assert got.shape == (len(pts),) and (WC.degrees(mesh)[got] >= 7).sum() >= 1000
+    _same(got, oracle.knn(mesh, pts).astype(np.int64), f"locate {key}")
 
 
 # ---- trajectories -----------------------------------------------------------------------------------------
@@ -204,6 +238,21 @@ def test_fixed_layer_matches_compiled_reference(runs, oracle, capsys, win):
     assert not np.array_equal(seen[0], seen[4], equal_nan=True) and not np.array_equal(seen[4], seen[9], equal_nan=True)
 
 
+@pytest.mark.parametrize("name", list(RC.WIDE_IMAGES))
+def test_wheel_mesh_images_match_compiled_reference(runs, oracle, capsys, name):
+    """VisualizeFixedLatitude along rows through wheel centres and VisualizeFixedLayer on the wheel windows: the
+    restatements' images, and the cell map, on cells of 7 to 20 vertices."""
+    kind, key = RC.WIDE_IMAGES[name]
+    res = runs[("wide_image", name)]
+    finite, nan = _assert_coverage(res["images"])
+    _report(capsys, f"{name}: {finite} of {finite + nan} pixels finite")
+    restated, cells = RC.wide_restated_image(kind, key)
+    _same(restated, res["images"], name)
+    assert np.all(res["images"][..., 3] == 1.0)
+    if cells is not None:
+        _same(res["cells"], cells, f"{name} cell map")
+
+
 # ---- RemoveNaN --------------------------------------------------------------------------------------------
 def _nan_cases():
     path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "remove_nan_cases.json")
@@ -233,15 +282,38 @@ def golden():
     return RC.Golden()
 
 
-GOLDEN_CASES = RC.GOLDEN_TRAJ + list(RC.GOLDEN_IMAGES)
+GOLDEN_CASES = RC.GOLDEN_TRAJ + list(RC.GOLDEN_IMAGES) + list(RC.WIDE_GOLDEN_IMAGES)
 
 
 def test_golden_catalogue(golden):
     """16 trajectory combinations on the small mesh, two z-level and two heptagon cases, the seeds on edge
-    planes, two images; the file no larger than the largest fixture beside it."""
-    assert golden.cases() == sorted(GOLDEN_CASES) and len(RC.GOLDEN_TRAJ) == 21
+    planes, two images; per wheel mesh four trajectory modes, a fixed-latitude and a fixed-layer image; the file
+    no larger than the largest fixture beside it."""
+    assert golden.cases() == sorted(GOLDEN_CASES) and len(RC.GOLDEN_TRAJ) == 21 + 4 * len(WC.KEYS)
     assert sum(n.startswith("small_") and "_edge_" not in n for n in RC.GOLDEN_TRAJ) == 16
+    wide = [n for n in GOLDEN_CASES if n.startswith(WC.KEYS)]
+    assert len(wide) == 6 * len(WC.KEYS) and len(GOLDEN_CASES) - len(wide) == RC.LEGACY_GOLDEN
+    for key in WC.KEYS:   # both values of each of the three choices, twice
+        modes = [n for n in RC.GOLDEN_TRAJ if n.startswith(key + "_")]
+        assert all(sum(word in n for n in modes) == 2 for word in ("path", "stream", "euler", "rk4", "forward", "backward"))
     assert os.path.getsize(RC.GOLDEN) <= os.path.getsize(os.path.join(os.path.dirname(RC.GOLDEN), "oracle_small.npz"))
+
+
+def test_golden_entries_from_before_the_wheel_meshes_keep_their_bytes(golden):
+    """The 23 entries recorded before the wheel meshes were added stand first in the file, with the same digests,
+    outcomes, sample offsets and sample bytes: SHA-256 of their part of the metadata and of the sample blob."""
+    import hashlib
+    legacy = {c: golden.meta[c] for c in golden.cases() if not c.startswith(WC.KEYS)}
+    assert len(legacy) == RC.LEGACY_GOLDEN
+    assert hashlib.sha256(json.dumps(legacy, sort_keys=True).encode()).hexdigest() == \
+        "46a65006aec6a0579ed8e79efcdeb5acf1af7bd4bcb8120b251aedaa08f2e4dc"
+    end = max(m["sample_offset"] + int(np.prod(m["sample_shape"])) * np.dtype(m["dtype"]).itemsize
+              for rec in legacy.values() for m in rec["arrays"].values())
+    first_wide = min(m["sample_offset"] for c in golden.cases() if c.startswith(WC.KEYS)
+                     for m in golden.meta[c]["arrays"].values())
+    assert end == first_wide == 84256
+    assert hashlib.sha256(golden.blob[:end]).hexdigest() == \
+        "a45563b2cb4f5efab455bba82e52ca079725881fa7c0ead26b69ba7a0a289a7d"
 
 
 def test_golden_is_what_the_compiled_reference_gives(driver, golden):
@@ -258,7 +330,10 @@ def test_oracle_and_restatements_hash_to_the_golden(oracle, golden, case):
         got = RC.oracle_lines(case)
         assert RC.line_outcome(case, got) == golden.outcome(case)
     else:
-        images, cells = RC.restated_image(*RC.GOLDEN_IMAGES[case])
+        if case in RC.WIDE_GOLDEN_IMAGES:
+            images, cells = RC.wide_restated_image(*RC.WIDE_GOLDEN_IMAGES[case])
+        else:
+            images, cells = RC.restated_image(*RC.GOLDEN_IMAGES[case])
         got = {"images": images} if cells is None else {"images": images, "cells": cells}
         assert RC.pixel_outcome(images) == golden.outcome(case)
     assert sorted(got) == golden.keys(case)

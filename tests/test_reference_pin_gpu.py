@@ -1,7 +1,9 @@
 """The GPU engine against digests recorded from the compiled reference (tests/golden/reference_pin.npz, written by
 tests/golden/make_reference_pin.py): the golden catalogue of tests/ref_case.py -- 16 trajectory combinations on
 the small mesh, two z-level and two heptagon-mesh cases, the seeds on edge planes, a fixed-latitude and a
-fixed-layer image -- through run_trajectories, remap_fixed_latitude and remap_fixed_layer.  Every output array
+fixed-layer image, and per wheel mesh (tests/wide_case.py: live cells of 7 to 20 vertices, maxEdges 7 / 12 / 20)
+four trajectory modes, a fixed-latitude row through wheel centres and a fixed-layer image of a wheel window --
+through run_trajectories, remap_fixed_latitude and remap_fixed_layer.  Every output array
 must hash to the recorded SHA-256 and the outcome counts (dead / alive particles, finite / NaN pixels) must be
 the recorded ones.
 
@@ -23,7 +25,7 @@ import ref_case as RC  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 ENGINE_LINE_FIELDS = ("points", "velocity", "temperature", "salinity", "lastPoint", "cells")
-GOLDEN_CASES = RC.GOLDEN_TRAJ + list(RC.GOLDEN_IMAGES)
+GOLDEN_CASES = RC.GOLDEN_TRAJ + list(RC.GOLDEN_IMAGES) + list(RC.WIDE_GOLDEN_IMAGES)
 
 
 @pytest.fixture(scope="module")
@@ -57,6 +59,20 @@ def _engine_lines(device, name):
     return out
 
 
+def _engine_wide_image(device, kind, key):
+    from mops_amd import engine
+    import wide_case as WC
+    world_key, name = key
+    dm, f0, _ = device(world_key)
+    mesh = RC.world(world_key)[0]
+    if kind == "fixed_latitude":
+        w, h, lon, lat = WC.LATITUDES[name]
+        return {"images": engine.remap_fixed_latitude(dm, f0, w, h, lon, lat, WC.depth_range(mesh)).cpu().numpy()[None]}
+    w, h, (lat, lon) = WC.WINDOWS[name]
+    image, cells = engine.remap_fixed_layer(dm, f0, w, h, lat, lon, WC.IMAGE_LAYER, return_cells=True)
+    return {"images": image.cpu().numpy()[None], "cells": cells.cpu().numpy().astype(np.int64)}
+
+
 def _engine_image(device, kind, key):
     from mops_amd import engine
     dm, f0, _ = device("small")
@@ -75,7 +91,10 @@ def _host_side(case):
     """The oracle's (restatement's) arrays for one case, computed on this machine."""
     if case in RC.TRAJ_CASES:
         return RC.oracle_lines(case)
-    images, cells = RC.restated_image(*RC.GOLDEN_IMAGES[case])
+    if case in RC.WIDE_GOLDEN_IMAGES:
+        images, cells = RC.wide_restated_image(*RC.WIDE_GOLDEN_IMAGES[case])
+    else:
+        images, cells = RC.restated_image(*RC.GOLDEN_IMAGES[case])
     return {"images": images} if cells is None else {"images": images, "cells": cells}
 
 
@@ -100,7 +119,10 @@ def test_engine_hashes_to_the_reference_golden(device, golden, case):
         assert set(got) == set(golden.keys(case)) - {"depth"}  # a line's depth is the input, not an engine output
         outcome = RC.line_outcome(case, got)
     else:
-        got = _engine_image(device, *RC.GOLDEN_IMAGES[case])
+        if case in RC.WIDE_GOLDEN_IMAGES:
+            got = _engine_wide_image(device, *RC.WIDE_GOLDEN_IMAGES[case])
+        else:
+            got = _engine_image(device, *RC.GOLDEN_IMAGES[case])
         assert sorted(got) == golden.keys(case)
         outcome = RC.pixel_outcome(got["images"])
     check_against_golden(golden, case, got, outcome)
