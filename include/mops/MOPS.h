@@ -152,6 +152,13 @@ struct TrajectorySettings {
     // kEuler it has no effect (Euler has no stages).  MOPS_RunStreamLine with it and kRK4, and MOPS_RunPathLine
     // with it, kRK4 and sampleAttributes, follow the reference's error convention: Error() and an empty list.
     bool relocateStages = false;
+    // This engine's extension, the layer mode (mops_traj_advance_layer, mops_traj.h; default -1: the depth mode).
+    // >= 0: MOPS_RunStreamLine / MOPS_RunPathLine advect within that model layer -- the Wachspress-weighted vertex
+    // velocity of the layer (TBBKernel::CalcVelocity), w = 0, a particle dying where that velocity is shorter than
+    // 1e-12 -- and `depth` is still carried, because the records keep their radius.  relocateStages then applies
+    // to streamlines as well.  A layer outside [0, nVertLevels), or sampleAttributes with it, follows the
+    // reference's error convention: Error() and an empty list.
+    int fixedLayer = -1;
 };
 
 struct SamplingSettings {

@@ -305,6 +305,48 @@ mops_status mops_traj_advance(const mops_mesh* mesh, const mops_field* front, co
                               int64_t step_begin, int64_t step_end, double* d_records,
                               int64_t record_stride, void* stream);
 
+/* ---- fixed-layer streamlines and pathlines -------------------------------- */
+
+/* Advection within ONE model layer k (0 <= k < nVertLevels): the StreamLine / PathLine loop of
+ * mops_traj_advance -- the one-hop walk, the Euler rotation, the RK4 stage positions, stage alphas, mean and
+ * chord step, the two recording rules, the step-0 pre-writes, the death bookkeeping, the zero-filled
+ * unsampled slots -- with calc_velocity_at replaced by the layer evaluation:
+ *   1. the reference's cell guards, TBBKernel::IsInMesh and the Wachspress weights of the cell;
+ *   2. h_f = sum_v w_v * cellVertexVelocity_front[v*L + k], in the reference's vertex order
+ *      (TBBKernel::CalcVelocity, TBBKernel.h:128-147); a streamline takes h = h_f, a pathline forms h_b the
+ *      same way from the back snapshot and h = h_b*alpha + h_f*(1 - alpha), in that order;
+ *   3. the evaluation fails, and the particle dies at that step, where |h| < 1e-12 with
+ *      |h| = sqrt((x*x + y*y) + z*z).  For streamlines that is the reference's own rule
+ *      (MPASOVisualizerKernels.cpp:838-852); for pathlines it is THIS ENGINE'S CHOICE (the reference's pathline
+ *      has no such test), so that particles over land die instead of sitting still for the rest of the run;
+ *   4. the vertical velocity is 0.0: zTop and cellVertexVertVelocity are never read.
+ * The vertical-update lines are kept with w = 0, so the depth stays what the caller gave (a negative depth
+ * becomes 0, as the reference's max(0, .) makes it) and the position is renormalised to its radius each step.
+ * With fields whose vertex zTop column is exactly 0, -100, -200, ... and whose w is zero, a depth-0 run of
+ * mops_traj_advance is a layer-0 run (its bracket blends level 0 with weight 1.0 exactly).
+ *
+ * cfg->method: MOPS_RK4 evaluates the stages in the step's start cell (quirk Q1); MOPS_RK4_RELOCATE locates
+ * each of stages 2-4 as mops_traj_advance does for pathlines -- here for streamlines as well (the refusals of
+ * the depth entries are unchanged).
+ *
+ * A layer slice is one snapshot's velocity at layer k as a compact per-vertex array in the engine's own vertex
+ * order: opaque to the caller, mops_layer_velocity_bytes(mesh) bytes of device memory, 16-byte aligned.
+ * mops_field_layer_velocity writes it (asynchronous on `stream`; rebuild it whenever the field is rebuilt);
+ * MOPS_ERR_INVALID before any launch for a null pointer, a field of another mesh or a layer outside
+ * [0, nVertLevels). */
+int64_t mops_layer_velocity_bytes(const mops_mesh* mesh);
+mops_status mops_field_layer_velocity(const mops_mesh* mesh, const mops_field* field, int32_t layer, void* d_out,
+                                      void* stream);
+
+/* mops_traj_advance in layer mode: d_front_layer / d_back_layer are layer slices of the same layer
+ * (d_back_layer NULL = a streamline).  Particles, step ranges, records, d_order / d_n_live, re-sorts between
+ * calls and the 32-bit ranges are those of mops_traj_advance; the kernel reads the mesh and the two slices
+ * only.  One lane per particle, no cooperative tile, no capture, no attribute channel.  MOPS_ERR_INVALID
+ * before any launch for a null d_front_layer. */
+mops_status mops_traj_advance_layer(const mops_mesh* mesh, const void* d_front_layer, const void* d_back_layer,
+                                    const mops_traj_cfg* cfg, const mops_particles* particles, int64_t step_begin,
+                                    int64_t step_end, double* d_records, int64_t record_stride, void* stream);
+
 /* FinalizeTrajectoryLines[WithAttrs] + RemoveNaNTrajectoriesAndReindex
  * (src/Common/TrajectoryCommon.h:57-190) on the device: seeds [n*3] and
  * records -> points/velocity [n*(K+1)*3], temperature/salinity [n*(K+1)]
@@ -726,6 +768,16 @@ mops_status mops_run_trajectories(const mops_mesh* mesh, const mops_field* front
                                   double* h_velocity, double* h_temperature, double* h_salinity,
                                   double* h_last_point, double* h_final_pos, float* h_final_depth,
                                   int32_t* h_death_step, void* stream);
+
+/* mops_run_trajectories in layer mode (mops_traj_advance_layer): the slices of `layer` are made from `front`
+ * and `back` (NULL = a streamline) inside the call; `depth` / h_depths are carried, because the records keep
+ * their radius.  MOPS_ERR_INVALID before any device work for a layer outside [0, nVertLevels). */
+mops_status mops_run_trajectories_layer(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                        const mops_traj_cfg* cfg, int32_t layer, int64_t n, const double* h_seeds,
+                                        const float* h_depths, float depth, int32_t* h_cells, double* h_points,
+                                        double* h_velocity, double* h_temperature, double* h_salinity,
+                                        double* h_last_point, double* h_final_pos, float* h_final_depth,
+                                        int32_t* h_death_step, void* stream);
 
 /* mops_run_trajectories for a PathLine with the attribute channel
  * (Kernel::PathLine's current_attrs, MPASOVisualizerKernels.cpp:1288-1324,

@@ -21,6 +21,7 @@ EXPORTED = (
     "mops_locate_cells", "mops_locate_cells_hinted", "mops_order_particles", "mops_order_scratch_bytes",
     "mops_order_particles_live", "mops_permute_arrays", "mops_records_clear_dead",
     "mops_traj_num_records", "mops_traj_num_steps", "mops_traj_advance", "mops_traj_finalize", "mops_traj_last_points",
+    "mops_layer_velocity_bytes", "mops_field_layer_velocity", "mops_traj_advance_layer", "mops_run_trajectories_layer",
     "mops_traj_alpha_table",
     "mops_traj_sample_attrs", "mops_traj_advance_sampled", "mops_traj_finalize_attrs", "mops_run_pathline_attrs",
     "mops_traj_capture_bytes", "mops_traj_capture_plan", "mops_traj_advance_captured",
@@ -160,6 +161,12 @@ def load(path: str | None = None):
     lib.mops_traj_num_records.argtypes = [P]; lib.mops_traj_num_records.restype = I64
     lib.mops_traj_num_steps.argtypes = [P]; lib.mops_traj_num_steps.restype = I64
     lib.mops_traj_advance.argtypes = [P, P, P, P, P, I64, I64, P, I64, P]; lib.mops_traj_advance.restype = st
+    lib.mops_layer_velocity_bytes.argtypes = [P]; lib.mops_layer_velocity_bytes.restype = I64
+    lib.mops_field_layer_velocity.argtypes = [P, P, I32, P, P]; lib.mops_field_layer_velocity.restype = st
+    lib.mops_traj_advance_layer.argtypes = [P, P, P, P, P, I64, I64, P, I64, P]
+    lib.mops_traj_advance_layer.restype = st
+    lib.mops_run_trajectories_layer.argtypes = [P, P, P, P, I32, I64, P, P, C.c_float, P, P, P, P, P, P, P, P, P, P]
+    lib.mops_run_trajectories_layer.restype = st
     lib.mops_traj_finalize.argtypes = [I64, I64, P, P, I64, I32, P, P, P, P, P, P, P]
     lib.mops_traj_finalize.restype = st
     lib.mops_traj_last_points.argtypes = [I64, I64, P, P, I64, P, P, P]

@@ -151,7 +151,7 @@ class PathlineChain:
             compute_stream=None, on_pair=None, timing=None, segment_steps: int = -1, reorder: bool = True,
             record_stride: int | None = None, defer_lines: bool = False, compact: bool | None = None,
             compact_chunks: int = 6, on_lines=None, lines_chunk: int | None = None, attrs: bool = False,
-            capture_slots: int | None = None, density=None):
+            capture_slots: int | None = None, density=None, layer: int | None = None):
         """Run all pairs; returns device tensors {points, velocity, temperature,
         salinity, lastPoint, death_step (of the last pair)} when ``keep_lines``,
         else only lastPoint/death_step.  ``on_pair(p, last, ps)`` is called after pair p
@@ -204,8 +204,20 @@ class PathlineChain:
         samples as images, with no line leaving the device.  Works in every mode above (it is a parameter and
         not an ``on_pair`` collector because an ``on_pair`` that reads the records is refused with ``attrs`` and
         ``defer_lines``).  A map of an attribute needs ``attrs`` and a sampled name (ValueError before any
-        trajectory launch).  The maps are not reset here; None changes nothing."""
+        trajectory launch).  The maps are not reset here; None changes nothing.
+        ``layer``: the layer mode (mops_traj_advance_layer) -- every pair advects within model layer ``layer``
+        with w = 0; ``depth`` is still carried (the records keep their radius).  One slice per snapshot
+        (DeviceField.layer_velocity), made on the stream that builds or refills the field, so pair p's back
+        slice is pair p + 1's front and a field rebuilt in place gets its slice again.  Works in every mode
+        above except ``attrs`` (ValueError before any launch); density and FTLE maps become maps of the layer.
+        None: the depth mode, unchanged."""
         import torch
+        if layer is not None:
+            if attrs:
+                raise ValueError("layer: attributes are not sampled in the layer mode")
+            if not 0 <= int(layer) < self.mesh.nVertLevels:
+                raise ValueError(f"layer {layer} outside [0, {self.mesh.nVertLevels})")
+            layer = int(layer)
         maps = [] if density is None else (list(density) if isinstance(density, (list, tuple)) else [density])
         for m in maps:
             if not isinstance(m, DensityMap):
@@ -233,7 +245,8 @@ class PathlineChain:
         cs = compute_stream or torch.cuda.current_stream(dev)
         side = torch.cuda.Stream(device=dev)
         cfgs = [TrajectoryConfig(deltaT=int(delta_t), simulationDuration=int(g), recordT=int(record_t),
-                                 depth=float(np.float32(depth)), direction=int(direction), method=int(method))
+                                 depth=float(np.float32(depth)), direction=int(direction), method=int(method),
+                                 layer=layer)
                 for g in self.gaps]
         for c in cfgs:
             if c.n_steps <= 0 or c.n_records <= 0:
@@ -276,11 +289,21 @@ class PathlineChain:
                     v.record_stream(cs)  # allocated beside the compute stream, read on it
             attr_t[i] = t
 
+        def build_layer(i, stream):
+            """Snapshot i's layer slice on the stream that built (or refilled) its field."""
+            if layer is None:
+                return
+            t = fields[i]._layer_slice(layer, stream.cuda_stream)
+            if stream != cs:
+                t.record_stream(cs)  # allocated beside the compute stream, read on it
+
         with torch.cuda.stream(cs):
             fields[0] = self.make_field(0, cs.cuda_stream)
             build_attrs(0, cs)
+            build_layer(0, cs)
             fields[1] = self.make_field(1, cs.cuda_stream)
             build_attrs(1, cs)
+            build_layer(1, cs)
             if attrs:
                 given = getattr(self.make_attrs, "names", None)
                 names.extend(sorted(given) if given else sorted(set(attr_t[0]) & set(attr_t[1])))
@@ -315,6 +338,7 @@ class PathlineChain:
                 with torch.cuda.stream(ov):
                     fields[p + 2] = self.make_field.refill(buf, p + 2, ov)
                     build_attrs(p + 2, ov)
+                    build_layer(p + 2, ov)
                     ready[p + 2] = torch.cuda.Event()
                     ready[p + 2].record(ov)
             if p + 1 in ready:
@@ -443,6 +467,7 @@ class PathlineChain:
                     with torch.cuda.stream(cs):
                         fields[p + 2] = self.make_field.refill(fields.pop(p), p + 2, cs)
                         build_attrs(p + 2, cs)
+                        build_layer(p + 2, cs)
                 continue
             # overlap: build the field pair p+1 will need while pair p computes
             if p + 2 < self.n_snapshots and (self.prefetch or not self.own_fields):
@@ -450,11 +475,13 @@ class PathlineChain:
                     with torch.cuda.stream(side):
                         fields[p + 2] = self.make_field(p + 2, side.cuda_stream)
                         build_attrs(p + 2, side)
+                        build_layer(p + 2, side)
                     cs.wait_stream(side)
                 else:
                     with torch.cuda.stream(cs):
                         fields[p + 2] = self.make_field(p + 2, cs.cuda_stream)
                         build_attrs(p + 2, cs)
+                        build_layer(p + 2, cs)
             done = fields.pop(p)
             if self.own_fields:
                 cs.synchronize()  # pair p finished with `done` before it is freed
@@ -464,6 +491,7 @@ class PathlineChain:
                     with torch.cuda.stream(cs):
                         fields[p + 2] = self.make_field(p + 2, cs.cuda_stream)
                         build_attrs(p + 2, cs)
+                        build_layer(p + 2, cs)
             else:
                 attr_t.pop(p, None)  # (made and read on `cs`)
         if self.own_fields:

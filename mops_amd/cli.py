@@ -9,6 +9,8 @@ Mirrors the reference's command-line driver (CLI/main.cpp) option for option:
     -g/--day       day gap (default 1)                  "day,g"
     -d/--depth     fixed depth in metres (default 10)   "depth,d"
     --vti          extension: also write the VTI of the reference's MOPS_VTK build branch
+    --layer K      extension: the streamline advects within model layer K (TrajectorySettings.fixedLayer)
+                   instead of at the fixed depth; absent = the reference's run
 
 and its run (CLI/main.cpp:94-262): grid and one solution per timestep from the
 YAML (initGrid_DemoLoading / initSolution_DemoLoading, with temperature and
@@ -49,6 +51,7 @@ def parse_command_line(argv):
     p.add_argument("-g", "--day", type=int, default=1, help="Day Gap")
     p.add_argument("-d", "--depth", type=float, default=10.0, help="Fixed depth")
     p.add_argument("--vti", action="store_true", help="Also write the remapped images as VTK ImageData")
+    p.add_argument("--layer", type=int, default=None, help="Streamline within this model layer (default: at the depth)")
     p.add_argument("-h", "--help", action="store_true", help="Print this information")
     args = p.parse_args(argv)
     if args.help:
@@ -56,6 +59,9 @@ def parse_command_line(argv):
         return None
     if not args.input:
         print("[ERROR]::Input yaml file is required.")
+        return None
+    if args.layer is not None and args.layer < 0:
+        print("[ERROR]::--layer must be a model layer index (>= 0).")
         return None
     args.range = _int_list(args.range)
     return args
@@ -148,6 +154,8 @@ def main(argv=None) -> int:
     cfg.simulationDuration = ONE_DAY * args.day
     cfg.recordT = ONE_HOUR * 6
     cfg.fileName = f"traj_line_{timesteps[0]}"
+    if args.layer is not None:
+        cfg.fixedLayer = args.layer
     if len(timesteps) == 1:
         print("== single timestep [streamline] ==")
         lines = M.MOPS_RunStreamLine(cfg, sample_points)

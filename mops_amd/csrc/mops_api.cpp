@@ -113,11 +113,24 @@ std::vector<TrajectoryLine> run(TrajectorySettings* config, std::vector<Cartesia
     }
     // TrajectorySettings::relocateStages (with kRK4 only: Euler has no stages)
     const bool relocate = config->relocateStages && config->methodType == CalcMethodType::kRK4;
-    if (relocate && !pathline) {
+    // TrajectorySettings::fixedLayer: the layer mode (mops_run_trajectories_layer), where relocateStages applies to
+    // streamlines too
+    const int layer = config->fixedLayer;
+    if (layer >= 0) {
+        if ((size_t)layer >= (size_t)g_app.grid->mVertLevels) {
+            Error("[%s] fixedLayer %d outside [0, %d)", stage, layer, (int)g_app.grid->mVertLevels);
+            return {};
+        }
+        if (config->sampleAttributes) {
+            Error("[%s] sampleAttributes is not supported with fixedLayer", stage);
+            return {};
+        }
+    }
+    if (layer < 0 && relocate && !pathline) {
         Error("[%s] relocateStages is for pathlines only", stage);
         return {};
     }
-    if (relocate && config->sampleAttributes) {
+    if (layer < 0 && relocate && config->sampleAttributes) {
         Error("[%s] sampleAttributes is not supported with relocateStages", stage);
         return {};
     }
@@ -147,7 +160,13 @@ std::vector<TrajectoryLine> run(TrajectorySettings* config, std::vector<Cartesia
     const int64_t P = K + 1;
     std::vector<double> hp((size_t)(n * P * 3)), hv((size_t)(n * P * 3)), ht((size_t)(n * P)), hs((size_t)(n * P)),
         hl((size_t)(n * 3));
-    if (pathline && config->sampleAttributes) {
+    if (layer >= 0) {
+        check(mops_run_trajectories_layer(g_app.mesh, g_app.front, pathline ? g_app.back : nullptr, &cfg, layer, n,
+                                          reinterpret_cast<const double*>(pts.data()), depths.data(), config->depth,
+                                          nullptr, hp.data(), hv.data(), ht.data(), hs.data(), hl.data(), nullptr,
+                                          nullptr, nullptr, nullptr),
+              "mops_run_trajectories_layer");
+    } else if (pathline && config->sampleAttributes) {
         // TrajectorySettings::sampleAttributes: the first two names, in std::map order, that both solutions carry
         // (the reference's size() > 1 gate, MPASOVisualizerKernels.cpp:1093, is not kept: one name is enough)
         const auto fs = g_app.sols.find(g_app.front_id), bs = g_app.sols.find(g_app.back_id);

@@ -2414,6 +2414,282 @@ __global__ void __launch_bounds__(kTrajBlock, (RelocWaves<MAXV>::value)) traj_rk
 }
 
 // ===========================================================================
+// fixed-layer streamlines and pathlines (mops_traj_advance_layer)
+// ===========================================================================
+// The StreamLine / PathLine loop of traj_kernel with calc_velocity_at replaced by the layer evaluation: the cell
+// guards, IsInMesh and the Wachspress weights (dev::weights), then TBBKernel::CalcVelocity's sum at ONE layer
+// (TBBKernel.h:128-147) per field, the pathline blend h_b * alpha + h_f * (1 - alpha), failure where |h| < 1e-12,
+// and w = 0.  No zTop column, no bracket, no vertical velocity is read: the kernel takes the mesh and one compact
+// per-vertex slice per snapshot (layer_slice_kernel) -- {vx, vy, vz, 0} of the layer, 32 B, internal vertex order.
+// The vertical-update lines stay with w = 0 (the depth is stored back as it came; the position is renormalised
+// to its radius each step, as the reference does).
+//
+// METHOD: MOPS_RK4 (stages in the step's cell, quirk Q1), MOPS_EULER, MOPS_RK4_RELOCATE (each of stages 2-4
+// located by the step's one-hop walk as traj_rk4_reloc_kernel does, for streamlines too).  One lane per particle,
+// no tile, no hand-off, no capture, no LDS normals; untuned.  Instantiations of its own everywhere a shared helper
+// has a tag (dev::kNvLayer, walk<MAXV, 2>), so no existing kernel's code moves.
+struct TrajLayerArgs : TrajArgs {
+    const double4* __restrict__ s0;  // the front snapshot's layer slice [V]
+    const double4* __restrict__ s1;  // the back snapshot's (a streamline: s0 again, never read)
+};
+
+namespace dev {
+constexpr int kNvLayer = -3;  // the general vertex count in instantiations of the layer kernel's own (see kNvSample)
+
+// load_cell<MAXV, false, false> without the fields' fast-path words (a layer run has no mops_field)
+template <int MAXV>
+__device__ __forceinline__ void load_cell_layer(Cell<MAXV>& c, int cell, const int* __restrict__ cellrec,
+                                                const double4* __restrict__ cxyz, const double4* __restrict__ cpoly) {
+    c.mono0 = 0u;
+    c.mono1 = 0u;
+    {
+        const double4 q = cxyz[cell];
+        c.cx = q.x; c.cy = q.y; c.cz = q.z; c.rs2 = q.w;
+    }
+    constexpr int REC = ((1 + 2 * MAXV) + 3) / 4 * 4;
+    const int* r = cellrec + (int64_t)cell * REC;
+    int buf[REC];
+#pragma unroll
+    for (int q = 0; q < REC / 4; ++q) {
+        const int4 v = reinterpret_cast<const int4*>(r)[q];
+        buf[4 * q] = v.x; buf[4 * q + 1] = v.y; buf[4 * q + 2] = v.z; buf[4 * q + 3] = v.w;
+    }
+    c.id = cell;
+    c.nv = buf[0];
+    c.rc = false;
+#pragma unroll
+    for (int k = 0; k < MAXV; ++k) c.vid[k] = buf[1 + k];
+    c.cpoly = cpoly;
+    if constexpr (MOPS_CPOLY_RANK && MAXV == 7) c.rank = c.crank[cell];
+}
+
+// dev::relocate with the layer kernel's own walk instantiation
+template <int MAXV>
+__device__ __forceinline__ int locate_layer(Cell<MAXV>& c, int cell, double x, double y, double z, const TrajArgs& a) {
+    const double ex = x - c.cx, ey = y - c.cy, ez = z - c.cz;
+    if (ex * ex + ey * ey + ez * ez < c.rs2) return cell;
+    if constexpr (MOPS_NBR_TEST && MAXV == 7) {
+        if (nbr_stay<MAXV>(c, cell, x, y, z, a.nbr)) return cell;
+    }
+    return walk<MAXV, 2>(c, cell, x, y, z, a.cellrec, a.cxyz, a.C);
+}
+
+// The layer evaluation: false where the reference's guards or IsInMesh fail, or where |h| < 1e-12 (the
+// streamline's own rule, MPASOVisualizerKernels.cpp:838-852; for pathlines this engine's choice, mops_traj.h)
+template <int MAXV, bool PATH>
+__device__ __forceinline__ bool eval_layer(const Cell<MAXV>& c, int L, int V, const double4* __restrict__ s0,
+                                           const double4* __restrict__ s1, double px, double py, double pz,
+                                           double alpha, double& hx, double& hy, double& hz) {
+    double w[MAXV];
+    bool wfin;
+    if (!weights<MAXV, kNvLayer>(c, L, V, px, py, pz, w, wfin)) return false;
+    double fx = 0.0, fy = 0.0, fz = 0.0, gx = 0.0, gy = 0.0, gz = 0.0;
+#pragma unroll
+    for (int v = 0; v < MAXV; ++v) {
+        if (v < c.nv) {
+            const double2* q = reinterpret_cast<const double2*>(s0 + c.vid[v]);
+            const double2 a = q[0], b = q[1];
+            fx += w[v] * a.x; fy += w[v] * a.y; fz += w[v] * b.x;
+            if constexpr (PATH) {
+                const double2* qb = reinterpret_cast<const double2*>(s1 + c.vid[v]);
+                const double2 e = qb[0], f = qb[1];
+                gx += w[v] * e.x; gy += w[v] * e.y; gz += w[v] * f.x;
+            }
+        }
+    }
+    if constexpr (PATH) {
+        hx = gx * alpha + fx * (1.0 - alpha);
+        hy = gy * alpha + fy * (1.0 - alpha);
+        hz = gz * alpha + fz * (1.0 - alpha);
+    } else {
+        hx = fx; hy = fy; hz = fz;
+    }
+    return !(len3(hx, hy, hz) < 1e-12);
+}
+}  // namespace dev
+
+template <int MAXV, int METHOD>
+struct LayerWaves {
+    static constexpr int value = MAXV <= 7 ? 2 : 1;  // (untuned; the resource report: DESIGN 3.18)
+};
+
+template <int MAXV, bool PATH, int METHOD>
+__global__ void __launch_bounds__(kTrajBlock, (LayerWaves<MAXV, METHOD>::value)) traj_layer_kernel(TrajLayerArgs a) {
+    constexpr bool EULER = METHOD == MOPS_EULER, RELOC = METHOD == MOPS_RK4_RELOCATE;
+    // the XCD block remap over the live slots (traj_kernel)
+    unsigned nblk = gridDim.x;
+    int64_t n = a.n;
+    if (a.n_live) {
+        const int64_t nl = *a.n_live;
+        n = nl < n ? nl : n;
+        nblk = (unsigned)((n + blockDim.x - 1) / blockDim.x);
+    }
+    const unsigned b = blockIdx.x;
+    if (b >= nblk) return;
+    const unsigned xcd = b % 8u, q = nblk / 8u, r8 = nblk % 8u;
+    const unsigned blk = (xcd < r8 ? xcd * (q + 1u) : r8 * (q + 1u) + (xcd - r8) * q) + b / 8u;
+    const int64_t slot = (int64_t)blk * blockDim.x + threadIdx.x;
+    if (slot >= n) return;
+    const int64_t pid = a.order ? (int64_t)a.order[slot] : slot;
+    const int sb = (int)a.step_begin, step_end = (int)a.step_end;  // (32-bit in here: mops_traj_advance_layer checks)
+    if (a.death[pid] >= 0) {  // the reference's lambda has returned
+        if (a.step_begin == 0) dev::clear_records(a.rec, a.rec_stride, pid, 0, a.K);
+        return;
+    }
+    double x = a.px[pid], y = a.py[pid], z = a.pz[pid];
+    float dep = a.depth[pid];
+    int cell = a.cell[pid];
+    int died = -1;
+    dev::Cell<MAXV> c, cs;  // the step's cell; RELOC: the cell the current stage is evaluated in
+    c.id = -1; c.nv = 0; c.V = a.V; c.cpolyr = a.cpolyr; c.crank = a.crank; c.C = (uint32_t)a.C;
+    c.nrm = nullptr; c.lds_n = false;
+    if constexpr (RELOC) cs = c;
+    const int C = a.C;
+    const int rec_period = (int)a.rec_period;
+    uint32_t rec_next = ~(uint32_t)0;
+    int rec_k = 0;
+    bool rec0 = sb > 0;  // record 0's step-0 part (seed position, zero velocity) written
+    if (rec_period > 0) {
+        rec_k = sb / rec_period;
+        rec_next = (uint32_t)(rec_k + 1) * (uint32_t)rec_period - 1u;
+    }
+    const double dt = (double)a.delta_t;
+    for (int step = sb; step < step_end; ++step) {
+        if (step == 0) {  // first_loop (:892-901, :1351-1360)
+            if (cell < 0 || cell >= C) { died = 0; break; }
+            dev::load_cell_layer<MAXV>(c, cell, a.cellrec, a.cxyz, a.cpoly);
+            double* r0 = a.rec;
+            r0[0 * a.rec_stride + pid] = x;
+            r0[1 * a.rec_stride + pid] = y;
+            r0[2 * a.rec_stride + pid] = z;
+            r0[3 * a.rec_stride + pid] = 0.0;  // (first_vel below, once step 0 evaluates)
+            r0[4 * a.rec_stride + pid] = 0.0;
+            r0[5 * a.rec_stride + pid] = 0.0;
+            rec0 = true;
+        } else {  // one-hop nearest-centre walk (:902-922, :1361-1381)
+            if (cell < 0 || cell >= C) { died = step; break; }
+            if (c.id != cell) dev::load_cell_layer<MAXV>(c, cell, a.cellrec, a.cxyz, a.cpoly);
+            cell = dev::locate_layer<MAXV>(c, cell, x, y, z, a);
+            if (c.id != cell) {
+                bool have = false;
+                if constexpr (RELOC) {
+                    if (cs.id == cell) { c = cs; have = true; }  // (the cell a stage was evaluated in)
+                }
+                if (!have) dev::load_cell_layer<MAXV>(c, cell, a.cellrec, a.cxyz, a.cpoly);
+            }
+        }
+        const double r = dev::len3(x, y, z);
+        double a1 = 0.0;
+        if constexpr (PATH) a1 = a.alpha_tab ? a.alpha_tab[step] : (double)step / (double)a.n_steps;  // (the same bits)
+        double hx = 0, hy = 0, hz = 0;
+        double nx, ny, nz;
+        if constexpr (EULER) {
+            if (!dev::eval_layer<MAXV, PATH>(c, a.L, a.V, a.s0, a.s1, x, y, z, a1, hx, hy, hz)) { died = step; break; }
+            const double ax = y * hz - z * hy, ay = z * hx - x * hz, az = x * hy - y * hx;
+            const double speed = dev::len3(hx, hy, hz);
+            const double th = (speed * a.delta_t) / dev::dmax(1e-12, r);
+            dev::rotate((unsigned)step, x, y, z, ax, ay, az, th, nx, ny, nz);
+        } else {
+            const double a2 = PATH ? dev::dclamp(a1 + 0.5 * a.dalpha, 0.0, 1.0) : 0.0;
+            const double a4 = PATH ? dev::dclamp(a1 + a.dalpha, 0.0, 1.0) : 0.0;
+            // the four stages, one evaluation in a loop (traj_rk4_reloc_kernel), summed in the reference's
+            // association ((s1 + 2 s2) + 2 s3) + s4
+            double sx = 0, sy = 0, sz = 0;
+            double qx = x, qy = y, qz = z;
+            bool ok = true;
+#pragma unroll 1
+            for (int st = 0; st < 4; ++st) {
+                if (st > 0) dev::advect((unsigned)step, x, y, z, sx, sy, sz, st == 3 ? dt : dt * 0.5, qx, qy, qz);
+                const double as = st == 0 ? a1 : (st == 3 ? a4 : a2);
+                if constexpr (RELOC) {
+                    int sc = cell;
+                    if (st > 0) sc = dev::locate_layer<MAXV>(c, cell, qx, qy, qz, a);
+                    if (cs.id != sc) {
+                        if (sc == cell) cs = c;
+                        else dev::load_cell_layer<MAXV>(cs, sc, a.cellrec, a.cxyz, a.cpoly);
+                    }
+                    ok = dev::eval_layer<MAXV, PATH>(cs, a.L, a.V, a.s0, a.s1, qx, qy, qz, as, sx, sy, sz);
+                } else {
+                    ok = dev::eval_layer<MAXV, PATH>(c, a.L, a.V, a.s0, a.s1, qx, qy, qz, as, sx, sy, sz);
+                }
+                if (!ok) break;
+                if (st == 0) { hx = sx; hy = sy; hz = sz; }
+                else if (st < 3) { hx = hx + sx * 2.0; hy = hy + sy * 2.0; hz = hz + sz * 2.0; }
+                else { hx = (hx + sx) / 6.0; hy = (hy + sy) / 6.0; hz = (hz + sz) / 6.0; }
+            }
+            if (!ok) { died = step; break; }
+            const double tx = x + hx * dt, ty = y + hy * dt, tz = z + hz * dt;
+            const double tl = dev::len3(tx, ty, tz);
+            if (tl > 1e-12) {
+                dev::xdiv_norm3(tx, ty, tz, tl, nx, ny, nz);
+                nx *= r; ny *= r; nz *= r;
+            }
+            else { nx = x; ny = y; nz = z; }
+        }
+        // vertical update (:977-986, :1458-1467) with w = 0: the depth keeps its value (max(0, (double)dep - 0 * dt)
+        // is dep for every dep >= 0 and 0 below, as the reference gives), the radius is max(1, r + 0 * dt)
+        const double wv = 0.0;
+        double nd = (double)dep - wv * (double)a.delta_t;
+        nd = dev::dmax(0.0, nd);
+        const double r_new = dev::dmax(1.0, r + wv * (double)a.delta_t);
+        dep = (float)nd;
+        const double nl = dev::len3(nx, ny, nz);
+        if (nl > 1e-12) {
+            dev::xdiv_norm3(nx, ny, nz, nl, nx, ny, nz);
+            nx *= r_new; ny *= r_new; nz *= r_new;
+        }
+        if (step == 0) {  // first_vel
+            a.rec[3 * a.rec_stride + pid] = hx;
+            a.rec[4 * a.rec_stride + pid] = hy;
+            a.rec[5 * a.rec_stride + pid] = hz;
+        }
+        x = nx; y = ny; z = nz;
+        if ((uint32_t)step == rec_next) {  // (step + 1) % rec_period == 0, record k = (step + 1) / rec_period - 1
+            const int k = rec_k;
+            rec_next += (uint32_t)rec_period;
+            ++rec_k;
+            if (k < (int)a.K) {
+                double* rk = a.rec + (int64_t)k * 6 * a.rec_stride;
+                rk[0 * a.rec_stride + pid] = x;
+                rk[1 * a.rec_stride + pid] = y;
+                rk[2 * a.rec_stride + pid] = z;
+                rk[3 * a.rec_stride + pid] = hx;
+                rk[4 * a.rec_stride + pid] = hy;
+                rk[5 * a.rec_stride + pid] = hz;
+            }
+        }
+    }
+    a.px[pid] = x; a.py[pid] = y; a.pz[pid] = z;
+    a.depth[pid] = dep;
+    a.cell[pid] = cell;
+    if (died >= 0) a.death[pid] = died;
+    // slots never sampled: after a death, and past the last record step (traj_kernel)
+    if (died >= 0 || step_end == (int)a.n_steps) dev::clear_records(a.rec, a.rec_stride, pid, (rec_k == 0 && rec0) ? 1 : rec_k, a.K);
+}
+
+// One snapshot's velocity at layer k per vertex, {vx, vy, vz, 0}: from cellVertexVelocity [V][L][3] where the field
+// holds every value, else (the fused derivation) from the level-pair records as records_to_vertex_kernel reads
+// them (level j from record j, level L-1 from the second half of record L-2)
+__global__ void __launch_bounds__(256) layer_slice_kernel(int64_t V, int L, int k, const double* __restrict__ vel,
+                                                          const double* __restrict__ pr, double4* __restrict__ out) {
+    const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= V) return;
+    double x, y, z;
+    if (pr) {
+        const bool hi = k == L - 1;
+        const double2* p2 = reinterpret_cast<const double2*>(pr) + pr_base((uint32_t)(hi ? k - 1 : k), (uint32_t)v, (uint32_t)V);
+        const double2 q2 = p2[2], q3 = p2[3], q4 = p2[4];  // doubles 4..9 of the record: vel_j (3), vel_{j+1} (3)
+        x = hi ? q3.y : q2.x;
+        y = hi ? q4.x : q2.y;
+        z = hi ? q4.y : q3.x;
+    } else {
+        const double* p = vel + (v * L + k) * 3;
+        x = p[0]; y = p[1]; z = p[2];
+    }
+    out[v] = make_double4(x, y, z, 0.0);
+}
+
+// ===========================================================================
 // attribute sampling along pathlines (mops_traj_sample_attrs)
 // ===========================================================================
 struct SampleArgs {
@@ -3978,6 +4254,21 @@ static mops_status launch_traj_reloc(int maxv, const TrajArgs& a, hipStream_t s)
     return MOPS_OK;
 }
 
+// mops_traj_advance_layer: the per-lane layer kernel of the run's kind and method
+template <int MAXV>
+static void launch_traj_layer(const TrajLayerArgs& a, bool path, int method, hipStream_t s) {
+    const unsigned g = (unsigned)((a.n + kTrajBlock - 1) / kTrajBlock);
+    if (path) {
+        if (method == MOPS_EULER) traj_layer_kernel<MAXV, true, MOPS_EULER><<<g, kTrajBlock, 0, s>>>(a);
+        else if (method == MOPS_RK4_RELOCATE) traj_layer_kernel<MAXV, true, MOPS_RK4_RELOCATE><<<g, kTrajBlock, 0, s>>>(a);
+        else traj_layer_kernel<MAXV, true, MOPS_RK4><<<g, kTrajBlock, 0, s>>>(a);
+    } else {
+        if (method == MOPS_EULER) traj_layer_kernel<MAXV, false, MOPS_EULER><<<g, kTrajBlock, 0, s>>>(a);
+        else if (method == MOPS_RK4_RELOCATE) traj_layer_kernel<MAXV, false, MOPS_RK4_RELOCATE><<<g, kTrajBlock, 0, s>>>(a);
+        else traj_layer_kernel<MAXV, false, MOPS_RK4><<<g, kTrajBlock, 0, s>>>(a);
+    }
+}
+
 // launch_traj's pathline MAXV 7 branch with the CAP instantiations (a.cap set; mops_traj_advance_captured)
 static void launch_traj_cap(const TrajArgsCap& a, bool euler, hipStream_t s) {
     const unsigned g = (unsigned)((a.n + kTrajBlock - 1) / kTrajBlock);
@@ -4948,6 +5239,93 @@ mops_status mops_traj_advance(const mops_mesh* mesh, const mops_field* front, co
     return traj_advance_impl(mesh, front, back, cfg, p, step_begin, step_end, d_records, record_stride, stream, nullptr);
 }
 
+// ---- fixed-layer trajectories ------------------------------------------------
+int64_t mops_layer_velocity_bytes(const mops_mesh* mesh) {
+    return mesh ? (int64_t)mesh->V * (int64_t)sizeof(double4) : -1;
+}
+
+mops_status mops_field_layer_velocity(const mops_mesh* mesh, const mops_field* field, int32_t layer, void* d_out,
+                                      void* stream) {
+    if (!mesh || !field || !d_out) return fail(MOPS_ERR_INVALID, "mops_field_layer_velocity: invalid inputs");
+    if (field->mesh != mesh) return fail(MOPS_ERR_INVALID, "mops_field_layer_velocity: the field belongs to another mesh");
+    if (layer < 0 || layer >= mesh->L)
+        return fail(MOPS_ERR_INVALID, "mops_field_layer_velocity: layer " + std::to_string(layer) + " outside [0, " +
+                                          std::to_string(mesh->L) + ")");
+    if (((uintptr_t)d_out & 15u) != 0) return fail(MOPS_ERR_INVALID, "mops_field_layer_velocity: d_out must be 16-byte aligned");
+    if (mesh->V == 0) return MOPS_OK;
+    const bool from_records = !field->vtx_full && mesh->L >= 2;
+    layer_slice_kernel<<<grid_for((int64_t)mesh->V), kBlock, 0, (hipStream_t)stream>>>(
+        (int64_t)mesh->V, mesh->L, (int)layer, field->d_vel, from_records ? field->d_pr : nullptr,
+        static_cast<double4*>(d_out));
+    HIP_TRY(hipGetLastError());
+    return MOPS_OK;
+}
+
+mops_status mops_traj_advance_layer(const mops_mesh* mesh, const void* d_front_layer, const void* d_back_layer,
+                                    const mops_traj_cfg* cfg, const mops_particles* p, int64_t step_begin,
+                                    int64_t step_end, double* d_records, int64_t record_stride, void* stream) {
+    if (!mesh || !cfg || !p) return fail(MOPS_ERR_INVALID, "mops_traj_advance_layer: invalid inputs");
+    if (!d_front_layer) return fail(MOPS_ERR_INVALID, "mops_traj_advance_layer: null layer slice");
+    if ((((uintptr_t)d_front_layer | (uintptr_t)d_back_layer) & 15u) != 0)
+        return fail(MOPS_ERR_INVALID, "mops_traj_advance_layer: a layer slice must be 16-byte aligned");
+    if (cfg->delta_t <= 0 || cfg->record_t <= 0 || cfg->simulation_duration <= 0)
+        return fail(MOPS_ERR_INVALID, "invalid trajectory settings");  // :666-669
+    const int64_t K = mops_traj_num_records(cfg), n_steps = mops_traj_num_steps(cfg);
+    if (K <= 0 || n_steps <= 0) return fail(MOPS_ERR_INVALID, "invalid integration steps");  // :709-712
+    const bool path = d_back_layer != nullptr;
+    const int64_t rec_period = path ? cfg->record_t / cfg->delta_t                          // record_interval (:1470)
+                                    : cfg->record_t / gcd64(cfg->record_t, cfg->delta_t);  // run_time % recordT == 0 (:994)
+    if (n_steps > INT32_MAX || K > INT32_MAX || rec_period > INT32_MAX)
+        return fail(MOPS_ERR_INVALID, "mops_traj_advance_layer: the number of steps, the number of records and the "
+                                      "record period in steps must each be below 2^31");
+    if (p->n < 0 || record_stride < p->n) return fail(MOPS_ERR_INVALID, "record_stride < n");
+    if (p->n == 0) return MOPS_OK;
+    if (!p->d_x || !p->d_y || !p->d_z || !p->d_depth || !p->d_cell || !p->d_death_step || !d_records)
+        return fail(MOPS_ERR_INVALID, "mops_traj_advance_layer: null device pointer");
+    step_begin = std::max<int64_t>(step_begin, 0);
+    step_end = std::min<int64_t>(step_end, n_steps);
+    if (step_begin >= step_end) return MOPS_OK;
+    if (cfg->delta_t > INT32_MAX) return fail(MOPS_ERR_INVALID, "deltaT too large");
+    TrajLayerArgs a;
+    a.cellrec = mesh->d_cellrec; a.cxyz = mesh->d_cxyz; a.vxyz = mesh->d_vxyz;
+    a.C = (int)mesh->C; a.V = (int)mesh->V; a.L = mesh->L;
+    a.f0 = dev::Field{nullptr, nullptr};
+    a.f1 = a.f0;
+    a.mono0 = nullptr; a.mono1 = nullptr;
+    a.order = p->d_order;
+    a.n_live = p->d_n_live;
+    a.cpoly = mesh->d_cpoly;
+    a.cnrm = mesh->d_cnrm;
+    a.alpha_tab = nullptr;
+    if (path) MOPS_TRY(alpha_table(mesh, n_steps, &a.alpha_tab));
+    a.nbr = mesh->d_nbr;
+    a.cpolyr = mesh->d_cpolyr;
+    a.crank = mesh->d_cell_rank;
+    a.coop_sel = nullptr;
+    a.handoff = 0;
+    a.px = p->d_x; a.py = p->d_y; a.pz = p->d_z; a.depth = p->d_depth; a.cell = p->d_cell; a.death = p->d_death_step;
+    a.n = p->n;
+    a.step_begin = step_begin; a.step_end = step_end; a.n_steps = n_steps;
+    const int dt_sign = (cfg->direction == MOPS_FORWARD) ? 1 : -1;
+    a.delta_t = dt_sign * (int)cfg->delta_t;
+    a.dalpha = (double)a.delta_t / (double)cfg->simulation_duration;
+    a.rec_period = rec_period;
+    a.K = K;
+    a.rec = d_records;
+    a.rec_stride = record_stride;
+    a.s0 = static_cast<const double4*>(d_front_layer);
+    a.s1 = path ? static_cast<const double4*>(d_back_layer) : a.s0;
+    const int method = (cfg->method == MOPS_EULER || cfg->method == MOPS_RK4_RELOCATE) ? cfg->method : MOPS_RK4;
+    hipStream_t s = (hipStream_t)stream;
+    switch (mesh->maxv) {
+        case 7: launch_traj_layer<7>(a, path, method, s); break;
+        case 12: launch_traj_layer<12>(a, path, method, s); break;
+        default: launch_traj_layer<20>(a, path, method, s); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return MOPS_OK;
+}
+
 mops_status mops_traj_finalize(int64_t n, int64_t K, const double* d_seeds, const double* d_records,
                                int64_t stride, int32_t pathline, const int32_t* d_line, double* d_points,
                                double* d_vel, double* d_tmp, double* d_sal, double* d_last, void* stream) {
@@ -5296,9 +5674,13 @@ static mops_status run_trajectories_impl(const mops_mesh* mesh, const mops_field
                                          double* h_vel, double* h_tmp, double* h_sal, double* h_last,
                                          double* h_final_pos, float* h_final_depth, int32_t* h_death, int32_t n_attr,
                                          const double* const* d_fa, const double* const* d_ba, double* h_attr_lines,
-                                         void* stream) {
+                                         void* stream, int layer = -1) {
     if (!mesh || !front || !cfg) return fail(MOPS_ERR_INVALID, "invalid inputs");  // :659-662
-    if (cfg->method == MOPS_RK4_RELOCATE && !back)  // (never silently the plain RK4)
+    if (layer >= 0) {  // the layer mode (mops_run_trajectories_layer): its range, before any device work
+        if (layer >= mesh->L)
+            return fail(MOPS_ERR_INVALID, "mops_run_trajectories_layer: layer " + std::to_string(layer) +
+                                              " outside [0, " + std::to_string(mesh->L) + ")");
+    } else if (cfg->method == MOPS_RK4_RELOCATE && !back)  // (never silently the plain RK4)
         return fail(MOPS_ERR_UNSUPPORTED, "mops_run_trajectories: MOPS_RK4_RELOCATE is for pathlines only (back == NULL)");
     if (n_attr != 0) {
         if (!back) return fail(MOPS_ERR_UNSUPPORTED, "mops_run_pathline_attrs: attributes are sampled along pathlines only (back == NULL)");
@@ -5324,6 +5706,7 @@ static mops_status run_trajectories_impl(const mops_mesh* mesh, const mops_field
     double *slab = nullptr, *alines = nullptr;  // n_attr > 0: [K][n_attr][n] and [n_attr][n * P]
     float* dep = nullptr;
     int *cells = nullptr, *death = nullptr, *order = nullptr;
+    double4 *sl0 = nullptr, *sl1 = nullptr;  // layer mode: the two snapshots' layer slices
     mops_status st = MOPS_OK;
     std::vector<double> hx((size_t)n), hy((size_t)n), hz((size_t)n);
     std::vector<float> hd((size_t)n);
@@ -5334,7 +5717,7 @@ static mops_status run_trajectories_impl(const mops_mesh* mesh, const mops_field
     auto cleanup = [&]() {
         (void)hipFree(seeds); (void)hipFree(x); (void)hipFree(y); (void)hipFree(z); (void)hipFree(rec); (void)hipFree(pts); (void)hipFree(vel);
         (void)hipFree(tmp); (void)hipFree(sal); (void)hipFree(last); (void)hipFree(dep); (void)hipFree(cells); (void)hipFree(death);
-        (void)hipFree(order); (void)hipFree(slab); (void)hipFree(alines);
+        (void)hipFree(order); (void)hipFree(slab); (void)hipFree(alines); (void)hipFree(sl0); (void)hipFree(sl1);
     };
     do {
         if ((st = upload(h_seeds, (size_t)(3 * n), &seeds, nullptr, s)) != MOPS_OK) break;
@@ -5391,6 +5774,16 @@ static mops_status run_trajectories_impl(const mops_mesh* mesh, const mops_field
                 break;
             e = hipMemcpyAsync(h_attr_lines, alines, (size_t)(n_attr * n * P) * sizeof(double), hipMemcpyDeviceToHost, s);
             if (e != hipSuccess) { st = fail(MOPS_ERR_HIP, hipGetErrorString(e)); break; }
+        } else if (layer >= 0) {
+            if ((st = dmalloc(&sl0, (size_t)std::max<int64_t>(mesh->V, 1), nullptr)) != MOPS_OK) break;
+            if ((st = mops_field_layer_velocity(mesh, front, layer, sl0, stream)) != MOPS_OK) break;
+            if (back) {
+                if ((st = dmalloc(&sl1, (size_t)std::max<int64_t>(mesh->V, 1), nullptr)) != MOPS_OK) break;
+                if ((st = mops_field_layer_velocity(mesh, back, layer, sl1, stream)) != MOPS_OK) break;
+            }
+            if ((st = mops_traj_advance_layer(mesh, sl0, back ? sl1 : nullptr, cfg, &prt, 0, n_steps, rec, n, stream)) !=
+                MOPS_OK)
+                break;
         } else if ((st = mops_traj_advance(mesh, front, back, cfg, &prt, 0, n_steps, rec, n, stream)) != MOPS_OK) {
             break;
         }
@@ -5427,6 +5820,18 @@ mops_status mops_run_trajectories(const mops_mesh* mesh, const mops_field* front
                                   int32_t* h_death, void* stream) {
     return run_trajectories_impl(mesh, front, back, cfg, n, h_seeds, h_depths, depth, h_cells, h_points, h_vel, h_tmp,
                                  h_sal, h_last, h_final_pos, h_final_depth, h_death, 0, nullptr, nullptr, nullptr, stream);
+}
+
+mops_status mops_run_trajectories_layer(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                        const mops_traj_cfg* cfg, int32_t layer, int64_t n, const double* h_seeds,
+                                        const float* h_depths, float depth, int32_t* h_cells, double* h_points,
+                                        double* h_vel, double* h_tmp, double* h_sal, double* h_last,
+                                        double* h_final_pos, float* h_final_depth, int32_t* h_death, void* stream) {
+    if (layer < 0) return fail(MOPS_ERR_INVALID, "mops_run_trajectories_layer: layer " + std::to_string(layer) +
+                                                     " is negative");
+    return run_trajectories_impl(mesh, front, back, cfg, n, h_seeds, h_depths, depth, h_cells, h_points, h_vel, h_tmp,
+                                 h_sal, h_last, h_final_pos, h_final_depth, h_death, 0, nullptr, nullptr, nullptr, stream,
+                                 layer);
 }
 
 mops_status mops_run_pathline_attrs(const mops_mesh* mesh, const mops_field* front, const mops_field* back,

@@ -34,6 +34,16 @@ def _stream_handle(stream) -> C.c_void_p:
     return C.c_void_p(int(stream.cuda_stream))
 
 
+def _torch_stream(stream):
+    """``stream`` (None, a raw handle or a torch stream) as a torch stream; None / 0 is the default stream."""
+    import torch
+    if stream is None or (isinstance(stream, int) and stream == 0):
+        return torch.cuda.default_stream()
+    if isinstance(stream, int):
+        return torch.cuda.ExternalStream(stream)
+    return stream
+
+
 @dataclasses.dataclass
 class TrajectoryConfig:
     """TrajectorySettings (src/Core/MPASOVisualizer.h:90-103)."""
@@ -43,6 +53,9 @@ class TrajectoryConfig:
     depth: float = 0.0
     direction: int = L.MOPS_FORWARD
     method: int = L.MOPS_EULER          # reference default (MPASOVisualizer.h:99); L.MOPS_RK4_RELOCATE: pathlines only
+    layer: int | None = None            # the layer mode (mops_traj_advance_layer): advect within model layer `layer`
+                                        # with w = 0; ``depth`` is still carried (records keep their radius).  There
+                                        # MOPS_RK4_RELOCATE runs for streamlines too.  None: the depth mode
 
     def ctype(self) -> L.TrajCfg:
         return L.TrajCfg(int(self.deltaT), int(self.simulationDuration), int(self.recordT), int(self.direction),
@@ -129,6 +142,9 @@ class DeviceField:
     def __init__(self, mesh: DeviceMesh, handle):
         self.mesh = mesh
         self.handle = handle
+        self._layers = {}     # layer -> its slice (layer_velocity), kept while the field lives
+        self._layer_made = {}  # layer -> (stream handle the slice was written on, event recorded behind the write)
+        self._stale = set()   # slices made before the last rebuild_from_device
 
     @classmethod
     def from_snapshot(cls, mesh: DeviceMesh, snap, stream=None, velocity: str = "zonal"):
@@ -179,7 +195,48 @@ class DeviceField:
         desc = self._device_desc(snap, timestep)
         L.check(L.load().mops_field_rebuild_device(self.handle, C.byref(desc), _stream_handle(stream)),
                 "mops_field_rebuild_device")
+        self._stale = set(self._layers)
         return self
+
+    def layer_velocity(self, k: int, out=None, stream=None):
+        """This snapshot's velocity at layer ``k`` as the compact per-vertex slice the layer kernels read
+        (mops_field_layer_velocity): an opaque CUDA tensor of mops_layer_velocity_bytes bytes, written into
+        ``out`` when given (a contiguous CUDA tensor of at least that size, 16-byte aligned).  Asynchronous on
+        ``stream``; the field remembers the slice with an event recorded behind the write, so a layer run
+        (``TrajectoryConfig.layer``) finds it and, on another stream, first waits for that event.  A caller that
+        reads the returned tensor itself on another stream orders that read.  After ``rebuild_from_device`` the
+        slice is made again."""
+        import torch
+        lib = L.load()
+        nb = int(lib.mops_layer_velocity_bytes(self.mesh.handle))
+        if out is None:
+            out = torch.empty((max(nb, 8) // 8,), dtype=torch.float64, device=torch.device("cuda",
+                                                                                        torch.cuda.current_device()))
+        elif not (out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= nb):
+            raise ValueError(f"layer_velocity: out must be a contiguous CUDA tensor of at least {nb} bytes")
+        L.check(lib.mops_field_layer_velocity(self.mesh.handle, self.handle, int(k), C.c_void_p(out.data_ptr()),
+                                              _stream_handle(stream)), "mops_field_layer_velocity")
+        ts = _torch_stream(stream)
+        ev = torch.cuda.Event()
+        ev.record(ts)
+        self._layers[int(k)] = out
+        self._layer_made[int(k)] = (int(ts.cuda_stream), ev)
+        self._stale.discard(int(k))
+        return out
+
+    def _layer_slice(self, k: int, stream):
+        """The remembered slice of layer ``k`` for a launch on ``stream``: made on ``stream`` first where there is
+        none or the field was rebuilt since; one written on another stream is waited for on ``stream`` (an event
+        wait on the device, no host synchronisation)."""
+        k = int(k)
+        t = self._layers.get(k)
+        if t is None or k in self._stale:
+            return self.layer_velocity(k, out=t, stream=stream)
+        made_on, ev = self._layer_made[k]
+        ts = _torch_stream(stream)
+        if int(ts.cuda_stream) != made_on:
+            ts.wait_event(ev)
+        return t
 
     @classmethod
     def from_derived(cls, mesh: DeviceMesh, vertex_ztop, vertex_vel, vertex_w=None, stream=None):
@@ -242,6 +299,18 @@ def run_trajectories(mesh: DeviceMesh, front: DeviceField, back: DeviceField | N
     dep = None if depths is None else np.ascontiguousarray(depths, dtype=np.float32)
     cl = np.full(n, -1, dtype=np.int32) if cells is None else np.ascontiguousarray(cells, dtype=np.int32).copy()
     c = cfg.ctype()
+    if cfg.layer is not None:
+        _refuse_attrs_layer(attrs, "run_trajectories")
+        st = lib.mops_run_trajectories_layer(mesh.handle, front.handle, None if back is None else back.handle,
+                                             C.byref(c), int(cfg.layer), n, _ptr(seeds), _ptr(dep),
+                                             C.c_float(cfg.depth), _ptr(cl), _ptr(out["points"]),
+                                             _ptr(out["velocity"]), _ptr(out["temperature"]), _ptr(out["salinity"]),
+                                             _ptr(out["lastPoint"]), _ptr(out["final_pos"]),
+                                             _ptr(out["final_depth"]), _ptr(out["death_step"]),
+                                             _stream_handle(stream))
+        L.check(st, "mops_run_trajectories_layer")
+        out["cells"] = cl
+        return out
     if attrs is not None:
         _refuse_attrs_relocate(cfg, "run_trajectories")
         names = list(attrs)
@@ -277,6 +346,20 @@ def _refuse_attrs_relocate(cfg: TrajectoryConfig, who: str):
     any launch (the C entries return MOPS_ERR_UNSUPPORTED)."""
     if int(cfg.method) == L.MOPS_RK4_RELOCATE:
         raise ValueError(f"{who}: attrs are not sampled with method MOPS_RK4_RELOCATE")
+
+
+def _refuse_attrs_layer(attrs, who: str):
+    """The layer mode has no attribute channel yet: refused before any launch."""
+    if attrs is not None:
+        raise ValueError(f"{who}: attrs are not sampled in the layer mode (TrajectoryConfig.layer)")
+
+
+def _layer_ptrs(front: DeviceField, back: DeviceField | None, layer: int, stream):
+    """The two slice pointers of a layer launch on ``stream`` (the back one None for a streamline), ordered before
+    it: made there, or waited for there (DeviceField._layer_slice)."""
+    f = front._layer_slice(layer, stream)
+    b = None if back is None else back._layer_slice(layer, stream)
+    return C.c_void_p(f.data_ptr()), (None if b is None else C.c_void_p(b.data_ptr()))
 
 
 def _attr_ptr_lists(mesh: DeviceMesh, front_list, back_list):
@@ -564,8 +647,22 @@ class ParticleSet:
         compact(0, n) returned (only the leading live slots are spread over the XCDs).  ``attrs``: a pair
         (front_list, back_list) of n_attr vertex attribute tensors each (``cell_to_vertex_attr``) -- the
         range's sample steps are sampled into the attribute slab (mops_traj_advance_sampled); positions,
-        records, depths and death steps are those of the plain call."""
+        records, depths and death steps are those of the plain call.  In the layer mode (``cfg.layer``) the
+        fields' slices of that layer are made on ``stream`` where they are missing or stale; one made earlier on
+        another stream (``DeviceField.layer_velocity``) is waited for on ``stream`` through its event."""
         p = self.particles() if live_count is None else self._sub_particles(0, self.n, live_count)
+        if self.cfg.layer is not None:  # the layer mode: the mesh and the two snapshots' slices only
+            _refuse_attrs_layer(attrs, "advance")
+            if self.attr_records is not None:
+                raise ValueError("advance: the layer mode does not run a particle set with an attribute slab")
+            fl, bl = _layer_ptrs(front, back, self.cfg.layer, stream)
+            st = L.load().mops_traj_advance_layer(self.mesh.handle, fl, bl, C.byref(self._c), C.byref(p),
+                                                  int(step_begin), int(step_end),
+                                                  C.c_void_p(self.records.data_ptr()), self.rec_stride,
+                                                  _stream_handle(stream))
+            L.check(st, "mops_traj_advance_layer")
+            self._written = True
+            return
         if attrs is not None:
             _refuse_attrs_relocate(self.cfg, "advance")
             if self.attr_records is None or len(attrs[0]) != self.n_attr:
@@ -629,6 +726,15 @@ class ParticleSet:
         each part runs the sampled advance on its own stream, into its columns of the attribute slab and
         its own piece of the capture slab; a compaction moves the attribute slots written so far."""
         torch = self.torch
+        fl = bl = None
+        if self.cfg.layer is not None:
+            _refuse_attrs_layer(attrs, "advance_pipelined")
+            if self.attr_records is not None:
+                raise ValueError("advance_pipelined: the layer mode does not run a particle set with an attribute "
+                                 "slab")
+            # (made on the first part's stream where missing; every part's stream waits for the slices' events)
+            for st in (list(streams) or [None]):
+                fl, bl = _layer_ptrs(front, back, self.cfg.layer, st)
         if self.attr_records is not None and attrs is None:
             raise ValueError("advance_pipelined: not supported for a particle set with an attribute slab")
         fa = ba = None
@@ -676,6 +782,11 @@ class ParticleSet:
                 p = self._sub_particles(lo, hi, self._n_live.get((lo, hi)) if (compact and t > 0) else None)
                 if attrs is not None:
                     self._advance_attrs(front, back, p, lo, tb[t], tb[t + 1], fa, ba, st)
+                elif fl is not None:
+                    rc = lib.mops_traj_advance_layer(self.mesh.handle, fl, bl, C.byref(self._c), C.byref(p), tb[t],
+                                                     tb[t + 1], C.c_void_p(self.records.data_ptr() + 8 * lo),
+                                                     self.rec_stride, _stream_handle(st))
+                    L.check(rc, "mops_traj_advance_layer")
                 else:
                     rc = lib.mops_traj_advance(self.mesh.handle, front.handle, None if back is None else back.handle,
                                                C.byref(self._c), C.byref(p), tb[t], tb[t + 1],

@@ -163,7 +163,7 @@ class MOPSPathline:
                              make_attrs=make_attrs if sample_attributes else None)
 
     def run(self, method: str = "rk4", delta_minutes: int = 1, record_every_minutes: int = 6,
-            sample_attributes: bool = False, density=None) -> list:
+            sample_attributes: bool = False, density=None, layer: int | None = None) -> list:
         """All month pairs as one device-resident chain; the per-pair lines concatenated (later pairs
         without their first sample), pyMOPSAPI.py:1396-1531.  Returns list[dict] with lineID, points
         (M, 3), velocity (M, 3), temperature (M,), salinity (M,), lastPoint (3,).
@@ -174,7 +174,11 @@ class MOPSPathline:
         each stage in its own cell, MOPS_RK4_RELOCATE: particles survive cell crossings; not with
         ``sample_attributes``); any other string means Euler, as in the reference's caller.
         ``density``: an engine.DensityMap or a list of them, filled with every pair's samples on the device
-        (PathlineChain.run(density=...)); a map of "temperature" / "salinity" needs ``sample_attributes``."""
+        (PathlineChain.run(density=...)); a map of "temperature" / "salinity" needs ``sample_attributes``.
+        ``layer``: advect within that model layer with w = 0 (PathlineChain.run(layer=...); the depth set by
+        ``set_seed`` is still carried, because the records keep their radius); not with ``sample_attributes``."""
+        if layer is not None and sample_attributes:
+            raise ValueError("sample_attributes is not supported with a layer")
         meth = {"rk4": L.MOPS_RK4, "rk4_relocate": L.MOPS_RK4_RELOCATE}.get(method.lower(), L.MOPS_EULER)
         if meth == L.MOPS_RK4_RELOCATE and sample_attributes:
             raise ValueError('sample_attributes is not supported with method="rk4_relocate"')
@@ -196,7 +200,7 @@ class MOPSPathline:
                         delta_t=int(delta_minutes) * self._one_min,
                         record_t=int(record_every_minutes) * self._one_min,
                         direction=L.MOPS_FORWARD if self.direction == "forward" else L.MOPS_BACKWARD,
-                        follow_last=self._follow_last, attrs=bool(sample_attributes), density=density)
+                        follow_last=self._follow_last, attrs=bool(sample_attributes), density=density, layer=layer)
         out = {k: res[k].cpu().numpy() for k in ("points", "velocity", "temperature", "salinity", "lastPoint")}
         self._last_pt = out["lastPoint"].astype(float, copy=True)
         if self._particle_depths is not None:  # :1491-1495
@@ -208,7 +212,8 @@ class MOPSPathline:
                 for i in range(out["points"].shape[0])]
 
     def ftle(self, width: int, height: int, lat_range, lon_range, depth: float, method: str = "rk4_relocate",
-             delta_minutes: int = 1, record_every_minutes: int = 1440, horizon_days: float | None = None):
+             delta_minutes: int = 1, record_every_minutes: int = 1440, horizon_days: float | None = None,
+             layer: int | None = None):
         """The FTLE image of the month pairs set by ``set_time``: one particle per pixel of the ``width`` x
         ``height`` window (engine.FlowMapLattice, seeded on the device: the pixel positions of a
         ``MOPS_RunRemapping`` image of the same window), integrated at ``depth`` through every pair as one
@@ -222,7 +227,8 @@ class MOPSPathline:
         gaps, in days).  ``method``: as ``run``; the default "rk4_relocate" keeps its particles, while the
         reference's "rk4" kills a particle at its first cell crossing (quirk Q1: two thirds of them within a
         day at config 3), so its map is mostly NaN -- use it only to reproduce the reference's lines.  Does not
-        touch the state ``run`` keeps between calls (seeds, last points)."""
+        touch the state ``run`` keeps between calls (seeds, last points).  ``layer``: the flow map of that model
+        layer (as ``run``), an image that overlays the ``MOPS_RunRemappingFixedLayer`` one."""
         from .chain import EverDead
         from .engine import FlowMapLattice
         meth = {"rk4": L.MOPS_RK4, "rk4_relocate": L.MOPS_RK4_RELOCATE}.get(method.lower(), L.MOPS_EULER)
@@ -235,5 +241,5 @@ class MOPSPathline:
                         delta_t=int(delta_minutes) * self._one_min,
                         record_t=int(record_every_minutes) * self._one_min,
                         direction=L.MOPS_FORWARD if self.direction == "forward" else L.MOPS_BACKWARD,
-                        follow_last=True, keep_lines=False, on_pair=ever)
+                        follow_last=True, keep_lines=False, on_pair=ever, layer=layer)
         return lattice.ftle(res["lastPoint"], ever.death(), horizon=float(horizon_days))

@@ -287,6 +287,11 @@ class TrajectorySettings:
         # MOPS_RunStreamLine with it and kRK4, and MOPS_RunPathLine with it, kRK4 and sampleAttributes: Error() and
         # an empty list.
         self.relocateStages = False
+        # this engine's extension, the layer mode (mops_traj_advance_layer, include/mops_traj.h): >= 0 makes
+        # MOPS_RunStreamLine / MOPS_RunPathLine advect within that model layer with w = 0 (``depth`` is still
+        # carried: the records keep their radius); there relocateStages applies to streamlines too.  A layer
+        # outside [0, nVertLevels), or sampleAttributes with it: Error() and an empty list.  -1: the depth mode.
+        self.fixedLayer = -1
 
     def hasPerParticleDepths(self) -> bool:
         return len(self.particle_depths) > 0
@@ -532,17 +537,28 @@ def _run(config: TrajectorySettings, sample_points_np, pathline: bool, stage: st
         depths = np.asarray(config.particle_depths, dtype=np.float32)
     eff = depths if depths is not None else np.full(len(seeds), np.float32(config.depth), dtype=np.float32)
     method = int(config.methodType)
-    if getattr(config, "relocateStages", False) and method == int(CalcMethodType.kRK4):
-        if not pathline:
-            _error(f"[{stage}] relocateStages is for pathlines only")
+    layer = int(getattr(config, "fixedLayer", -1))
+    if layer >= 0:
+        if layer >= _app.mesh.nVertLevels:
+            _error(f"[{stage}] fixedLayer {layer} outside [0, {_app.mesh.nVertLevels})")
             return None, seeds, None
         if getattr(config, "sampleAttributes", False):
+            _error(f"[{stage}] sampleAttributes is not supported with fixedLayer")
+            return None, seeds, None
+    if getattr(config, "relocateStages", False) and method == int(CalcMethodType.kRK4):
+        if layer >= 0:
+            pass  # (the layer mode locates the stages of streamlines and pathlines alike)
+        elif not pathline:
+            _error(f"[{stage}] relocateStages is for pathlines only")
+            return None, seeds, None
+        elif getattr(config, "sampleAttributes", False):
             _error(f"[{stage}] sampleAttributes is not supported with relocateStages")
             return None, seeds, None
         method = _L.MOPS_RK4_RELOCATE
     cfg = _E.TrajectoryConfig(deltaT=int(config.deltaT), simulationDuration=int(config.simulationDuration),
                               recordT=int(config.recordT), depth=float(np.float32(config.depth)),
-                              direction=int(config.directionType), method=method)
+                              direction=int(config.directionType), method=method,
+                              layer=layer if layer >= 0 else None)
     if cfg.n_records <= 0 or cfg.n_steps <= 0:
         _error(f"[{stage}] invalid integration steps")  # seed-only lines (:709-712)
         return "seed_only", seeds, eff
