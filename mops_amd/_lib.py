@@ -129,6 +129,8 @@ def load(path: str | None = None):
         lib.mops_traj_alpha_table.argtypes = [I64, P]; lib.mops_traj_alpha_table.restype = I64
     if hasattr(lib, "mops_selftest_walk"):
         lib.mops_selftest_walk.argtypes = [P, I64, P, P, P, P]; lib.mops_selftest_walk.restype = st
+    if hasattr(lib, "mops_debug_prof_ext"):  # (-DMOPS_PROF experiment builds only: tools/prof_ext.py)
+        lib.mops_debug_prof_ext.argtypes = [P, I32]; lib.mops_debug_prof_ext.restype = st
     lib.mops_mesh_create.argtypes = [P, P, P]; lib.mops_mesh_create.restype = st
     lib.mops_mesh_destroy.argtypes = [P]; lib.mops_mesh_destroy.restype = None
     lib.mops_mesh_bytes.argtypes = [P]; lib.mops_mesh_bytes.restype = I64

@@ -1126,6 +1126,10 @@ __device__ __forceinline__ int bracket_mono(const Cell<MAXV>& c, const double* w
 // [6] cooperative wave-steps (pathline Euler tile), [7] their groups,
 // [4] wave-steps with a walk, [5] wave-steps with a cell load.  Never set in a product build.
 __device__ unsigned long long g_prof[16];
+// ... and with mops_debug_prof_ext (the cooperative pathline Euler kernel): [0] wave-steps that execute
+// dev::nbr_stay, [1] regroups that filled a tile, [2] tile pieces they loaded (sum), [3] their groups (sum),
+// [4] of those, groups that hold a lane whose (cell, hints) did not change: their pieces were in the tile already
+__device__ unsigned long long g_prof_ext[8];
 #endif
 
 template <int MAXV, int TAG = 0>  // (TAG: instantiations of the relocating RK4 kernel's own, see kNvReloc)
@@ -1850,6 +1854,9 @@ traj_kernel(std::conditional_t<CAP, TrajArgsCap, TrajArgs> a) {
     // wave's LDS operations running in order: one wave per block
     static_assert(!kCoop || kTrajBlock == 64, "the cooperative tile needs one wave per block");
     constexpr bool kNbrT = MOPS_NBR_TEST && MAXV == 7 && (EULER || MOPS_NBR_RK4);  // dev::nbr_stay before a walk
+    // wave-synchronous re-anchoring (the tile Euler kernel): when one live lane is outside
+    // its stay ball, every live lane runs dev::nbr_stay and re-centres its ball
+    constexpr bool kStayW = kNbrT && kCoop && EULER;
     // per-lane edge normals (Cell::nrm); in the cooperative kernel the same LDS holds either them (a wave in
     // lane-normal mode, c.lds_n) or the wave's tile
     // groups per tile and tile pieces per live lane at most (per kernel: the RK4 one has LDS to spare)
@@ -1917,9 +1924,14 @@ traj_kernel(std::conditional_t<CAP, TrajArgsCap, TrajArgs> a) {
             const double e2p = ex * ex + ey * ey + ez * ez;
             bool stay_p = e2p < c.rs2;
             if constexpr (kNbrT) {
-                if (!stay_p && dev::nbr_stay<MAXV>(c, cell, x, y, z, a.nbr)) {
-                    stay_p = true;
-                    atomicAdd(&dev::g_prof[13], 1ull);  // lane-steps the neighbour table kept in c
+                if (kStayW ? __ballot(!stay_p) != 0ull : !stay_p) {  // (as the product path below)
+                    if (kCoop && EULER && (int)__lane_id() == __builtin_ctzll(__ballot(1)))
+                        atomicAdd(&dev::g_prof_ext[0], 1ull);  // wave-steps that execute nbr_stay
+                    const bool in = stay_p;
+                    if (dev::nbr_stay<MAXV>(c, cell, x, y, z, a.nbr) && !in) {
+                        stay_p = true;
+                        atomicAdd(&dev::g_prof[13], 1ull);  // lane-steps the neighbour table kept in c
+                    }
                 }
             }
             const bool walking = !stay_p;
@@ -1943,7 +1955,13 @@ traj_kernel(std::conditional_t<CAP, TrajArgsCap, TrajArgs> a) {
 #else
             const double e2 = ex * ex + ey * ey + ez * ez;
             bool stay = e2 < c.rs2;
-            if constexpr (kNbrT) {
+            if constexpr (kStayW) {
+                // one lane outside its ball: every live lane takes the test and, where it proves that c stays,
+                // a fresh ball around its own position.  A lane inside its ball stays whatever the test answers
+                // (it keeps the old anchor then), so the wave's next miss is its worst lane's, not the first of
+                // 64 balls that age on their own
+                if (__ballot(!stay) != 0ull) stay |= dev::nbr_stay<MAXV>(c, cell, x, y, z, a.nbr);
+            } else if constexpr (kNbrT) {
                 if (!stay) stay = dev::nbr_stay<MAXV>(c, cell, x, y, z, a.nbr);  // exact: every bisector clear
             }
 #if defined(MOPS_ABL_NOWALK)  // ablation: never walk (wrong results; the walks' cost bound)
@@ -2021,6 +2039,21 @@ traj_kernel(std::conditional_t<CAP, TrajArgsCap, TrajArgs> a) {
                                         (hint0 == __builtin_amdgcn_readlane(hint0, l2)) &
                                         (hint1 == __builtin_amdgcn_readlane(hint1, l2)));
                     }
+                    // groups that hold a lane whose (cell, hints) did not change since the tile was filled: their
+                    // pieces are still in the tile (a lower bound of the groups whose key survives)
+                    if (EULER && coop && have_tile && !c.lds_n) {
+                        int gs = 0;
+                        const uint64_t still = __ballot(!moved);
+                        for (uint64_t r2 = act; r2 != 0ull;) {
+                            const int l2 = __builtin_ctzll(r2);
+                            const uint64_t m2 = __ballot((cell == __builtin_amdgcn_readlane(cell, l2)) &
+                                                         (hint0 == __builtin_amdgcn_readlane(hint0, l2)) &
+                                                         (hint1 == __builtin_amdgcn_readlane(hint1, l2)));
+                            if ((m2 & still) != 0ull) ++gs;
+                            r2 &= ~m2;
+                        }
+                        if ((int)__lane_id() == __builtin_ctzll(act)) atomicAdd(&dev::g_prof_ext[4], (unsigned long long)gs);
+                    }
                     if ((int)__lane_id() == __builtin_ctzll(act)) {
                         atomicAdd(&dev::g_prof[7], 1ull);  // regroupings
                         atomicAdd(&dev::g_prof[8], (unsigned long long)gc);
@@ -2032,6 +2065,13 @@ traj_kernel(std::conditional_t<CAP, TrajArgsCap, TrajArgs> a) {
                 }
     #endif
                 if (coop) {
+    #if defined(MOPS_PROF)
+                    if (EULER && (int)__lane_id() == __builtin_ctzll(act)) {
+                        atomicAdd(&dev::g_prof_ext[1], 1ull);
+                        atomicAdd(&dev::g_prof_ext[2], (unsigned long long)(G * kTilePieces));
+                        atomicAdd(&dev::g_prof_ext[3], (unsigned long long)G);
+                    }
+    #endif
                     if (lead) {  // the group's header: {cell, nv}, then each slot's level-pair record index per field
                         const uint32_t zr = pr_zero((uint32_t)a.V, (uint32_t)a.L);
                         uint32_t r0[8], r1[8];
@@ -4362,6 +4402,16 @@ int mops_debug_prof(uint64_t* out) {
     for (int i = 0; i < 16; ++i) out[i] = h[i];
     const unsigned long long z[16] = {};
     if (hipMemcpyToSymbol(HIP_SYMBOL(dev::g_prof), z, sizeof(z)) != hipSuccess) return -1;
+    return 0;
+}
+// ... and the second counter array (dev::g_prof_ext), the first min(n, 8) words
+int mops_debug_prof_ext(uint64_t* out, int n) {
+    unsigned long long h[8];
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(dev::g_prof_ext), sizeof(h)) != hipSuccess) return -1;
+    for (int i = 0; i < n && i < 8; ++i) out[i] = h[i];
+    const unsigned long long z[8] = {};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(dev::g_prof_ext), z, sizeof(z)) != hipSuccess) return -1;
     return 0;
 }
 #endif

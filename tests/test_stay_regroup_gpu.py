@@ -1,0 +1,194 @@
+"""Cooperative pathline waves whose lanes change cell and layer often: the tile kernel's wave-synchronous
+stay-ball re-anchoring and its regroups against the CPU oracle, bit for bit.
+
+The stay ball and the tile are speed-only state, so every comparison is tests/test_gpu_parity.py's
+assert_lines_match (np.array_equal on points, velocity, lastPoint, depth and death steps).  The seeds are those
+of test_pathline_cooperative_waves (14 random cells x 45..58 particles jittered by 20 km), here on the 41k-cell
+mesh with 30-minute steps over 10 days, so that most particles cross several cell edges while the cells stay
+shared between the lanes of a wave.
+"""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+DT, DAYS, REC = 1800, 10, 86400
+TOL_RAD = 1e-6
+
+
+def _ang_err(a, b):
+    na = np.linalg.norm(a, axis=-1)
+    nb = np.linalg.norm(b, axis=-1)
+    both = (na > 0) & (nb > 0) & np.isfinite(na) & np.isfinite(nb)
+    c = np.sum(a * b, -1) / np.where(both, na * nb, 1.0)
+    return np.where(both, np.arccos(np.clip(c, -1.0, 1.0)), 0.0)
+
+
+def assert_lines_match(got, ref, label):
+    """Bit-exact match of one run against the oracle: death steps, where zeros and NaN fall, every point,
+    velocity and final depth (the semantics of tests/test_gpu_parity.py's assert_lines_match)."""
+    assert np.array_equal(got["death_step"], ref["death"]), f"{label}: death steps differ"
+    for key in ("points", "lastPoint"):
+        a, b = got[key], ref[key]
+        assert np.array_equal(np.linalg.norm(a, axis=-1) == 0, np.linalg.norm(b, axis=-1) == 0), f"{label} {key} zeros"
+        assert np.array_equal(np.isfinite(a), np.isfinite(b)), f"{label} {key} NaN pattern"
+        e = _ang_err(a, b)
+        assert e.max() < TOL_RAD, f"{label} {key}: max angular error {e.max()} rad"
+        assert np.array_equal(a, b, equal_nan=True), (
+            f"{label} {key}: not bit-exact ({np.mean(np.all(a == b, axis=-1)):.6f} of points equal, "
+            f"max angular error {e.max():.3e} rad)")
+    assert np.array_equal(got["velocity"], ref["velocity"], equal_nan=True), f"{label}: velocity not bit-exact"
+    assert np.array_equal(got["final_depth"], ref["final_depth"], equal_nan=True), f"{label}: depth not bit-exact"
+
+
+def _seeds(mesh, zlevel=False):
+    rng = np.random.default_rng(41)
+    cc = np.asarray(mesh.cellCoord, dtype=np.float64).reshape(-1, 3)
+    cells = rng.choice(mesh.nCells, 14, replace=False)
+    seeds, depths = [], []
+    for j, c in enumerate(cells):
+        k = 45 + j  # uneven counts: groups straddle wave boundaries
+        u = cc[c] / np.linalg.norm(cc[c])
+        jit = rng.normal(size=(k, 3)) * 2.0e4
+        p = u + (jit - np.outer(jit @ u, u)) / 6.371e6
+        seeds.append(p / np.linalg.norm(p, axis=1, keepdims=True) * 6.37101e6)
+        d = np.full(k, 300.0) if j < 7 else np.where(np.arange(k) % 2 == 0, 300.0, 1100.0)
+        if zlevel:  # around the local bottom of the shallowest columns (1500-4000 m)
+            d = np.where(np.arange(k) % 3 == 0, 1450.0 + 10.0 * j, d)
+        depths.append(d)
+    seeds = np.concatenate(seeds)
+    assert len(seeds) == 721 and len(seeds) % 64 != 0  # (the last wave is partial)
+    return seeds, np.concatenate(depths).astype(np.float32)
+
+
+@pytest.fixture(scope="module")
+def case(gpu, engine_lib, oracle_lib, medium_case):
+    """The device mesh, both fields and their oracle counterparts, per topography, made once."""
+    from mops_amd import synth
+    from mops_amd.engine import DeviceField, DeviceMesh
+    mesh, s0, s1 = medium_case
+    dm = DeviceMesh.from_mesh(mesh)
+    made = {}
+
+    def get(topo):
+        if topo not in made:
+            if topo == "zlevel":
+                a = synth.make_snapshot(mesh, timestep=0, topography="zlevel")
+                b = synth.make_snapshot(mesh, timestep=1, phase=0.35, topography="zlevel")
+            else:
+                a, b = s0, s1
+            made[topo] = (DeviceField.from_snapshot(dm, a), DeviceField.from_snapshot(dm, b),
+                          oracle_lib.preprocess(mesh, a), oracle_lib.preprocess(mesh, b))
+        return made[topo]
+
+    return mesh, dm, get
+
+
+def _run_both(case, oracle_lib, topo, euler, back, seeds, depths, dt=DT, duration=DAYS * 86400, rec=REC):
+    from mops_amd.engine import TrajectoryConfig, run_trajectories
+    mesh, dm, get = case
+    f0, f1, r0, r1 = get(topo)
+    cfg = TrajectoryConfig(deltaT=dt, simulationDuration=duration, recordT=rec, depth=0.0, method=1 if euler else 0,
+                           direction=1 if back else 0)
+    got = run_trajectories(dm, f0, f1, cfg, seeds, depths=depths)
+    ref = oracle_lib.run(mesh, r0, r1, seeds, depths=depths, delta_t=dt, duration=duration, record_t=rec,
+                         euler=euler, backward=back, cells=got["cells"])
+    return got, ref
+
+
+def _assert_crossing_heavy(mesh, oracle_lib, ref, cells0):
+    """On the oracle's output: more than half of the particles stay alive and at least half of the live ones
+    end in another cell than they started in (so the case cannot pass without cell changes)."""
+    live = ref["death"] < 0
+    assert live.sum() > len(live) // 2
+    end = oracle_lib.knn(mesh, ref["lastPoint"][live])
+    changed = int(np.sum(end != np.asarray(cells0)[live]))
+    print(f"live {int(live.sum())} of {len(live)}, {changed} of them changed cell")
+    assert 2 * changed >= int(live.sum())
+
+
+@pytest.mark.parametrize("direction", ["forward", "backward"])
+def test_crossing_heavy_cooperative_waves(case, oracle_lib, direction):
+    """Case 1: two (cell, hint) groups in half of the cells, 480 Euler steps of 30 minutes."""
+    mesh = case[0]
+    seeds, depths = _seeds(mesh)
+    got, ref = _run_both(case, oracle_lib, "sigma", True, direction == "backward", seeds, depths)
+    assert_lines_match(got, ref, f"crossing-heavy cooperative waves ({direction})")
+    _assert_crossing_heavy(mesh, oracle_lib, ref, got["cells"])
+
+
+@pytest.mark.parametrize("direction", ["forward", "backward"])
+def test_crossing_heavy_zlevel(case, oracle_lib, direction):
+    """Case 2: z-level columns with depths near the local bottom -- hint misses change groups while the cells
+    stay, so a regroup finds some groups as they were and others new."""
+    mesh = case[0]
+    seeds, depths = _seeds(mesh, zlevel=True)
+    got, ref = _run_both(case, oracle_lib, "zlevel", True, direction == "backward", seeds, depths)
+    assert_lines_match(got, ref, f"crossing-heavy z-level waves ({direction})")
+    _assert_crossing_heavy(mesh, oracle_lib, ref, got["cells"])
+
+
+def test_launch_boundaries(gpu, case):
+    """Case 3: one launch against launches of one record period -- every launch starts with cell-centred stay
+    balls and an empty tile, a long launch carries re-anchored balls and its tile across the same steps; records
+    and final state must be identical."""
+    import torch
+    from mops_amd.engine import ParticleSet, TrajectoryConfig
+    mesh, dm, get = case
+    f0, f1, _, _ = get("sigma")
+    seeds, depths = _seeds(mesh)
+    cfg = TrajectoryConfig(deltaT=DT, simulationDuration=DAYS * 86400, recordT=REC, depth=0.0, method=1)
+    a = ParticleSet(dm, seeds, depths, cfg)
+    a.advance(f0, f1, 0, cfg.n_steps)
+    b = ParticleSet(dm, seeds, depths, cfg)
+    per = REC // DT
+    assert cfg.n_steps == DAYS * per
+    for s in range(0, cfg.n_steps, per):
+        b.advance(f0, f1, s, s + per)
+    torch.cuda.synchronize()
+    assert torch.equal(a.records, b.records)
+    for k in ("x", "y", "z", "depth", "cell", "death"):
+        assert torch.equal(getattr(a, k), getattr(b, k)), k
+    assert int((a.death < 0).sum()) > a.n // 2
+
+
+def test_fallback_and_return(case, oracle_lib):
+    """Case 4: 64 particles in 64 distinct neighbouring cells (more than MOPS_COOP_G groups: lane-normal mode,
+    which retries the tile every 64 steps) beside twenty dense waves that keep the launch on the tile kernel;
+    200 steps."""
+    mesh = case[0]
+    cc = np.asarray(mesh.cellCoord, dtype=np.float64).reshape(-1, 3)
+    coc = np.asarray(mesh.cellsOnCell, dtype=np.int64).reshape(mesh.nCells, -1) - 1
+    ne = np.asarray(mesh.nEdgesOnCell, dtype=np.int64)
+    rng = np.random.default_rng(43)
+    start = int(np.argmin(np.linalg.norm(cc / 6.371e6 - np.array([0.6, -0.64, -0.48]), axis=1)))  # South Pacific
+    patch, seen = [start], {start}
+    for c in patch:  # breadth first: 64 neighbouring cells
+        if len(patch) >= 64:
+            break
+        for nb in coc[c, :ne[c]]:
+            if 0 <= nb < mesh.nCells and nb not in seen and len(patch) < 64:
+                seen.add(int(nb)); patch.append(int(nb))
+    assert len(patch) == 64
+    seeds = [cc[patch] / np.linalg.norm(cc[patch], axis=1, keepdims=True) * 6.37101e6]
+    dense = rng.choice(mesh.nCells, 4, replace=False)
+    for c in dense:
+        u = cc[c] / np.linalg.norm(cc[c])
+        jit = rng.normal(size=(320, 3)) * 5.0e3
+        p = u + (jit - np.outer(jit @ u, u)) / 6.371e6
+        seeds.append(p / np.linalg.norm(p, axis=1, keepdims=True) * 6.37101e6)
+    seeds = np.concatenate(seeds)
+    depths = np.full(len(seeds), 300.0, dtype=np.float32)
+    got, ref = _run_both(case, oracle_lib, "sigma", True, False, seeds, depths, duration=200 * DT, rec=50 * DT)
+    assert_lines_match(got, ref, "lane-normal wave beside cooperative waves")
+    assert len(np.unique(got["cells"][:64])) == 64
+    assert (ref["death"][:64] < 0).sum() > 32 and (ref["death"][64:] < 0).sum() > 640
+
+
+def test_rk4_unchanged(case, oracle_lib):
+    """Case 5: case 1 with RK4 -- the hand-off kernel and the resumed tile kernel, which share the step loop and
+    the regroup code with the Euler kernel and keep the per-lane stay test."""
+    mesh = case[0]
+    seeds, depths = _seeds(mesh)
+    got, ref = _run_both(case, oracle_lib, "sigma", False, False, seeds, depths)
+    assert_lines_match(got, ref, "crossing-heavy cooperative waves (rk4)")
