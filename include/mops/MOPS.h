@@ -159,6 +159,16 @@ struct TrajectorySettings {
     // to streamlines as well.  A layer outside [0, nVertLevels), or sampleAttributes with it, follows the
     // reference's error convention: Error() and an empty list.
     int fixedLayer = -1;
+    // This engine's extension, a horizontal random walk on top of the advection (mops_diffusion, mops_traj.h;
+    // default 0: none, the same bytes as before).  diffusivity: the eddy diffusivity Kh in m^2/s; randomSeed: the
+    // 64-bit key of the counter-based generator; randomEpoch: a counter word the caller owns, so that successive
+    // calls with one seed draw different deviates.  Particle i of the call draws with id i: a run is reproducible
+    // to the bit.  With diffusivity > 0, MOPS_RunStreamLine without fixedLayer and MOPS_RunPathLine with
+    // sampleAttributes, and a negative or non-finite diffusivity always, follow the reference's error convention:
+    // Error() and an empty list.
+    double diffusivity = 0.0;
+    unsigned long long randomSeed = 0;
+    unsigned int randomEpoch = 0;
 };
 
 struct SamplingSettings {

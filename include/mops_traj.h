@@ -347,6 +347,64 @@ mops_status mops_traj_advance_layer(const mops_mesh* mesh, const void* d_front_l
                                     const mops_traj_cfg* cfg, const mops_particles* particles, int64_t step_begin,
                                     int64_t step_end, double* d_records, int64_t record_stride, void* stream);
 
+/* ---- random-walk horizontal diffusion (no reference counterpart) ----------- */
+
+/* A horizontal random walk with a constant eddy diffusivity kh (m^2/s; Visser's walk with uniform deviates): one
+ * kick per live particle per step, after the step's position update (the vertical update and its renormalisation
+ * included) and before the record test, so records hold the kicked position; the recorded velocity stays the
+ * advective one.  A particle that dies at a step gets no kick at that step.  All of it in FP64 without
+ * contraction, len(v) = sqrt((x*x + y*y) + z*z), every `/` and sqrt correctly rounded.
+ *
+ * Generator: Philox4x32-10 as in Random123 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 /
+ * 0xBB67AE85, 10 rounds) with key = (seed & 0xffffffff, seed >> 32) and counter = (gid & 0xffffffff, gid >> 32,
+ * step, epoch): gid = id_base + d_id[particle] (d_id NULL: the particle's index in the arrays) is the 64-bit
+ * global particle id, step the call's global step index, epoch a word the caller owns (a chain of calls sets it
+ * to the call's index).  So a run's bytes do not depend on how it is split into launches, re-sorted, compacted or
+ * spread over devices, as long as every particle keeps its id.
+ * Deviates: R1 from output word 0, R2 from word 1, R = ((double)(int32_t)w + 0.5) * 2^-31 -- exact, symmetric,
+ * in (-1, 1), never 0, variance 1/3.
+ * Kick of p = (x, y, z):
+ *   s   = sqrt(6.0 * kh * (double)|delta_t|)                       (once, on the host: mops_diffusion_scale)
+ *   r   = len(p), rho = sqrt(x*x + y*y)
+ *   e   = (-y/rho, x/rho, 0) if rho > 1e-6, else (1, 0, 0)         (east)
+ *   n   = ((0.0 - z*e_y)/r, (z*e_x)/r, (x*e_y - y*e_x)/r)          (north)
+ *   a   = R1*s, b = R2*s, d = (a*e_x + b*n_x, a*e_y + b*n_y, b*n_z)
+ *   p'  = CalcPositionAfterRotation(p, axis = p x d, theta = len(d) / max(1e-12, r))
+ * with the cross-product order of the Euler step.  No renormalisation follows: the kick is horizontal, depth and
+ * radius are untouched.  A kick onto land or out of the mesh kills the particle at the next step by the existing
+ * rules.  Backward runs use |delta_t|.
+ *
+ * kh == 0 runs no kick code: every entry below forwards to the entry it mirrors (the same bytes).  kh < 0 or a
+ * non-finite kh is MOPS_ERR_INVALID before any launch. */
+typedef struct {
+    double kh;                           /* eddy diffusivity, m^2/s */
+    uint64_t seed;                       /* the Philox key */
+    uint32_t epoch;                      /* counter word 3 */
+    int64_t id_base;                     /* added to every id */
+    const int32_t* d_id;                 /* device ids [n], indexed like the particle arrays; NULL = the index */
+} mops_diffusion;
+
+/* sqrt(6.0 * kh * (double)|delta_t|) as the entries form it. */
+double mops_diffusion_scale(double kh, int64_t delta_t);
+
+/* mops_traj_advance with the kick, for pathlines: every method (MOPS_EULER, MOPS_RK4, MOPS_RK4_RELOCATE), a
+ * per-lane kernel (no cooperative tile, no capture).  MOPS_ERR_UNSUPPORTED for back == NULL with kh > 0. */
+mops_status mops_traj_advance_diffuse(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                      const mops_traj_cfg* cfg, const mops_particles* particles,
+                                      const mops_diffusion* diffusion, int64_t step_begin, int64_t step_end,
+                                      double* d_records, int64_t record_stride, void* stream);
+
+/* mops_traj_advance_layer with the kick: streamlines (d_back_layer NULL) and pathlines, every method. */
+mops_status mops_traj_advance_layer_diffuse(const mops_mesh* mesh, const void* d_front_layer,
+                                            const void* d_back_layer, const mops_traj_cfg* cfg,
+                                            const mops_particles* particles, const mops_diffusion* diffusion,
+                                            int64_t step_begin, int64_t step_end, double* d_records,
+                                            int64_t record_stride, void* stream);
+
+/* Self-test of the generator on the device: d_in holds n rows of {4 counter words, 2 key words}; d_words gets the
+ * 4 output words per row, d_r the deviates {R1, R2} of words 0 and 1. */
+mops_status mops_selftest_philox(int64_t n, const uint32_t* d_in, uint32_t* d_words, double* d_r, void* stream);
+
 /* FinalizeTrajectoryLines[WithAttrs] + RemoveNaNTrajectoriesAndReindex
  * (src/Common/TrajectoryCommon.h:57-190) on the device: seeds [n*3] and
  * records -> points/velocity [n*(K+1)*3], temperature/salinity [n*(K+1)]
@@ -778,6 +836,24 @@ mops_status mops_run_trajectories_layer(const mops_mesh* mesh, const mops_field*
                                         double* h_velocity, double* h_temperature, double* h_salinity,
                                         double* h_last_point, double* h_final_pos, float* h_final_depth,
                                         int32_t* h_death_step, void* stream);
+
+/* mops_run_trajectories / mops_run_trajectories_layer with the random walk (mops_diffusion above): the particle
+ * ids are id_base + the seed index (d_id is not read).  kh == 0 is the call without it; MOPS_ERR_INVALID for a
+ * negative or non-finite kh, MOPS_ERR_UNSUPPORTED for a depth-mode streamline with kh > 0, before any device work. */
+mops_status mops_run_trajectories_diffuse(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                          const mops_traj_cfg* cfg, const mops_diffusion* diffusion, int64_t n,
+                                          const double* h_seeds, const float* h_depths, float depth,
+                                          int32_t* h_cells, double* h_points, double* h_velocity,
+                                          double* h_temperature, double* h_salinity, double* h_last_point,
+                                          double* h_final_pos, float* h_final_depth, int32_t* h_death_step,
+                                          void* stream);
+mops_status mops_run_trajectories_layer_diffuse(const mops_mesh* mesh, const mops_field* front,
+                                                const mops_field* back, const mops_traj_cfg* cfg, int32_t layer,
+                                                const mops_diffusion* diffusion, int64_t n, const double* h_seeds,
+                                                const float* h_depths, float depth, int32_t* h_cells,
+                                                double* h_points, double* h_velocity, double* h_temperature,
+                                                double* h_salinity, double* h_last_point, double* h_final_pos,
+                                                float* h_final_depth, int32_t* h_death_step, void* stream);
 
 /* mops_run_trajectories for a PathLine with the attribute channel
  * (Kernel::PathLine's current_attrs, MPASOVisualizerKernels.cpp:1288-1324,

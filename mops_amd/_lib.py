@@ -23,6 +23,8 @@ EXPORTED = (
     "mops_traj_num_records", "mops_traj_num_steps", "mops_traj_advance", "mops_traj_finalize", "mops_traj_last_points",
     "mops_layer_velocity_bytes", "mops_field_layer_velocity", "mops_traj_advance_layer", "mops_run_trajectories_layer",
     "mops_traj_alpha_table",
+    "mops_diffusion_scale", "mops_traj_advance_diffuse", "mops_traj_advance_layer_diffuse", "mops_selftest_philox",
+    "mops_run_trajectories_diffuse", "mops_run_trajectories_layer_diffuse",
     "mops_traj_sample_attrs", "mops_traj_advance_sampled", "mops_traj_finalize_attrs", "mops_run_pathline_attrs",
     "mops_traj_capture_bytes", "mops_traj_capture_plan", "mops_traj_advance_captured",
     "mops_remove_nan_lines", "mops_remove_nan_ragged", "mops_run_trajectories", "mops_build_id",
@@ -69,6 +71,12 @@ class Particles(C.Structure):
     _fields_ = [("n", C.c_int64), ("d_x", C.c_void_p), ("d_y", C.c_void_p), ("d_z", C.c_void_p),
                 ("d_depth", C.c_void_p), ("d_cell", C.c_void_p), ("d_death_step", C.c_void_p),
                 ("d_order", C.c_void_p), ("d_n_live", C.c_void_p)]
+
+
+class Diffusion(C.Structure):
+    """mops_diffusion: the random walk's diffusivity (m^2/s), Philox seed, epoch word and particle ids."""
+    _fields_ = [("kh", C.c_double), ("seed", C.c_uint64), ("epoch", C.c_uint32), ("id_base", C.c_int64),
+                ("d_id", C.c_void_p)]
 
 
 class PermArray(C.Structure):
@@ -169,6 +177,17 @@ def load(path: str | None = None):
     lib.mops_traj_advance_layer.restype = st
     lib.mops_run_trajectories_layer.argtypes = [P, P, P, P, I32, I64, P, P, C.c_float, P, P, P, P, P, P, P, P, P, P]
     lib.mops_run_trajectories_layer.restype = st
+    lib.mops_diffusion_scale.argtypes = [C.c_double, I64]; lib.mops_diffusion_scale.restype = C.c_double
+    lib.mops_traj_advance_diffuse.argtypes = [P, P, P, P, P, P, I64, I64, P, I64, P]
+    lib.mops_traj_advance_diffuse.restype = st
+    lib.mops_traj_advance_layer_diffuse.argtypes = [P, P, P, P, P, P, I64, I64, P, I64, P]
+    lib.mops_traj_advance_layer_diffuse.restype = st
+    lib.mops_selftest_philox.argtypes = [I64, P, P, P, P]; lib.mops_selftest_philox.restype = st
+    lib.mops_run_trajectories_diffuse.argtypes = [P, P, P, P, P, I64, P, P, C.c_float, P, P, P, P, P, P, P, P, P, P]
+    lib.mops_run_trajectories_diffuse.restype = st
+    lib.mops_run_trajectories_layer_diffuse.argtypes = [P, P, P, P, I32, P, I64, P, P, C.c_float, P, P, P, P, P, P, P,
+                                                        P, P, P]
+    lib.mops_run_trajectories_layer_diffuse.restype = st
     lib.mops_traj_finalize.argtypes = [I64, I64, P, P, I64, I32, P, P, P, P, P, P, P]
     lib.mops_traj_finalize.restype = st
     lib.mops_traj_last_points.argtypes = [I64, I64, P, P, I64, P, P, P]

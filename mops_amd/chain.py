@@ -151,7 +151,8 @@ class PathlineChain:
             compute_stream=None, on_pair=None, timing=None, segment_steps: int = -1, reorder: bool = True,
             record_stride: int | None = None, defer_lines: bool = False, compact: bool | None = None,
             compact_chunks: int = 6, on_lines=None, lines_chunk: int | None = None, attrs: bool = False,
-            capture_slots: int | None = None, density=None, layer: int | None = None):
+            capture_slots: int | None = None, density=None, layer: int | None = None, diffusivity: float = 0.0,
+            seed: int = 0, epochs=None):
         """Run all pairs; returns device tensors {points, velocity, temperature,
         salinity, lastPoint, death_step (of the last pair)} when ``keep_lines``,
         else only lastPoint/death_step.  ``on_pair(p, last, ps)`` is called after pair p
@@ -210,8 +211,19 @@ class PathlineChain:
         (DeviceField.layer_velocity), made on the stream that builds or refills the field, so pair p's back
         slice is pair p + 1's front and a field rebuilt in place gets its slice again.  Works in every mode
         above except ``attrs`` (ValueError before any launch); density and FTLE maps become maps of the layer.
-        None: the depth mode, unchanged."""
+        None: the depth mode, unchanged.
+        ``diffusivity`` (m^2/s), ``seed``: the horizontal random walk (TrajectoryConfig.diffusivity; mops_diffusion
+        in mops_traj.h) in every pair, keyed by ``seed``, the particle's index in ``seeds`` and the pair's global
+        step, with the epoch word set to the pair index so that no two pairs draw the same deviates (``epochs``: a
+        list of one word per pair instead).  Works in every mode above except ``attrs`` (ValueError before any
+        launch).  0: no kick code runs, unchanged."""
         import torch
+        if not (float(diffusivity) >= 0.0) or not np.isfinite(float(diffusivity)):
+            raise ValueError(f"diffusivity must be finite and >= 0, not {diffusivity!r}")
+        if float(diffusivity) > 0.0 and attrs:
+            raise ValueError("diffusivity: attributes are not sampled with diffusivity > 0")
+        if epochs is not None and len(epochs) != len(self.gaps):
+            raise ValueError(f"epochs: one word per pair ({len(self.gaps)})")
         if layer is not None:
             if attrs:
                 raise ValueError("layer: attributes are not sampled in the layer mode")
@@ -246,8 +258,9 @@ class PathlineChain:
         side = torch.cuda.Stream(device=dev)
         cfgs = [TrajectoryConfig(deltaT=int(delta_t), simulationDuration=int(g), recordT=int(record_t),
                                  depth=float(np.float32(depth)), direction=int(direction), method=int(method),
-                                 layer=layer)
-                for g in self.gaps]
+                                 layer=layer, diffusivity=float(diffusivity), seed=int(seed),
+                                 epoch=int(p if epochs is None else epochs[p]))
+                for p, g in enumerate(self.gaps)]
         for c in cfgs:
             if c.n_steps <= 0 or c.n_records <= 0:
                 raise ValueError("invalid trajectory settings for a pair (deltaT/recordT vs the snapshot gap "

@@ -11,6 +11,9 @@ Mirrors the reference's command-line driver (CLI/main.cpp) option for option:
     --vti          extension: also write the VTI of the reference's MOPS_VTK build branch
     --layer K      extension: the streamline advects within model layer K (TrajectorySettings.fixedLayer)
                    instead of at the fixed depth; absent = the reference's run
+    --kh KH        extension: a horizontal random walk of eddy diffusivity KH (m^2/s) on top of the streamline
+                   (TrajectorySettings.diffusivity); needs --layer
+    --seed N       extension: the random walk's seed (TrajectorySettings.randomSeed, default 0)
 
 and its run (CLI/main.cpp:94-262): grid and one solution per timestep from the
 YAML (initGrid_DemoLoading / initSolution_DemoLoading, with temperature and
@@ -52,6 +55,8 @@ def parse_command_line(argv):
     p.add_argument("-d", "--depth", type=float, default=10.0, help="Fixed depth")
     p.add_argument("--vti", action="store_true", help="Also write the remapped images as VTK ImageData")
     p.add_argument("--layer", type=int, default=None, help="Streamline within this model layer (default: at the depth)")
+    p.add_argument("--kh", type=float, default=0.0, help="Horizontal eddy diffusivity in m^2/s (needs --layer)")
+    p.add_argument("--seed", type=int, default=0, help="Seed of the random walk")
     p.add_argument("-h", "--help", action="store_true", help="Print this information")
     args = p.parse_args(argv)
     if args.help:
@@ -62,6 +67,15 @@ def parse_command_line(argv):
         return None
     if args.layer is not None and args.layer < 0:
         print("[ERROR]::--layer must be a model layer index (>= 0).")
+        return None
+    if not (args.kh >= 0.0) or not np.isfinite(args.kh):
+        print("[ERROR]::--kh must be a finite diffusivity (>= 0).")
+        return None
+    if args.kh > 0.0 and args.layer is None:
+        print("[ERROR]::--kh needs --layer (the streamline at a fixed depth has no diffusion).")
+        return None
+    if args.seed < 0 or args.seed >= 2 ** 64:
+        print("[ERROR]::--seed must be in [0, 2^64).")
         return None
     args.range = _int_list(args.range)
     return args
@@ -156,6 +170,8 @@ def main(argv=None) -> int:
     cfg.fileName = f"traj_line_{timesteps[0]}"
     if args.layer is not None:
         cfg.fixedLayer = args.layer
+    cfg.diffusivity = args.kh
+    cfg.randomSeed = args.seed
     if len(timesteps) == 1:
         print("== single timestep [streamline] ==")
         lines = M.MOPS_RunStreamLine(cfg, sample_points)

@@ -134,6 +134,21 @@ std::vector<TrajectoryLine> run(TrajectorySettings* config, std::vector<Cartesia
         Error("[%s] sampleAttributes is not supported with relocateStages", stage);
         return {};
     }
+    // TrajectorySettings::diffusivity: the random walk (mops_run_trajectories_diffuse / _layer_diffuse)
+    const double kh = config->diffusivity;
+    if (!(kh >= 0.0) || !std::isfinite(kh)) {
+        Error("[%s] diffusivity must be finite and >= 0", stage);
+        return {};
+    }
+    if (kh > 0.0 && layer < 0 && !pathline) {
+        Error("[%s] diffusivity needs fixedLayer for streamlines", stage);
+        return {};
+    }
+    if (kh > 0.0 && config->sampleAttributes) {
+        Error("[%s] sampleAttributes is not supported with diffusivity", stage);
+        return {};
+    }
+    const mops_diffusion dif{kh, (uint64_t)config->randomSeed, (uint32_t)config->randomEpoch, 0, nullptr};
     const int64_t n = (int64_t)pts.size();
     const bool per_particle = config->hasPerParticleDepths() && config->particle_depths.size() == pts.size();
     std::vector<float> depths(pts.size(), config->depth);  // BuildEffectiveDepths (TrajectoryCommon.h:29-41)
@@ -160,7 +175,21 @@ std::vector<TrajectoryLine> run(TrajectorySettings* config, std::vector<Cartesia
     const int64_t P = K + 1;
     std::vector<double> hp((size_t)(n * P * 3)), hv((size_t)(n * P * 3)), ht((size_t)(n * P)), hs((size_t)(n * P)),
         hl((size_t)(n * 3));
-    if (layer >= 0) {
+    if (kh > 0.0) {
+        if (layer >= 0)
+            check(mops_run_trajectories_layer_diffuse(g_app.mesh, g_app.front, pathline ? g_app.back : nullptr, &cfg,
+                                                      layer, &dif, n, reinterpret_cast<const double*>(pts.data()),
+                                                      depths.data(), config->depth, nullptr, hp.data(), hv.data(),
+                                                      ht.data(), hs.data(), hl.data(), nullptr, nullptr, nullptr,
+                                                      nullptr),
+                  "mops_run_trajectories_layer_diffuse");
+        else
+            check(mops_run_trajectories_diffuse(g_app.mesh, g_app.front, g_app.back, &cfg, &dif, n,
+                                                reinterpret_cast<const double*>(pts.data()), depths.data(),
+                                                config->depth, nullptr, hp.data(), hv.data(), ht.data(), hs.data(),
+                                                hl.data(), nullptr, nullptr, nullptr, nullptr),
+                  "mops_run_trajectories_diffuse");
+    } else if (layer >= 0) {
         check(mops_run_trajectories_layer(g_app.mesh, g_app.front, pathline ? g_app.back : nullptr, &cfg, layer, n,
                                           reinterpret_cast<const double*>(pts.data()), depths.data(), config->depth,
                                           nullptr, hp.data(), hv.data(), ht.data(), hs.data(), hl.data(), nullptr,

@@ -2707,6 +2707,317 @@ __global__ void __launch_bounds__(kTrajBlock, (LayerWaves<MAXV, METHOD>::value))
     if (died >= 0 || step_end == (int)a.n_steps) dev::clear_records(a.rec, a.rec_stride, pid, (rec_k == 0 && rec0) ? 1 : rec_k, a.K);
 }
 
+// ===========================================================================
+// random-walk horizontal diffusion (mops_traj_advance_diffuse, mops_traj_advance_layer_diffuse; DESIGN.md
+// section 3.20)
+// ===========================================================================
+// The per-lane step loops above -- the layer step (traj_layer_kernel) and the depth-mode pathline step (the Euler
+// rotation, RK4 in the step's cell, RK4 with relocated stages as traj_rk4_reloc_kernel) -- with ONE kick per live
+// particle per step after the step's position update (vertical update and renormalisation included) and before the
+// record test.  The kick (include/mops_traj.h has the full statement): two uniform deviates R1, R2 in (-1, 1) from
+// Philox4x32-10 keyed by the run's seed with the counter (particle id lo, hi, step, epoch), a displacement
+// d = R1 s e + R2 s n in the local east / north frame with s = sqrt(6 Kh |dt|), and the Euler step's rotation of p
+// about p x d by |d| / max(1e-12, |p|).  No renormalisation after it; a particle that dies at a step gets no kick.
+// One lane per particle, no tile, no hand-off, no capture, no LDS normals; instantiations of its own wherever a
+// shared helper has a tag (dev::kNvDiff, walk<MAXV, 3>), so no existing kernel's code moves.
+struct TrajDiffuseArgs : TrajLayerArgs {
+    double kick_s;                  // sqrt(6 Kh |delta_t|), formed once on the host
+    uint32_t key0, key1;            // seed & 0xffffffff, seed >> 32
+    uint32_t epoch;                 // counter word 3
+    int64_t id_base;                // gid = id_base + id[pid]
+    const int32_t* __restrict__ id;  // per particle (NULL: pid)
+};
+
+namespace dev {
+constexpr int kNvDiff = -4;  // the general vertex count in instantiations of the diffusion kernel's own (see kNvSample)
+
+__device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0,
+                                             uint32_t k1) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+}
+
+// Philox4x32-10 (Random123): ten rounds, the key bumped by the Weyl constants between them.  Words that depend only
+// on wave-uniform inputs (the key schedule, the first round's product of counter word 2) stay scalar by themselves.
+__device__ __forceinline__ void philox4x32_10(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0,
+                                              uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        philox_round(c0, c1, c2, c3, k0, k1);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+
+// The uniform deviate of one output word: ((double)(int32_t)w + 0.5) * 2^-31 -- exact, symmetric, in (-1, 1), never 0
+__device__ __forceinline__ double philox_deviate(uint32_t w) { return ((double)(int32_t)w + 0.5) * 0x1p-31; }
+
+// The kick of position (x, y, z) by the deviates R1 (east), R2 (north) and the scale s
+__device__ __forceinline__ void kick(unsigned salt, double s, double R1, double R2, double& x, double& y, double& z) {
+    const double r = len3(x, y, z);
+    const double rho = xsqrt(x * x + y * y);
+    double ex = 1.0, ey = 0.0;
+    if (rho > 1e-6) { ex = -y / rho; ey = x / rho; }
+    const double nx = (0.0 - z * ey) / r, ny = (z * ex) / r, nz = (x * ey - y * ex) / r;
+    const double ka = R1 * s, kb = R2 * s;
+    const double dx = ka * ex + kb * nx, dy = ka * ey + kb * ny, dz = kb * nz;
+    const double ax = y * dz - z * dy, ay = z * dx - x * dz, az = x * dy - y * dx;
+    const double th = len3(dx, dy, dz) / dmax(1e-12, r);
+    double ox, oy, oz;
+    rotate(salt, x, y, z, ax, ay, az, th, ox, oy, oz);
+    x = ox; y = oy; z = oz;
+}
+
+// dev::relocate / dev::locate_layer with the diffusion kernel's own walk instantiation
+template <int MAXV>
+__device__ __forceinline__ int locate_diffuse(Cell<MAXV>& c, int cell, double x, double y, double z, const TrajArgs& a) {
+    const double ex = x - c.cx, ey = y - c.cy, ez = z - c.cz;
+    if (ex * ex + ey * ey + ez * ez < c.rs2) return cell;
+    if constexpr (MOPS_NBR_TEST && MAXV == 7) {
+        if (nbr_stay<MAXV>(c, cell, x, y, z, a.nbr)) return cell;
+    }
+    return walk<MAXV, 3>(c, cell, x, y, z, a.cellrec, a.cxyz, a.C);
+}
+
+// eval_layer with the diffusion kernel's own weights instantiation
+template <int MAXV, bool PATH>
+__device__ __forceinline__ bool eval_layer_diffuse(const Cell<MAXV>& c, int L, int V, const double4* __restrict__ s0,
+                                                   const double4* __restrict__ s1, double px, double py, double pz,
+                                                   double alpha, double& hx, double& hy, double& hz) {
+    double w[MAXV];
+    bool wfin;
+    if (!weights<MAXV, kNvDiff>(c, L, V, px, py, pz, w, wfin)) return false;
+    double fx = 0.0, fy = 0.0, fz = 0.0, gx = 0.0, gy = 0.0, gz = 0.0;
+#pragma unroll
+    for (int v = 0; v < MAXV; ++v) {
+        if (v < c.nv) {
+            const double2* q = reinterpret_cast<const double2*>(s0 + c.vid[v]);
+            const double2 a = q[0], b = q[1];
+            fx += w[v] * a.x; fy += w[v] * a.y; fz += w[v] * b.x;
+            if constexpr (PATH) {
+                const double2* qb = reinterpret_cast<const double2*>(s1 + c.vid[v]);
+                const double2 e = qb[0], f = qb[1];
+                gx += w[v] * e.x; gy += w[v] * e.y; gz += w[v] * f.x;
+            }
+        }
+    }
+    if constexpr (PATH) {
+        hx = gx * alpha + fx * (1.0 - alpha);
+        hy = gy * alpha + fy * (1.0 - alpha);
+        hz = gz * alpha + fz * (1.0 - alpha);
+    } else {
+        hx = fx; hy = fy; hz = fz;
+    }
+    return !(len3(hx, hy, hz) < 1e-12);
+}
+}  // namespace dev
+
+constexpr int kDiffLayerStream = 0, kDiffLayerPath = 1, kDiffDepthPath = 2;  // traj_diffuse_kernel's MODE
+
+template <int MAXV>
+struct DiffuseWaves {
+    static constexpr int value = MAXV <= 7 ? 2 : 1;  // (as the layer and relocating kernels; the resource report: DESIGN 3.20)
+};
+
+template <int MAXV, int MODE, int METHOD>
+__global__ void __launch_bounds__(kTrajBlock, (DiffuseWaves<MAXV>::value)) traj_diffuse_kernel(TrajDiffuseArgs a) {
+    constexpr bool EULER = METHOD == MOPS_EULER, RELOC = METHOD == MOPS_RK4_RELOCATE;
+    constexpr bool DEPTH = MODE == kDiffDepthPath, PATH = MODE != kDiffLayerStream;
+    // the XCD block remap over the live slots (traj_kernel)
+    unsigned nblk = gridDim.x;
+    int64_t n = a.n;
+    if (a.n_live) {
+        const int64_t nl = *a.n_live;
+        n = nl < n ? nl : n;
+        nblk = (unsigned)((n + blockDim.x - 1) / blockDim.x);
+    }
+    const unsigned b = blockIdx.x;
+    if (b >= nblk) return;
+    const unsigned xcd = b % 8u, q = nblk / 8u, r8 = nblk % 8u;
+    const unsigned blk = (xcd < r8 ? xcd * (q + 1u) : r8 * (q + 1u) + (xcd - r8) * q) + b / 8u;
+    const int64_t slot = (int64_t)blk * blockDim.x + threadIdx.x;
+    if (slot >= n) return;
+    const int64_t pid = a.order ? (int64_t)a.order[slot] : slot;
+    const int sb = (int)a.step_begin, step_end = (int)a.step_end;  // (32-bit in here: the entries check)
+    if (a.death[pid] >= 0) {  // the reference's lambda has returned
+        if (a.step_begin == 0) dev::clear_records(a.rec, a.rec_stride, pid, 0, a.K);
+        return;
+    }
+    const uint64_t gid = (uint64_t)(a.id_base + (a.id ? (int64_t)a.id[pid] : pid));  // the only per-lane counter words
+    const uint32_t gid_lo = (uint32_t)gid, gid_hi = (uint32_t)(gid >> 32);
+    double x = a.px[pid], y = a.py[pid], z = a.pz[pid];
+    float dep = a.depth[pid];
+    int cell = a.cell[pid];
+    int died = -1;
+    int hint0 = -1, hint1 = -1;  // DEPTH: previous layer per field (speed only)
+    dev::Cell<MAXV> c, cs;  // the step's cell; RELOC: the cell the current stage is evaluated in
+    c.id = -1; c.nv = 0; c.V = a.V; c.cpolyr = a.cpolyr; c.crank = a.crank; c.C = (uint32_t)a.C;
+    c.nrm = nullptr; c.lds_n = false;
+    if constexpr (RELOC || (DEPTH && !EULER)) cs = c;
+    const int C = a.C;
+    const int rec_period = (int)a.rec_period;
+    uint32_t rec_next = ~(uint32_t)0;
+    int rec_k = 0;
+    bool rec0 = sb > 0;  // record 0's step-0 part (seed position, zero velocity) written
+    if (rec_period > 0) {
+        rec_k = sb / rec_period;
+        rec_next = (uint32_t)(rec_k + 1) * (uint32_t)rec_period - 1u;
+    }
+    constexpr int GR = PairGroup<true, EULER>::value;
+    const double dt = (double)a.delta_t;
+    auto load = [&](dev::Cell<MAXV>& t, int id) {
+        if constexpr (DEPTH) dev::load_cell<MAXV, false, false>(t, id, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly);
+        else dev::load_cell_layer<MAXV>(t, id, a.cellrec, a.cxyz, a.cpoly);
+    };
+    for (int step = sb; step < step_end; ++step) {
+        if (step == 0) {  // first_loop
+            if (cell < 0 || cell >= C) { died = 0; break; }
+            load(c, cell);
+            double* r0 = a.rec;
+            r0[0 * a.rec_stride + pid] = x;
+            r0[1 * a.rec_stride + pid] = y;
+            r0[2 * a.rec_stride + pid] = z;
+            r0[3 * a.rec_stride + pid] = 0.0;  // (first_vel below, once step 0 evaluates)
+            r0[4 * a.rec_stride + pid] = 0.0;
+            r0[5 * a.rec_stride + pid] = 0.0;
+            rec0 = true;
+        } else {  // one-hop nearest-centre walk
+            if (cell < 0 || cell >= C) { died = step; break; }
+            if (c.id != cell) load(c, cell);
+            cell = dev::locate_diffuse<MAXV>(c, cell, x, y, z, a);
+            if (c.id != cell) {
+                bool have = false;
+                if constexpr (RELOC) {
+                    if (cs.id == cell) { c = cs; have = true; }  // (the cell a stage was evaluated in)
+                }
+                if (!have) load(c, cell);
+            }
+        }
+        const double d = -1.0 * (double)dep;
+        const double r = dev::len3(x, y, z);
+        double a1 = 0.0;
+        if constexpr (PATH) a1 = a.alpha_tab ? a.alpha_tab[step] : (double)step / (double)a.n_steps;  // (the same bits)
+        // one evaluation of the mode, in cell t at point (ex, ey, ez)
+        auto eval = [&](const dev::Cell<MAXV>& t, double ex, double ey, double ez, double al, double& ox, double& oy,
+                        double& oz, double& ow) -> bool {
+            if constexpr (DEPTH) {
+                return dev::eval_path<MAXV, GR, dev::kNvDiff>(t, a.L, a.V, a.f0, a.f1, ex, ey, ez, d, al, hint0, hint1, ox,
+                                                              oy, oz, ow);
+            } else {
+                ow = 0.0;
+                return dev::eval_layer_diffuse<MAXV, PATH>(t, a.L, a.V, a.s0, a.s1, ex, ey, ez, al, ox, oy, oz);
+            }
+        };
+        double hx = 0, hy = 0, hz = 0, wv = 0;
+        double nx, ny, nz;
+        if constexpr (EULER) {
+            if (!eval(c, x, y, z, a1, hx, hy, hz, wv)) { died = step; break; }
+            const double ax = y * hz - z * hy, ay = z * hx - x * hz, az = x * hy - y * hx;
+            const double speed = dev::len3(hx, hy, hz);
+            const double th = (speed * a.delta_t) / dev::dmax(1e-12, r);
+            dev::rotate((unsigned)step, x, y, z, ax, ay, az, th, nx, ny, nz);
+        } else {
+            const double a2 = PATH ? dev::dclamp(a1 + 0.5 * a.dalpha, 0.0, 1.0) : 0.0;
+            const double a4 = PATH ? dev::dclamp(a1 + a.dalpha, 0.0, 1.0) : 0.0;
+            // the four stages, one evaluation in a loop (traj_rk4_reloc_kernel), summed in the reference's
+            // association ((s1 + 2 s2) + 2 s3) + s4
+            double sx = 0, sy = 0, sz = 0, sw = 0;
+            double qx = x, qy = y, qz = z;
+            bool ok = true;
+#pragma unroll 1
+            for (int st = 0; st < 4; ++st) {
+                if (st > 0) dev::advect((unsigned)step, x, y, z, sx, sy, sz, st == 3 ? dt : dt * 0.5, qx, qy, qz);
+                const double as = st == 0 ? a1 : (st == 3 ? a4 : a2);
+                if constexpr (RELOC) {
+                    int sc = cell;
+                    if (st > 0) sc = dev::locate_diffuse<MAXV>(c, cell, qx, qy, qz, a);
+                    if (cs.id != sc) {
+                        if (sc == cell) cs = c;
+                        else load(cs, sc);
+                    }
+                    ok = eval(cs, qx, qy, qz, as, sx, sy, sz, sw);
+                } else if constexpr (DEPTH) {
+                    // (RK4 in the step's cell, evaluated through the stage copy as the relocating variant does:
+                    // evaluated in `c` itself this loop spilled 136 VGPRs at MAXV 7)
+                    if (cs.id != cell) cs = c;
+                    ok = eval(cs, qx, qy, qz, as, sx, sy, sz, sw);
+                } else {
+                    ok = eval(c, qx, qy, qz, as, sx, sy, sz, sw);
+                }
+                if (!ok) break;
+                if (st == 0) { hx = sx; hy = sy; hz = sz; wv = sw; }
+                else if (st < 3) { hx = hx + sx * 2.0; hy = hy + sy * 2.0; hz = hz + sz * 2.0; wv = wv + 2.0 * sw; }
+                else { hx = (hx + sx) / 6.0; hy = (hy + sy) / 6.0; hz = (hz + sz) / 6.0; wv = (wv + sw) / 6.0; }
+            }
+            if (!ok) { died = step; break; }
+            const double tx = x + hx * dt, ty = y + hy * dt, tz = z + hz * dt;
+            const double tl = dev::len3(tx, ty, tz);
+            if (tl > 1e-12) {
+                dev::xdiv_norm3(tx, ty, tz, tl, nx, ny, nz);
+                nx *= r; ny *= r; nz *= r;
+            }
+            else { nx = x; ny = y; nz = z; }
+        }
+        // vertical update (layer mode: w = 0, the depth keeps its value)
+        double nd = (double)dep - wv * (double)a.delta_t;
+        nd = dev::dmax(0.0, nd);
+        const double r_new = dev::dmax(1.0, r + wv * (double)a.delta_t);
+        dep = (float)nd;
+        const double nl = dev::len3(nx, ny, nz);
+        if (nl > 1e-12) {
+            dev::xdiv_norm3(nx, ny, nz, nl, nx, ny, nz);
+            nx *= r_new; ny *= r_new; nz *= r_new;
+        }
+        if (step == 0) {  // first_vel
+            a.rec[3 * a.rec_stride + pid] = hx;
+            a.rec[4 * a.rec_stride + pid] = hy;
+            a.rec[5 * a.rec_stride + pid] = hz;
+        }
+        x = nx; y = ny; z = nz;
+        {  // the kick: counter (gid lo, gid hi, step, epoch), deviates from output words 0 and 1
+            uint32_t c0 = gid_lo, c1 = gid_hi, c2 = (uint32_t)step, c3 = a.epoch;
+            dev::philox4x32_10(c0, c1, c2, c3, a.key0, a.key1);
+            dev::kick((unsigned)step, a.kick_s, dev::philox_deviate(c0), dev::philox_deviate(c1), x, y, z);
+        }
+        if ((uint32_t)step == rec_next) {  // (step + 1) % rec_period == 0, record k = (step + 1) / rec_period - 1
+            const int k = rec_k;
+            rec_next += (uint32_t)rec_period;
+            ++rec_k;
+            if (k < (int)a.K) {
+                double* rk = a.rec + (int64_t)k * 6 * a.rec_stride;
+                rk[0 * a.rec_stride + pid] = x;
+                rk[1 * a.rec_stride + pid] = y;
+                rk[2 * a.rec_stride + pid] = z;
+                rk[3 * a.rec_stride + pid] = hx;
+                rk[4 * a.rec_stride + pid] = hy;
+                rk[5 * a.rec_stride + pid] = hz;
+            }
+        }
+    }
+    a.px[pid] = x; a.py[pid] = y; a.pz[pid] = z;
+    a.depth[pid] = dep;
+    a.cell[pid] = cell;
+    if (died >= 0) a.death[pid] = died;
+    // slots never sampled: after a death, and past the last record step (traj_kernel)
+    if (died >= 0 || step_end == (int)a.n_steps) dev::clear_records(a.rec, a.rec_stride, pid, (rec_k == 0 && rec0) ? 1 : rec_k, a.K);
+}
+
+// mops_selftest_philox: row i of `in` is {4 counter words, 2 key words}
+__global__ void selftest_philox_kernel(int64_t n, const uint32_t* __restrict__ in, uint32_t* __restrict__ words,
+                                       double* __restrict__ r) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t c0 = in[6 * i], c1 = in[6 * i + 1], c2 = in[6 * i + 2], c3 = in[6 * i + 3];
+    dev::philox4x32_10(c0, c1, c2, c3, in[6 * i + 4], in[6 * i + 5]);
+    words[4 * i] = c0; words[4 * i + 1] = c1; words[4 * i + 2] = c2; words[4 * i + 3] = c3;
+    r[2 * i] = dev::philox_deviate(c0);
+    r[2 * i + 1] = dev::philox_deviate(c1);
+}
+
 // One snapshot's velocity at layer k per vertex, {vx, vy, vz, 0}: from cellVertexVelocity [V][L][3] where the field
 // holds every value, else (the fused derivation) from the level-pair records as records_to_vertex_kernel reads
 // them (level j from record j, level L-1 from the second half of record L-2)
@@ -4309,6 +4620,22 @@ static void launch_traj_layer(const TrajLayerArgs& a, bool path, int method, hip
     }
 }
 
+// mops_traj_advance_diffuse / mops_traj_advance_layer_diffuse: the per-lane diffusion kernel of the mode and method
+template <int MAXV, int MODE>
+static void launch_traj_diffuse(const TrajDiffuseArgs& a, int method, hipStream_t s) {
+    const unsigned g = (unsigned)((a.n + kTrajBlock - 1) / kTrajBlock);
+    if (method == MOPS_EULER) traj_diffuse_kernel<MAXV, MODE, MOPS_EULER><<<g, kTrajBlock, 0, s>>>(a);
+    else if (method == MOPS_RK4_RELOCATE) traj_diffuse_kernel<MAXV, MODE, MOPS_RK4_RELOCATE><<<g, kTrajBlock, 0, s>>>(a);
+    else traj_diffuse_kernel<MAXV, MODE, MOPS_RK4><<<g, kTrajBlock, 0, s>>>(a);
+}
+
+template <int MAXV>
+static void launch_traj_diffuse_mode(const TrajDiffuseArgs& a, int mode, int method, hipStream_t s) {
+    if (mode == kDiffDepthPath) launch_traj_diffuse<MAXV, kDiffDepthPath>(a, method, s);
+    else if (mode == kDiffLayerPath) launch_traj_diffuse<MAXV, kDiffLayerPath>(a, method, s);
+    else launch_traj_diffuse<MAXV, kDiffLayerStream>(a, method, s);
+}
+
 // launch_traj's pathline MAXV 7 branch with the CAP instantiations (a.cap set; mops_traj_advance_captured)
 static void launch_traj_cap(const TrajArgsCap& a, bool euler, hipStream_t s) {
     const unsigned g = (unsigned)((a.n + kTrajBlock - 1) / kTrajBlock);
@@ -5376,6 +5703,135 @@ mops_status mops_traj_advance_layer(const mops_mesh* mesh, const void* d_front_l
     return MOPS_OK;
 }
 
+// ---- random-walk horizontal diffusion ------------------------------------------
+// Kh of a mops_diffusion: false (the error set) for a null struct, a negative or a non-finite value
+static bool diffusion_valid(const char* who, const mops_diffusion* dif) {
+    if (!dif) { fail(MOPS_ERR_INVALID, std::string(who) + ": null mops_diffusion"); return false; }
+    if (!(dif->kh >= 0.0) || !std::isfinite(dif->kh)) {
+        fail(MOPS_ERR_INVALID, std::string(who) + ": the diffusivity must be finite and >= 0");
+        return false;
+    }
+    return true;
+}
+
+// Both diffusive entries past their Kh == 0 dispatch: the checks of mops_traj_advance / mops_traj_advance_layer,
+// then the per-lane diffusion kernel of the mode (layer: sl0 set, sl1 NULL = a streamline; depth: front and back)
+static mops_status traj_advance_diffuse_impl(const char* who, const mops_mesh* mesh, const mops_field* front,
+                                             const mops_field* back, const void* sl0, const void* sl1,
+                                             const mops_traj_cfg* cfg, const mops_particles* p,
+                                             const mops_diffusion* dif, int64_t step_begin, int64_t step_end,
+                                             double* d_records, int64_t record_stride, void* stream) {
+    const std::string w(who);
+    const bool layer = sl0 != nullptr;
+    if (cfg->delta_t <= 0 || cfg->record_t <= 0 || cfg->simulation_duration <= 0)
+        return fail(MOPS_ERR_INVALID, "invalid trajectory settings");
+    const int64_t K = mops_traj_num_records(cfg), n_steps = mops_traj_num_steps(cfg);
+    if (K <= 0 || n_steps <= 0) return fail(MOPS_ERR_INVALID, "invalid integration steps");
+    const bool path = layer ? sl1 != nullptr : true;
+    const int64_t rec_period = path ? cfg->record_t / cfg->delta_t : cfg->record_t / gcd64(cfg->record_t, cfg->delta_t);
+    if (n_steps > INT32_MAX || K > INT32_MAX || rec_period > INT32_MAX)
+        return fail(MOPS_ERR_INVALID, w + ": the number of steps, the number of records and the record period in "
+                                          "steps must each be below 2^31");
+    if (!layer && (front->mesh != mesh || back->mesh != mesh)) return fail(MOPS_ERR_INVALID, "field/mesh mismatch");
+    if (p->n < 0 || record_stride < p->n) return fail(MOPS_ERR_INVALID, "record_stride < n");
+    if (p->n == 0) return MOPS_OK;
+    if (!p->d_x || !p->d_y || !p->d_z || !p->d_depth || !p->d_cell || !p->d_death_step || !d_records)
+        return fail(MOPS_ERR_INVALID, w + ": null device pointer");
+    step_begin = std::max<int64_t>(step_begin, 0);
+    step_end = std::min<int64_t>(step_end, n_steps);
+    if (step_begin >= step_end) return MOPS_OK;
+    if (cfg->delta_t > INT32_MAX) return fail(MOPS_ERR_INVALID, "deltaT too large");
+    TrajDiffuseArgs a;
+    a.cellrec = mesh->d_cellrec; a.cxyz = mesh->d_cxyz; a.vxyz = mesh->d_vxyz;
+    a.C = (int)mesh->C; a.V = (int)mesh->V; a.L = mesh->L;
+    a.f0 = layer ? dev::Field{nullptr, nullptr} : dev::Field{front->d_zt, front->d_pr};
+    a.f1 = layer ? a.f0 : dev::Field{back->d_zt, back->d_pr};
+    a.mono0 = layer ? nullptr : front->d_mono;
+    a.mono1 = layer ? nullptr : back->d_mono;
+    a.order = p->d_order;
+    a.n_live = p->d_n_live;
+    a.cpoly = mesh->d_cpoly;
+    a.cnrm = mesh->d_cnrm;
+    a.alpha_tab = nullptr;
+    if (path) MOPS_TRY(alpha_table(mesh, n_steps, &a.alpha_tab));
+    a.nbr = mesh->d_nbr;
+    a.cpolyr = mesh->d_cpolyr;
+    a.crank = mesh->d_cell_rank;
+    a.coop_sel = nullptr;
+    a.handoff = 0;
+    a.px = p->d_x; a.py = p->d_y; a.pz = p->d_z; a.depth = p->d_depth; a.cell = p->d_cell; a.death = p->d_death_step;
+    a.n = p->n;
+    a.step_begin = step_begin; a.step_end = step_end; a.n_steps = n_steps;
+    const int dt_sign = (cfg->direction == MOPS_FORWARD) ? 1 : -1;
+    a.delta_t = dt_sign * (int)cfg->delta_t;
+    a.dalpha = (double)a.delta_t / (double)cfg->simulation_duration;
+    a.rec_period = rec_period;
+    a.K = K;
+    a.rec = d_records;
+    a.rec_stride = record_stride;
+    a.s0 = static_cast<const double4*>(sl0);
+    a.s1 = sl1 ? static_cast<const double4*>(sl1) : a.s0;
+    a.kick_s = mops_diffusion_scale(dif->kh, cfg->delta_t);
+    a.key0 = (uint32_t)(dif->seed & 0xffffffffu);
+    a.key1 = (uint32_t)(dif->seed >> 32);
+    a.epoch = dif->epoch;
+    a.id_base = dif->id_base;
+    a.id = dif->d_id;
+    const int method = (cfg->method == MOPS_EULER || cfg->method == MOPS_RK4_RELOCATE) ? cfg->method : MOPS_RK4;
+    const int mode = layer ? (path ? kDiffLayerPath : kDiffLayerStream) : kDiffDepthPath;
+    hipStream_t s = (hipStream_t)stream;
+    switch (mesh->maxv) {
+        case 7: launch_traj_diffuse_mode<7>(a, mode, method, s); break;
+        case 12: launch_traj_diffuse_mode<12>(a, mode, method, s); break;
+        default: launch_traj_diffuse_mode<20>(a, mode, method, s); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return MOPS_OK;
+}
+
+double mops_diffusion_scale(double kh, int64_t delta_t) {
+    const double adt = (double)(delta_t < 0 ? -delta_t : delta_t);
+    return std::sqrt(6.0 * kh * adt);
+}
+
+mops_status mops_traj_advance_diffuse(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                      const mops_traj_cfg* cfg, const mops_particles* p, const mops_diffusion* dif,
+                                      int64_t step_begin, int64_t step_end, double* d_records, int64_t record_stride,
+                                      void* stream) {
+    if (!diffusion_valid("mops_traj_advance_diffuse", dif)) return MOPS_ERR_INVALID;
+    if (dif->kh == 0.0)  // no kick code runs: the existing entry, its checks and its bytes
+        return mops_traj_advance(mesh, front, back, cfg, p, step_begin, step_end, d_records, record_stride, stream);
+    if (!mesh || !front || !cfg || !p) return fail(MOPS_ERR_INVALID, "mops_traj_advance_diffuse: invalid inputs");
+    if (!back)
+        return fail(MOPS_ERR_UNSUPPORTED, "mops_traj_advance_diffuse: depth-mode streamlines have no diffusion (back == NULL)");
+    return traj_advance_diffuse_impl("mops_traj_advance_diffuse", mesh, front, back, nullptr, nullptr, cfg, p, dif,
+                                     step_begin, step_end, d_records, record_stride, stream);
+}
+
+mops_status mops_traj_advance_layer_diffuse(const mops_mesh* mesh, const void* d_front_layer, const void* d_back_layer,
+                                            const mops_traj_cfg* cfg, const mops_particles* p,
+                                            const mops_diffusion* dif, int64_t step_begin, int64_t step_end,
+                                            double* d_records, int64_t record_stride, void* stream) {
+    if (!diffusion_valid("mops_traj_advance_layer_diffuse", dif)) return MOPS_ERR_INVALID;
+    if (dif->kh == 0.0)
+        return mops_traj_advance_layer(mesh, d_front_layer, d_back_layer, cfg, p, step_begin, step_end, d_records,
+                                       record_stride, stream);
+    if (!mesh || !cfg || !p) return fail(MOPS_ERR_INVALID, "mops_traj_advance_layer_diffuse: invalid inputs");
+    if (!d_front_layer) return fail(MOPS_ERR_INVALID, "mops_traj_advance_layer_diffuse: null layer slice");
+    if ((((uintptr_t)d_front_layer | (uintptr_t)d_back_layer) & 15u) != 0)
+        return fail(MOPS_ERR_INVALID, "mops_traj_advance_layer_diffuse: a layer slice must be 16-byte aligned");
+    return traj_advance_diffuse_impl("mops_traj_advance_layer_diffuse", mesh, nullptr, nullptr, d_front_layer,
+                                     d_back_layer, cfg, p, dif, step_begin, step_end, d_records, record_stride, stream);
+}
+
+mops_status mops_selftest_philox(int64_t n, const uint32_t* d_in, uint32_t* d_words, double* d_r, void* stream) {
+    if (n < 0 || (n > 0 && (!d_in || !d_words || !d_r))) return fail(MOPS_ERR_INVALID, "mops_selftest_philox: invalid inputs");
+    if (n == 0) return MOPS_OK;
+    selftest_philox_kernel<<<grid_for(n), kBlock, 0, (hipStream_t)stream>>>(n, d_in, d_words, d_r);
+    HIP_TRY(hipGetLastError());
+    return MOPS_OK;
+}
+
 mops_status mops_traj_finalize(int64_t n, int64_t K, const double* d_seeds, const double* d_records,
                                int64_t stride, int32_t pathline, const int32_t* d_line, double* d_points,
                                double* d_vel, double* d_tmp, double* d_sal, double* d_last, void* stream) {
@@ -5724,8 +6180,11 @@ static mops_status run_trajectories_impl(const mops_mesh* mesh, const mops_field
                                          double* h_vel, double* h_tmp, double* h_sal, double* h_last,
                                          double* h_final_pos, float* h_final_depth, int32_t* h_death, int32_t n_attr,
                                          const double* const* d_fa, const double* const* d_ba, double* h_attr_lines,
-                                         void* stream, int layer = -1) {
+                                         void* stream, int layer = -1, const mops_diffusion* dif = nullptr) {
     if (!mesh || !front || !cfg) return fail(MOPS_ERR_INVALID, "invalid inputs");  // :659-662
+    if (dif && dif->kh == 0.0) dif = nullptr;  // (validated by the caller) Kh == 0: the existing paths
+    if (dif && layer < 0 && !back)
+        return fail(MOPS_ERR_UNSUPPORTED, "mops_run_trajectories_diffuse: depth-mode streamlines have no diffusion (back == NULL)");
     if (layer >= 0) {  // the layer mode (mops_run_trajectories_layer): its range, before any device work
         if (layer >= mesh->L)
             return fail(MOPS_ERR_INVALID, "mops_run_trajectories_layer: layer " + std::to_string(layer) +
@@ -5831,9 +6290,11 @@ static mops_status run_trajectories_impl(const mops_mesh* mesh, const mops_field
                 if ((st = dmalloc(&sl1, (size_t)std::max<int64_t>(mesh->V, 1), nullptr)) != MOPS_OK) break;
                 if ((st = mops_field_layer_velocity(mesh, back, layer, sl1, stream)) != MOPS_OK) break;
             }
-            if ((st = mops_traj_advance_layer(mesh, sl0, back ? sl1 : nullptr, cfg, &prt, 0, n_steps, rec, n, stream)) !=
-                MOPS_OK)
-                break;
+            if (dif) st = mops_traj_advance_layer_diffuse(mesh, sl0, back ? sl1 : nullptr, cfg, &prt, dif, 0, n_steps, rec, n, stream);
+            else st = mops_traj_advance_layer(mesh, sl0, back ? sl1 : nullptr, cfg, &prt, 0, n_steps, rec, n, stream);
+            if (st != MOPS_OK) break;
+        } else if (dif) {
+            if ((st = mops_traj_advance_diffuse(mesh, front, back, cfg, &prt, dif, 0, n_steps, rec, n, stream)) != MOPS_OK) break;
         } else if ((st = mops_traj_advance(mesh, front, back, cfg, &prt, 0, n_steps, rec, n, stream)) != MOPS_OK) {
             break;
         }
@@ -5882,6 +6343,37 @@ mops_status mops_run_trajectories_layer(const mops_mesh* mesh, const mops_field*
     return run_trajectories_impl(mesh, front, back, cfg, n, h_seeds, h_depths, depth, h_cells, h_points, h_vel, h_tmp,
                                  h_sal, h_last, h_final_pos, h_final_depth, h_death, 0, nullptr, nullptr, nullptr, stream,
                                  layer);
+}
+
+// The one-call forms with diffusion: the particle ids are the seed indices (d_id of `dif` is not read: the call's
+// particles are its own; id_base offsets them)
+mops_status mops_run_trajectories_diffuse(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                          const mops_traj_cfg* cfg, const mops_diffusion* dif, int64_t n,
+                                          const double* h_seeds, const float* h_depths, float depth, int32_t* h_cells,
+                                          double* h_points, double* h_vel, double* h_tmp, double* h_sal, double* h_last,
+                                          double* h_final_pos, float* h_final_depth, int32_t* h_death, void* stream) {
+    if (!diffusion_valid("mops_run_trajectories_diffuse", dif)) return MOPS_ERR_INVALID;
+    mops_diffusion d = *dif;
+    d.d_id = nullptr;
+    return run_trajectories_impl(mesh, front, back, cfg, n, h_seeds, h_depths, depth, h_cells, h_points, h_vel, h_tmp,
+                                 h_sal, h_last, h_final_pos, h_final_depth, h_death, 0, nullptr, nullptr, nullptr, stream,
+                                 -1, &d);
+}
+
+mops_status mops_run_trajectories_layer_diffuse(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                                const mops_traj_cfg* cfg, int32_t layer, const mops_diffusion* dif,
+                                                int64_t n, const double* h_seeds, const float* h_depths, float depth,
+                                                int32_t* h_cells, double* h_points, double* h_vel, double* h_tmp,
+                                                double* h_sal, double* h_last, double* h_final_pos,
+                                                float* h_final_depth, int32_t* h_death, void* stream) {
+    if (!diffusion_valid("mops_run_trajectories_layer_diffuse", dif)) return MOPS_ERR_INVALID;
+    if (layer < 0) return fail(MOPS_ERR_INVALID, "mops_run_trajectories_layer_diffuse: layer " + std::to_string(layer) +
+                                                     " is negative");
+    mops_diffusion d = *dif;
+    d.d_id = nullptr;
+    return run_trajectories_impl(mesh, front, back, cfg, n, h_seeds, h_depths, depth, h_cells, h_points, h_vel, h_tmp,
+                                 h_sal, h_last, h_final_pos, h_final_depth, h_death, 0, nullptr, nullptr, nullptr, stream,
+                                 layer, &d);
 }
 
 mops_status mops_run_pathline_attrs(const mops_mesh* mesh, const mops_field* front, const mops_field* back,

@@ -56,6 +56,21 @@ class TrajectoryConfig:
     layer: int | None = None            # the layer mode (mops_traj_advance_layer): advect within model layer `layer`
                                         # with w = 0; ``depth`` is still carried (records keep their radius).  There
                                         # MOPS_RK4_RELOCATE runs for streamlines too.  None: the depth mode
+    diffusivity: float = 0.0            # horizontal eddy diffusivity Kh (m^2/s) of the random walk (mops_diffusion in
+                                        # mops_traj.h); 0: none, the existing kernels
+    seed: int = 0                       # ... its 64-bit Philox key
+    epoch: int = 0                      # ... and the counter word the caller owns (a chain: the pair index)
+
+    def diffusion(self, d_id=None, id_base: int = 0):
+        """The mops_diffusion of this configuration (``d_id``: a device pointer to the particles' int32 ids), or
+        None where ``diffusivity`` is 0.  ValueError for a negative or non-finite diffusivity."""
+        kh = float(self.diffusivity)
+        if not (kh >= 0.0) or not np.isfinite(kh):
+            raise ValueError(f"diffusivity must be finite and >= 0, not {self.diffusivity!r}")
+        if kh == 0.0:
+            return None
+        return L.Diffusion(kh, int(self.seed) & 0xFFFFFFFFFFFFFFFF, int(self.epoch) & 0xFFFFFFFF, int(id_base),
+                           None if d_id is None else C.c_void_p(int(d_id)))
 
     def ctype(self) -> L.TrajCfg:
         return L.TrajCfg(int(self.deltaT), int(self.simulationDuration), int(self.recordT), int(self.direction),
@@ -299,6 +314,20 @@ def run_trajectories(mesh: DeviceMesh, front: DeviceField, back: DeviceField | N
     dep = None if depths is None else np.ascontiguousarray(depths, dtype=np.float32)
     cl = np.full(n, -1, dtype=np.int32) if cells is None else np.ascontiguousarray(cells, dtype=np.int32).copy()
     c = cfg.ctype()
+    dif = _diffusion_of(cfg, back, attrs, "run_trajectories")
+    if dif is not None:  # the seed indices are the particle ids
+        hb = None if back is None else back.handle
+        tail = (n, _ptr(seeds), _ptr(dep), C.c_float(cfg.depth), _ptr(cl), _ptr(out["points"]), _ptr(out["velocity"]),
+                _ptr(out["temperature"]), _ptr(out["salinity"]), _ptr(out["lastPoint"]), _ptr(out["final_pos"]),
+                _ptr(out["final_depth"]), _ptr(out["death_step"]), _stream_handle(stream))
+        if cfg.layer is not None:
+            L.check(lib.mops_run_trajectories_layer_diffuse(mesh.handle, front.handle, hb, C.byref(c), int(cfg.layer),
+                                                            C.byref(dif), *tail), "mops_run_trajectories_layer_diffuse")
+        else:
+            L.check(lib.mops_run_trajectories_diffuse(mesh.handle, front.handle, hb, C.byref(c), C.byref(dif), *tail),
+                    "mops_run_trajectories_diffuse")
+        out["cells"] = cl
+        return out
     if cfg.layer is not None:
         _refuse_attrs_layer(attrs, "run_trajectories")
         st = lib.mops_run_trajectories_layer(mesh.handle, front.handle, None if back is None else back.handle,
@@ -348,6 +377,20 @@ def _refuse_attrs_relocate(cfg: TrajectoryConfig, who: str):
         raise ValueError(f"{who}: attrs are not sampled with method MOPS_RK4_RELOCATE")
 
 
+def _diffusion_of(cfg: TrajectoryConfig, back, attrs, who: str, d_id=None, id_base: int = 0):
+    """The launch's mops_diffusion (None for diffusivity 0: the existing entries) after the refusals of the random
+    walk, all before any launch: a negative or non-finite diffusivity, attribute sampling with it, and a depth-mode
+    streamline with it."""
+    dif = cfg.diffusion(d_id, id_base)
+    if dif is None:
+        return None
+    if attrs is not None:
+        raise ValueError(f"{who}: attrs are not sampled with diffusivity > 0")
+    if cfg.layer is None and back is None:
+        raise ValueError(f"{who}: a depth-mode streamline has no diffusion (use the layer mode, or a pathline)")
+    return dif
+
+
 def _refuse_attrs_layer(attrs, who: str):
     """The layer mode has no attribute channel yet: refused before any launch."""
     if attrs is not None:
@@ -383,16 +426,19 @@ class ParticleSet:
 
     def __init__(self, mesh: DeviceMesh, seeds_xyz, depth: float | np.ndarray, cfg: TrajectoryConfig, device=None,
                  cells=None, use_order: bool = True, record_stride: int | None = None, n_attr: int = 0,
-                 capture_slots: int = 0):
+                 capture_slots: int = 0, id_base: int = 0):
         """``record_stride``: columns of the [K][6][stride] record slab (default n); a multi-GPU
         shard pads it to the largest shard so every rank's slab has one shape
         (distributed.RecordGather).  ``n_attr`` (pathlines, at most 4): also keep a zero-filled
         [K][n_attr][stride] attribute slab, which ``advance(..., attrs=...)`` samples into.
         ``capture_slots`` > 0 (with ``n_attr``): also a capture slab of that many window slots (32 B per
         particle and slot, mops_traj_capture_bytes); ``advance(attrs=)`` then runs one trajectory launch per
-        window instead of one per sample step (mops_traj_advance_captured), with the same bytes."""
+        window instead of one per sample step (mops_traj_advance_captured), with the same bytes.
+        ``id_base``: the global id of this set's first seed -- the random walk (``cfg.diffusivity``) draws particle
+        i's deviates for the id ``id_base + i``, so the parts of a split ensemble continue one numbering."""
         import torch
         self.use_order = use_order
+        self.id_base = int(id_base)
         self.torch = torch
         dev = device or torch.device("cuda", torch.cuda.current_device())
         if isinstance(seeds_xyz, torch.Tensor):  # already resident: no host round trip
@@ -651,6 +697,13 @@ class ParticleSet:
         fields' slices of that layer are made on ``stream`` where they are missing or stale; one made earlier on
         another stream (``DeviceField.layer_velocity``) is waited for on ``stream`` through its event."""
         p = self.particles() if live_count is None else self._sub_particles(0, self.n, live_count)
+        dif = _diffusion_of(self.cfg, back, attrs, "advance", self.ids.data_ptr(), self.id_base)
+        if dif is not None:
+            if self.attr_records is not None:
+                raise ValueError("advance: diffusivity > 0 does not run a particle set with an attribute slab")
+            self._advance_diffuse(front, back, p, 0, int(step_begin), int(step_end), dif, None, stream)
+            self._written = True
+            return
         if self.cfg.layer is not None:  # the layer mode: the mesh and the two snapshots' slices only
             _refuse_attrs_layer(attrs, "advance")
             if self.attr_records is not None:
@@ -676,6 +729,22 @@ class ParticleSet:
                                         C.c_void_p(self.records.data_ptr()), self.rec_stride, _stream_handle(stream))
         L.check(st, "mops_traj_advance")
         self._written = True
+
+    def _advance_diffuse(self, front, back, p, lo: int, step_begin: int, step_end: int, dif, layer_ptrs, stream):
+        """The advance with the random walk of the slots ``p`` describes, which begin at slot ``lo`` (``dif``: the
+        mops_diffusion whose id pointer is already that part's): mops_traj_advance_layer_diffuse in the layer mode
+        (``layer_ptrs``: the slices, made here when None), else mops_traj_advance_diffuse."""
+        lib = L.load()
+        rec = C.c_void_p(self.records.data_ptr() + 8 * lo)
+        if self.cfg.layer is not None:
+            fl, bl = layer_ptrs if layer_ptrs is not None else _layer_ptrs(front, back, self.cfg.layer, stream)
+            L.check(lib.mops_traj_advance_layer_diffuse(self.mesh.handle, fl, bl, C.byref(self._c), C.byref(p),
+                                                        C.byref(dif), step_begin, step_end, rec, self.rec_stride,
+                                                        _stream_handle(stream)), "mops_traj_advance_layer_diffuse")
+        else:
+            L.check(lib.mops_traj_advance_diffuse(self.mesh.handle, front.handle, None if back is None else back.handle,
+                                                  C.byref(self._c), C.byref(p), C.byref(dif), step_begin, step_end, rec,
+                                                  self.rec_stride, _stream_handle(stream)), "mops_traj_advance_diffuse")
 
     def _advance_attrs(self, front, back, p, lo: int, step_begin: int, step_end: int, fa, ba, stream):
         """The sampled advance of the slots ``p`` describes, which begin at slot ``lo``: through the capture
@@ -727,6 +796,9 @@ class ParticleSet:
         its own piece of the capture slab; a compaction moves the attribute slots written so far."""
         torch = self.torch
         fl = bl = None
+        diffuse = _diffusion_of(self.cfg, back, attrs, "advance_pipelined") is not None
+        if diffuse and self.attr_records is not None:
+            raise ValueError("advance_pipelined: diffusivity > 0 does not run a particle set with an attribute slab")
         if self.cfg.layer is not None:
             _refuse_attrs_layer(attrs, "advance_pipelined")
             if self.attr_records is not None:
@@ -782,6 +854,10 @@ class ParticleSet:
                 p = self._sub_particles(lo, hi, self._n_live.get((lo, hi)) if (compact and t > 0) else None)
                 if attrs is not None:
                     self._advance_attrs(front, back, p, lo, tb[t], tb[t + 1], fa, ba, st)
+                elif diffuse:  # (the part's ids: the id pointer offset by its first slot)
+                    dif = self.cfg.diffusion(self.ids.data_ptr() + 4 * lo, self.id_base)
+                    self._advance_diffuse(front, back, p, lo, tb[t], tb[t + 1], dif,
+                                          None if fl is None else (fl, bl), st)
                 elif fl is not None:
                     rc = lib.mops_traj_advance_layer(self.mesh.handle, fl, bl, C.byref(self._c), C.byref(p), tb[t],
                                                      tb[t + 1], C.c_void_p(self.records.data_ptr() + 8 * lo),

@@ -163,7 +163,8 @@ class MOPSPathline:
                              make_attrs=make_attrs if sample_attributes else None)
 
     def run(self, method: str = "rk4", delta_minutes: int = 1, record_every_minutes: int = 6,
-            sample_attributes: bool = False, density=None, layer: int | None = None) -> list:
+            sample_attributes: bool = False, density=None, layer: int | None = None, diffusivity: float = 0.0,
+            seed: int = 0) -> list:
         """All month pairs as one device-resident chain; the per-pair lines concatenated (later pairs
         without their first sample), pyMOPSAPI.py:1396-1531.  Returns list[dict] with lineID, points
         (M, 3), velocity (M, 3), temperature (M,), salinity (M,), lastPoint (3,).
@@ -176,7 +177,12 @@ class MOPSPathline:
         ``density``: an engine.DensityMap or a list of them, filled with every pair's samples on the device
         (PathlineChain.run(density=...)); a map of "temperature" / "salinity" needs ``sample_attributes``.
         ``layer``: advect within that model layer with w = 0 (PathlineChain.run(layer=...); the depth set by
-        ``set_seed`` is still carried, because the records keep their radius); not with ``sample_attributes``."""
+        ``set_seed`` is still carried, because the records keep their radius); not with ``sample_attributes``.
+        ``diffusivity`` (m^2/s), ``seed``: a horizontal random walk on top of the advection
+        (PathlineChain.run(diffusivity=, seed=): reproducible to the bit for a given seed); not with
+        ``sample_attributes``."""
+        if float(diffusivity) > 0.0 and sample_attributes:
+            raise ValueError("sample_attributes is not supported with diffusivity > 0")
         if layer is not None and sample_attributes:
             raise ValueError("sample_attributes is not supported with a layer")
         meth = {"rk4": L.MOPS_RK4, "rk4_relocate": L.MOPS_RK4_RELOCATE}.get(method.lower(), L.MOPS_EULER)
@@ -200,7 +206,8 @@ class MOPSPathline:
                         delta_t=int(delta_minutes) * self._one_min,
                         record_t=int(record_every_minutes) * self._one_min,
                         direction=L.MOPS_FORWARD if self.direction == "forward" else L.MOPS_BACKWARD,
-                        follow_last=self._follow_last, attrs=bool(sample_attributes), density=density, layer=layer)
+                        follow_last=self._follow_last, attrs=bool(sample_attributes), density=density, layer=layer,
+                        diffusivity=diffusivity, seed=seed)
         out = {k: res[k].cpu().numpy() for k in ("points", "velocity", "temperature", "salinity", "lastPoint")}
         self._last_pt = out["lastPoint"].astype(float, copy=True)
         if self._particle_depths is not None:  # :1491-1495
@@ -213,7 +220,7 @@ class MOPSPathline:
 
     def ftle(self, width: int, height: int, lat_range, lon_range, depth: float, method: str = "rk4_relocate",
              delta_minutes: int = 1, record_every_minutes: int = 1440, horizon_days: float | None = None,
-             layer: int | None = None):
+             layer: int | None = None, diffusivity: float = 0.0, seed: int = 0):
         """The FTLE image of the month pairs set by ``set_time``: one particle per pixel of the ``width`` x
         ``height`` window (engine.FlowMapLattice, seeded on the device: the pixel positions of a
         ``MOPS_RunRemapping`` image of the same window), integrated at ``depth`` through every pair as one
@@ -228,7 +235,8 @@ class MOPSPathline:
         reference's "rk4" kills a particle at its first cell crossing (quirk Q1: two thirds of them within a
         day at config 3), so its map is mostly NaN -- use it only to reproduce the reference's lines.  Does not
         touch the state ``run`` keeps between calls (seeds, last points).  ``layer``: the flow map of that model
-        layer (as ``run``), an image that overlays the ``MOPS_RunRemappingFixedLayer`` one."""
+        layer (as ``run``), an image that overlays the ``MOPS_RunRemappingFixedLayer`` one.  ``diffusivity``,
+        ``seed``: as ``run``."""
         from .chain import EverDead
         from .engine import FlowMapLattice
         meth = {"rk4": L.MOPS_RK4, "rk4_relocate": L.MOPS_RK4_RELOCATE}.get(method.lower(), L.MOPS_EULER)
@@ -241,5 +249,6 @@ class MOPSPathline:
                         delta_t=int(delta_minutes) * self._one_min,
                         record_t=int(record_every_minutes) * self._one_min,
                         direction=L.MOPS_FORWARD if self.direction == "forward" else L.MOPS_BACKWARD,
-                        follow_last=True, keep_lines=False, on_pair=ever, layer=layer)
+                        follow_last=True, keep_lines=False, on_pair=ever, layer=layer, diffusivity=diffusivity,
+                        seed=seed)
         return lattice.ftle(res["lastPoint"], ever.death(), horizon=float(horizon_days))

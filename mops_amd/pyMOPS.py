@@ -292,6 +292,11 @@ class TrajectorySettings:
         # carried: the records keep their radius); there relocateStages applies to streamlines too.  A layer
         # outside [0, nVertLevels), or sampleAttributes with it: Error() and an empty list.  -1: the depth mode.
         self.fixedLayer = -1
+        # a horizontal random walk on top of the advection (TrajectoryConfig.diffusivity; 0: none): Kh in m^2/s,
+        # the generator's 64-bit key, and a counter word the caller owns
+        self.diffusivity = 0.0
+        self.randomSeed = 0
+        self.randomEpoch = 0
 
     def hasPerParticleDepths(self) -> bool:
         return len(self.particle_depths) > 0
@@ -555,10 +560,21 @@ def _run(config: TrajectorySettings, sample_points_np, pathline: bool, stage: st
             _error(f"[{stage}] sampleAttributes is not supported with relocateStages")
             return None, seeds, None
         method = _L.MOPS_RK4_RELOCATE
+    kh = float(getattr(config, "diffusivity", 0.0))
+    if not (kh >= 0.0) or not np.isfinite(kh):
+        _error(f"[{stage}] diffusivity must be finite and >= 0")
+        return None, seeds, None
+    if kh > 0.0 and layer < 0 and not pathline:
+        _error(f"[{stage}] diffusivity needs fixedLayer for streamlines")
+        return None, seeds, None
+    if kh > 0.0 and getattr(config, "sampleAttributes", False):
+        _error(f"[{stage}] sampleAttributes is not supported with diffusivity")
+        return None, seeds, None
     cfg = _E.TrajectoryConfig(deltaT=int(config.deltaT), simulationDuration=int(config.simulationDuration),
                               recordT=int(config.recordT), depth=float(np.float32(config.depth)),
                               direction=int(config.directionType), method=method,
-                              layer=layer if layer >= 0 else None)
+                              layer=layer if layer >= 0 else None, diffusivity=kh,
+                              seed=int(getattr(config, "randomSeed", 0)), epoch=int(getattr(config, "randomEpoch", 0)))
     if cfg.n_records <= 0 or cfg.n_steps <= 0:
         _error(f"[{stage}] invalid integration steps")  # seed-only lines (:709-712)
         return "seed_only", seeds, eff
