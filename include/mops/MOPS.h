@@ -114,7 +114,7 @@ struct VisualizationSettings {
     vec2 imageSize;  // x = width, y = height
     vec2 LonRange;
     vec2 LatRange;
-    vec2 DepthRange;
+    vec2 DepthRange{0.0, 0.0};
     double FixedLatitude;
     union {
         double FixedDepth;
@@ -127,6 +127,9 @@ struct VisualizationSettings {
     SaveType saveType = SaveType::kNone;
     double TimeStep;
     LayerRule layerRule = LayerRule::kReference;
+    // MOPS_RunRemappingSection's great-circle path (this engine's extension): waypoints (x = lat, y = lon) in
+    // degrees; its rows span DepthRange, or the grid's reference bottom depths while DepthRange is (0, 0)
+    std::vector<vec2> SectionPath;
     VisualizationSettings() = default;
 };
 
@@ -210,6 +213,7 @@ class MPASOGrid {
         numberVertexOnCell_vec, cellsOnEdge_vec, edgesOnCell_vec;
     std::vector<float> cellWeight_vec;
     std::string mCachedDataDir;
+    std::vector<double> cellRefBottomDepth_vec;  // refBottomDepth: the default rows of MOPS_RunRemappingSection
 };
 
 // SolutionID (MPASOSolution.h:12-16); timestep is value-initialised here
@@ -282,6 +286,19 @@ std::vector<CartesianCoord> MOPS_LatticeSeeds(VisualizationSettings* config);
 // image.
 ImageBuffer<double> MOPS_RunFTLE(const std::vector<TrajectoryLine>& lines, VisualizationSettings* config,
                                  double horizon);
+// Extension ("vertical sections", mops_traj.h): a depth-by-distance image of the active front solution along the
+// great-circle legs through config->SectionPath (mops_section_points, mops_remap_section): imageSize = (columns,
+// rows), rows over config->DepthRange, or over the grid's cellRefBottomDepth_vec front / back while DepthRange
+// is (0, 0).  {image0} or, with double attributes, {image0, image1}: image0 = {zonal, meridional, across} (alpha
+// 1; channels 0 and 1 are the fixed-latitude curtain's pixel, across is positive to the left of the direction of
+// travel), image1 = the first two double attributes in name order, {attr0, attr1 or 0, 0}, blended in depth as
+// the velocity is.  NaN where a pixel fails.  Invalid inputs (null config, no solution, image size below 1,
+// fewer than two waypoints or columns, a bad waypoint or leg, no depth range): Error() and an empty vector.
+std::vector<ImageBuffer<double>> MOPS_RunRemappingSection(VisualizationSettings* config);
+// The volume transport in Sverdrups (1e6 m^3/s) through image0 of MOPS_RunRemappingSection(config): the across
+// channel times ds * dz over the non-NaN pixels, one fixed-order FP64 sum on the host (mops_section_transport).
+// Invalid inputs: Error() and NaN.
+double MOPS_SectionTransport(const ImageBuffer<double>& image, VisualizationSettings* config);
 void MOPS_GenerateSamplePoints(SamplingSettings* config, std::vector<CartesianCoord>& sample_points);
 
 // SaveToPNG (src/Common/ImageBuffer.hpp:91-136) for the double image (the one instantiation the reference

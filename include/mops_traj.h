@@ -644,6 +644,87 @@ mops_status mops_remap_fixed_latitude(const mops_mesh* mesh, const mops_field* f
 mops_status mops_remap_fixed_layer(const mops_mesh* mesh, const mops_field* field, const mops_remap_cfg* cfg,
                                    double* d_image, int32_t* d_cells, void* stream);
 
+/* ---- vertical sections along great-circle paths -------------------------- */
+
+/* The columns of a section through n_way >= 2 waypoints h_waypoints
+ * [n_way][2] = (lat, lon) in degrees, joined by great-circle legs: width >= 2
+ * columns equally spaced in arc length over the whole polyline.  Host only, no
+ * device work; FP64, libm cos / sin / atan2 / sqrt, no contraction, every
+ * expression as written here, left to right (R = 6371010, the remapping's
+ * radius; dot(a, b) = (ax*bx + ay*by) + az*bz; len(q) = sqrt((qx*qx + qy*qy) +
+ * qz*qz)):
+ *   waypoint i:  theta = lat * (M_PI / 180.0), phi = lon * (M_PI / 180.0),
+ *                u_i = (cos(theta)*cos(phi), cos(theta)*sin(phi), sin(theta))
+ *   leg i (a = u_i, b = u_i+1):  d = dot(a, b), q = b - d*a (per component),
+ *                ang_i = atan2(len(q), d), t_i = q / len(q) (per component),
+ *                cum_0 = 0.0, cum_i+1 = cum_i + ang_i, total = cum_(n_way-1)
+ *   column j:    j == 0: leg 0, s = 0.0, phi = 0.0;  j == width-1: the last
+ *                leg, s = total, phi = its ang;  else s = ((double)j * total) /
+ *                (double)(width - 1), the leg is the first whose cum_i+1 is
+ *                not below s (the last leg otherwise), phi = s - cum_leg,
+ *                lowered to ang_leg where it exceeds it
+ *                c = cos(phi), sn = sin(phi), with the leg's a and t:
+ *                p^ = c*a + sn*t          (unit position)
+ *                tau = c*t - sn*a         (direction of travel)
+ *                h_points[j]  = (R * p^x, R * p^y, R * p^z)
+ *                h_normals[j] = p^ x tau = (p^y*tauz - p^z*tauy,
+ *                               p^z*taux - p^x*tauz, p^x*tauy - p^y*taux)
+ *                h_dist[j]    = R * s     (metres from the first waypoint)
+ * The normal is the horizontal unit vector to the LEFT of the direction of
+ * travel: north for a west-to-east section.  h_points, h_normals [width][3],
+ * h_dist [width].  MOPS_ERR_INVALID, nothing written: a null pointer, n_way <
+ * 2, width < 2, a non-finite waypoint, |lat| > 90, a leg of zero length (ang <
+ * 1e-12 rad, where q is rounding noise) or within 1e-9 rad of antipodal (ang >
+ * M_PI - 1e-9: its great circle is not defined). */
+mops_status mops_section_points(int32_t n_way, const double* h_waypoints, int32_t width, double* h_points,
+                                double* h_normals, double* h_dist);
+
+/* A depth-by-distance image along `width` columns.  h_points [width][3] (host;
+ * mops_section_points' or any others) are the column positions, located with
+ * mops_locate_cells; rows are depths, depth_plot = min_depth + ih * i_step,
+ * i_step = height > 1 ? (max_depth - min_depth) / (height - 1) : 0, DEPTH =
+ * -fabs(depth_plot), as in mops_remap_fixed_latitude.
+ *   d_image0 [height][width][4] = {zonal, meridional, across, 1}: channels 0
+ *   and 1 are Kernel::VisualizeFixedLatitude's pixel
+ *   (MPASOVisualizerKernels.cpp:545-651) for the column's position and the
+ *   row's depth, bit for bit: MPASOField::isOnOcean, the Wachspress weights,
+ *   the weighted zTop column with its clamp, the range test and the layer
+ *   search with EPSILON = 1e-6, `up` / `dn` ordered, denom = up - dn (|denom| <
+ *   1e-30 fails), t = (DEPTH - dn) / denom, c = 1.0 - t, the level sums vel_up
+ *   (layer - 1) and vel_dn (layer), f = c*vel_dn + t*vel_up per component,
+ *   convertXYZVelocityToENU(position, f).  across = (fx*nx + fy*ny) + fz*nz
+ *   with the column's h_normals [width][3] row n; 0.0 when h_normals is NULL.
+ *   A failed pixel is {NaN, NaN, NaN, 1}.
+ *   d_image1 (written iff n_attr >= 1) = {attr0, attr1 or 0, 0, 1}: d_attr0 /
+ *   d_attr1 are vertex arrays [V*L] in the caller's vertex order
+ *   (mops_cell_to_vertex_attr); up_a = sum_v w_v * attr[v*L + layer-1], dn_a =
+ *   sum_v w_v * attr[v*L + layer], both in the cell's vertex order from 0.0,
+ *   attr = c*dn_a + t*up_a.  NaN where image 0 is NaN.
+ * d_cells [width] (optional) receives the columns' cells.  n_attr is 0..2.
+ * The per-column work is done once per column, not per pixel; the values do
+ * not depend on that.  Synchronises `stream`.  MOPS_ERR_INVALID before any
+ * device work, nothing written: a null handle or pointer (h_points, d_image0;
+ * d_attr0 and d_image1 with n_attr >= 1; d_attr1 with n_attr == 2), a field of
+ * another mesh, width or height < 1, width * height > 2^31 - 1, n_attr outside
+ * 0..2, a non-finite depth, a mesh of more than 100 levels. */
+mops_status mops_remap_section(const mops_mesh* mesh, const mops_field* field, int32_t width, int32_t height,
+                               double min_depth, double max_depth, const double* h_points, const double* h_normals,
+                               int32_t n_attr, const double* d_attr0, const double* d_attr1, double* d_image0,
+                               double* d_image1, int32_t* d_cells, void* stream);
+
+/* Volume transport through a section image (host only): h_image0
+ * [height][width][4] from mops_remap_section, h_dist [width] from
+ * mops_section_points, the rows' depth range.  ds_j = 0.5 * (dist[min(j+1,
+ * width-1)] - dist[max(j-1, 0)]) (half the distance to each neighbour,
+ * one-sided at the ends); dz = (max_depth - min_depth) / (height - 1), dz_i =
+ * 0.5 * dz in the first and last row, dz elsewhere.  Over the pixels whose
+ * across channel is not NaN, row major, one sequential FP64 sum each from 0.0:
+ * sum += (across * ds_j) * dz_i; area += ds_j * dz_i.  *h_sverdrup = sum /
+ * 1.0e6 (1e6 m^3/s), *h_valid_area = area (m^2).  MOPS_ERR_INVALID, nothing
+ * written: a null pointer, width or height < 2, a non-finite depth. */
+mops_status mops_section_transport(int32_t width, int32_t height, const double* h_image0, const double* h_dist,
+                                   double min_depth, double max_depth, double* h_sverdrup, double* h_valid_area);
+
 /* ---- colour mapping ------------------------------------------------------ */
 
 /* MOPS::SaveToPNG's pixel work (src/Common/ImageBuffer.hpp:91-136) on the

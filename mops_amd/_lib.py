@@ -30,6 +30,7 @@ EXPORTED = (
     "mops_remove_nan_lines", "mops_remove_nan_ragged", "mops_run_trajectories", "mops_build_id",
     "mops_remap_num_images", "mops_remap_tables", "mops_remap_fixed_depth", "mops_remap_fixed_latitude",
     "mops_remap_fixed_layer", "mops_colormap_rgba8", "mops_colormap_image",
+    "mops_section_points", "mops_remap_section", "mops_section_transport",
     "mops_density_bytes", "mops_density_accumulate", "mops_density_image",
     "mops_flowmap_lattice", "mops_ftle_image",
     # include/mops_io.h
@@ -220,6 +221,12 @@ def load(path: str | None = None):
     lib.mops_remap_fixed_depth.argtypes = [P, P, P, I32, P, P, P, P, P, P]; lib.mops_remap_fixed_depth.restype = st
     lib.mops_remap_fixed_latitude.argtypes = [P, P, P, P, P, P]; lib.mops_remap_fixed_latitude.restype = st
     lib.mops_remap_fixed_layer.argtypes = [P, P, P, P, P, P]; lib.mops_remap_fixed_layer.restype = st
+    if hasattr(lib, "mops_remap_section"):  # (older engine builds timed as variants lack the sections)
+        D = C.c_double
+        lib.mops_section_points.argtypes = [I32, P, I32, P, P, P]; lib.mops_section_points.restype = st
+        lib.mops_remap_section.argtypes = [P, P, I32, I32, D, D, P, P, I32, P, P, P, P, P, P]
+        lib.mops_remap_section.restype = st
+        lib.mops_section_transport.argtypes = [I32, I32, P, P, D, D, P, P]; lib.mops_section_transport.restype = st
     lib.mops_colormap_rgba8.argtypes = [P, I32, I32, I32, P, P, P]; lib.mops_colormap_rgba8.restype = st
     lib.mops_colormap_image.argtypes = [P, I32, I32, I32, P, P, P]; lib.mops_colormap_image.restype = st
     lib.mops_density_bytes.argtypes = [I32, I32]; lib.mops_density_bytes.restype = I64

@@ -14,6 +14,11 @@ Mirrors the reference's command-line driver (CLI/main.cpp) option for option:
     --kh KH        extension: a horizontal random walk of eddy diffusivity KH (m^2/s) on top of the streamline
                    (TrajectorySettings.diffusivity); needs --layer
     --seed N       extension: the random walk's seed (TrajectorySettings.randomSeed, default 0)
+    --section "lat,lon;lat,lon[;...]"
+                   extension: per timestep also a vertical section along the great-circle legs through these
+                   waypoints (3601 columns x 201 rows over the reference bottom depths; the YAML carries no image
+                   size), written as ``section_output_<i>_ch<c>.png`` (with ``--vti`` also
+                   ``section_timestep_<t>_tile_0_fixed_depth_0.000000.vti``), and its transport, printed
 
 and its run (CLI/main.cpp:94-262): grid and one solution per timestep from the
 YAML (initGrid_DemoLoading / initSolution_DemoLoading, with temperature and
@@ -57,7 +62,13 @@ def parse_command_line(argv):
     p.add_argument("--layer", type=int, default=None, help="Streamline within this model layer (default: at the depth)")
     p.add_argument("--kh", type=float, default=0.0, help="Horizontal eddy diffusivity in m^2/s (needs --layer)")
     p.add_argument("--seed", type=int, default=0, help="Seed of the random walk")
+    p.add_argument("--section", default=None, help='Vertical section along "lat,lon;lat,lon[;...]"')
     p.add_argument("-h", "--help", action="store_true", help="Print this information")
+    argv = list(argv)
+    for i in range(len(argv) - 1):  # a path that begins with a southern latitude ("-30,...") is a value, not an option
+        if argv[i] == "--section":
+            argv[i:i + 2] = ["--section=" + argv[i + 1]]
+            break
     args = p.parse_args(argv)
     if args.help:
         print(p.format_help())
@@ -77,6 +88,12 @@ def parse_command_line(argv):
     if args.seed < 0 or args.seed >= 2 ** 64:
         print("[ERROR]::--seed must be in [0, 2^64).")
         return None
+    if args.section is not None:
+        try:
+            args.section = parse_section(args.section)
+        except ValueError as e:
+            print(f'[ERROR]::--section must be "lat,lon;lat,lon[;...]" ({e}).')
+            return None
     args.range = _int_list(args.range)
     return args
 
@@ -113,6 +130,61 @@ def run_remapping_stage(M, mio, timestep, depth, vti=False, width=REMAP_WIDTH, h
         written.append(M.SaveVTI(images.cpu().numpy(), cfg, VTI_NAMES, f"timestep_{timestep}_tile_{cfg.tile_index}"))
     print(f"[MOPS_CLI] timestep {timestep}: remapping images written: " + " ".join(written))
     return written
+
+
+SECTION_WIDTH, SECTION_HEIGHT = REMAP_WIDTH, 201   # the remap's columns; rows every 1/200 of the depth range
+SECTION_VTI_NAMES = ("E: Zonal Velocity", "N: Meridional Velocity", "Across-section Velocity",
+                     "Salinity", "Temperature", "None")   # image 1: the attributes in name order
+
+
+def parse_section(text):
+    """``"lat,lon;lat,lon[;...]"`` -> [(lat, lon), ...]; ValueError for anything else."""
+    path = []
+    for part in str(text).split(";"):
+        xy = part.split(",")
+        if len(xy) != 2:
+            raise ValueError(f"bad waypoint {part!r}")
+        path.append((float(xy[0]), float(xy[1])))
+    if len(path) < 2:
+        raise ValueError("a section needs two waypoints")
+    return path
+
+
+def run_section_stage(M, mio, timestep, path, vti=False, width=SECTION_WIDTH, height=SECTION_HEIGHT):
+    """The extension ``--section``: the vertical section of the active timestep along ``path`` over the grid's
+    reference bottom depths, written beside the remapping stage's files in its naming with a ``section_``
+    prefix -- ``section_output_<i>_ch<c>.png`` and, with ``vti``, ``section_timestep_<t>_tile_0_fixed_depth_
+    0.000000.vti`` (x: metres along the path, y: -depth) -- and its transport, printed.  Returns (the files
+    written, the transport in Sverdrups), or ([], None) for invalid inputs."""
+    from . import engine
+    cfg = M.VisualizationSettings()
+    cfg.imageSize = (float(width), float(height))
+    cfg.SectionPath = list(path)
+    cfg.TimeStep = timestep
+    cfg.SaveType = M.SaveType.kVTI if vti else M.SaveType.kPNG
+    images = M._section_device(cfg)
+    if images is None:
+        return [], None
+    written = []
+    for i in range(images.shape[0]):
+        planes = engine.colormap_rgba(images[i], channels=(0, 1, 2)).cpu().numpy()
+        for ch in range(3):
+            name = f"section_output_{i}_ch{ch}.png"
+            mio.write_png_rgba8(name, planes[ch])
+            written.append(name)
+    _, _, dist = engine.section_points(path, int(width))
+    ref = np.asarray(M._app.grid.cellRefBottomDepth_vec, dtype=np.float64).reshape(-1)
+    if vti:
+        cfg.FixedDepth = 0.0
+        cfg.LonRange = (0.0, float(dist[-1]))
+        cfg.LatRange = (-float(ref[-1]), -float(ref[0]))
+        written.append(M.SaveVTI(images.cpu().numpy(), cfg, SECTION_VTI_NAMES,
+                                 f"section_timestep_{timestep}_tile_{cfg.tile_index}"))
+    sv, _ = engine.section_transport(images[0], dist, (float(ref[0]), float(ref[-1])))
+    print(f"[MOPS_CLI] timestep {timestep}: section images written: " + " ".join(written))
+    print(f"[MOPS_CLI] timestep {timestep}: section of {dist[-1] / 1000.0:.3f} km, transport {sv:.6f} Sv "
+          "(positive to the left of the direction of travel)")
+    return written, sv
 
 
 def main(argv=None) -> int:
@@ -152,6 +224,8 @@ def main(argv=None) -> int:
     for t in timesteps:
         M.MOPS_ActiveAttribute(t)
         run_remapping_stage(M, mio, t, args.depth, args.vti)
+        if args.section is not None:
+            run_section_stage(M, mio, t, args.section, args.vti)
 
     # 7. sample points: 31 x 31 lattice request in [35, 45] x [-90, -15] (exclusive upper bounds)
     print("== generate sample points ==")

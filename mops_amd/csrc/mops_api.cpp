@@ -540,6 +540,111 @@ std::vector<ImageBuffer<double>> MOPS_RunRemapping(VisualizationSettings* config
     return img_vec;
 }
 
+namespace {
+
+// (width, height, waypoints [n][2], depth range) of a section; false after Error() for invalid inputs
+bool section_inputs(const VisualizationSettings* config, const char* who, int& W, int& H, std::vector<double>& way,
+                    double& d0, double& d1) {
+    if (config == nullptr || (int)config->imageSize.x <= 0 || (int)config->imageSize.y <= 0) {
+        Error("[MI355X::%s] invalid inputs", who);
+        return false;
+    }
+    W = (int)config->imageSize.x; H = (int)config->imageSize.y;
+    way.clear();
+    for (const vec2& p : config->SectionPath) { way.push_back(p.x); way.push_back(p.y); }
+    d0 = config->DepthRange.x; d1 = config->DepthRange.y;
+    if (d0 == 0.0 && d1 == 0.0) {
+        if (g_app.grid == nullptr || g_app.grid->cellRefBottomDepth_vec.empty()) {
+            Error("[MI355X::%s] refBottomDepth is empty", who);
+            return false;
+        }
+        d0 = g_app.grid->cellRefBottomDepth_vec.front(); d1 = g_app.grid->cellRefBottomDepth_vec.back();
+    }
+    return true;
+}
+
+}  // namespace
+
+std::vector<ImageBuffer<double>> MOPS_RunRemappingSection(VisualizationSettings* config) {
+    ScopedTimer t("GPUKernel::Section", "GPUKernel");
+    int W = 0, H = 0;
+    double d0 = 0.0, d1 = 0.0;
+    std::vector<double> way;
+    if (!section_inputs(config, "Section", W, H, way, d0, d1)) return {};
+    if (g_app.mesh == nullptr || g_app.front == nullptr) {
+        Error("[MI355X::Section] invalid inputs");
+        return {};
+    }
+    std::vector<double> pts(3 * (size_t)W), nrm(3 * (size_t)W), dist((size_t)W);
+    if (mops_section_points((int32_t)(way.size() / 2), way.data(), W, pts.data(), nrm.data(), dist.data()) != MOPS_OK) {
+        Error("[MI355X::Section] %s", mops_last_error());
+        return {};
+    }
+    const auto sit = g_app.sols.find(g_app.front_id);
+    static const std::map<std::string, std::vector<double>> none;
+    const auto& attrs = (sit == g_app.sols.end() || !sit->second) ? none : sit->second->mDoubleAttributes;
+    const int n_attr = attrs.size() > 2 ? 2 : (int)attrs.size();
+    const int n_img = n_attr > 0 ? 2 : 1;
+    const size_t px = (size_t)W * H * 4, VL = (size_t)g_app.grid->mVertexSize * g_app.grid->mVertLevels,
+                 CL = (size_t)g_app.grid->mCellsSize * g_app.grid->mVertLevels;
+    // one allocation: images | the vertex attribute arrays | one cell attribute staging array
+    struct DevBuf {
+        void* p = nullptr;
+        ~DevBuf() { (void)hipFree(p); }
+    } buf;
+    auto hip = [](hipError_t e, const char* what) {
+        if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+    };
+    hip(hipMalloc(&buf.p, (px * n_img + (n_attr ? n_attr * VL + CL : 0)) * sizeof(double)),
+        "MOPS_RunRemappingSection: hipMalloc");
+    double* d_img = static_cast<double*>(buf.p);
+    double* d_attr[2] = {nullptr, nullptr};
+    if (n_attr) {  // the first attributes in std::map name order, as MOPS_RunRemapping's
+        double* d_cell = d_img + px * n_img + (size_t)n_attr * VL;
+        auto it = attrs.begin();
+        for (int k = 0; k < n_attr; ++k, ++it) {
+            if (it->second.size() != CL)
+                throw std::runtime_error("MOPS_RunRemappingSection: attribute " + it->first +
+                                         " is not [nCells*nVertLevels]");
+            d_attr[k] = d_img + px * n_img + (size_t)k * VL;
+            hip(hipMemcpy(d_cell, it->second.data(), CL * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy attribute");
+            check(mops_cell_to_vertex_attr(g_app.mesh, d_cell, d_attr[k], nullptr), "mops_cell_to_vertex_attr");
+            hip(hipDeviceSynchronize(), "mops_cell_to_vertex_attr");
+        }
+    }
+    check(mops_remap_section(g_app.mesh, g_app.front, W, H, d0, d1, pts.data(), nrm.data(), n_attr, d_attr[0], d_attr[1],
+                             d_img, n_attr ? d_img + px : nullptr, nullptr, nullptr),
+          "mops_remap_section");
+    std::vector<ImageBuffer<double>> img_vec;
+    for (int k = 0; k < n_img; ++k) {
+        img_vec.emplace_back(W, H);
+        hip(hipMemcpy(img_vec[(size_t)k].mPixels.data(), d_img + px * k, px * sizeof(double), hipMemcpyDeviceToHost),
+            "hipMemcpy image");
+    }
+    return img_vec;
+}
+
+double MOPS_SectionTransport(const ImageBuffer<double>& image, VisualizationSettings* config) {
+    ScopedTimer t("Section::Transport", "GPUKernel");
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    int W = 0, H = 0;
+    double d0 = 0.0, d1 = 0.0;
+    std::vector<double> way;
+    if (!section_inputs(config, "SectionTransport", W, H, way, d0, d1)) return nan;
+    if (image.mPixels.size() != (size_t)W * H * 4) {
+        Error("[MI355X::SectionTransport] the image is not imageSize");
+        return nan;
+    }
+    std::vector<double> pts(3 * (size_t)W), nrm(3 * (size_t)W), dist((size_t)W);
+    double sv = nan, area = 0.0;
+    if (mops_section_points((int32_t)(way.size() / 2), way.data(), W, pts.data(), nrm.data(), dist.data()) != MOPS_OK ||
+        mops_section_transport(W, H, image.mPixels.data(), dist.data(), d0, d1, &sv, &area) != MOPS_OK) {
+        Error("[MI355X::SectionTransport] %s", mops_last_error());
+        return nan;
+    }
+    return sv;
+}
+
 ImageBuffer<double> MOPS_RunDensity(const std::vector<TrajectoryLine>& lines, VisualizationSettings* config,
                                     const std::string& value) {
     ScopedTimer t("GPUKernel::Density", "GPUKernel");

@@ -6460,7 +6460,8 @@ __device__ __forceinline__ void remap_set_pixel(double* img, int64_t g, double x
 // The cell's vertices, the inside test and the Wachspress weights.  OCEAN false: TBBKernel::IsInMesh
 // (TBBKernel.h:21-54); true: MPASOField::isOnOcean (MPASOField.cpp:36-81), a sign-consistency test on (p - A).
 // Then Interpolator::CalcPolygonWachspress (Interpolation.hpp:137-165).  false = the pixel is NaN.
-template <int MAXV, bool OCEAN>
+// TAG: the section kernel's instantiations are its own (kSectionTag), so the curtain's code does not move.
+template <int MAXV, bool OCEAN, int TAG = 0>
 __device__ __forceinline__ bool remap_stencil(const RemapArgs& a, int cell, double px, double py, double pz,
                                               RemapStencil<MAXV>& s) {
     const int* r = a.cellrec + (int64_t)cell * a.rec_ints;
@@ -6954,6 +6955,277 @@ mops_status mops_remap_fixed_layer(const mops_mesh* mesh, const mops_field* fiel
         a.pts = pts; a.cells = cells;
         launch_remap_layer(maxv, a, layer, s);
     });
+}
+
+}  // extern "C"
+
+// ===========================================================================
+// vertical sections along great-circle paths (mops_section_points, mops_remap_section,
+// mops_section_transport; no reference counterpart beyond the pixel, which is VisualizeFixedLatitude's).
+// A column's position, cell, inside test, Wachspress weights and weighted zTop column do not depend on the
+// row, so one wave owns one column: every lane forms the column's stencil (wave-uniform operands), the lanes
+// share out the L level sums into LDS, lane 0 applies the monotone clamp's recurrence in place, and then each
+// lane takes rows ih = lane, lane + 64, ...: the layer search over the LDS column, two level sums for the
+// velocity and two per attribute.  Every value comes out of the per-pixel form's FP64 expressions in that
+// form's order (remap_stencil / remap_velocity / remap_attribute / remap_enu inline here as they do there; the
+// search is remap_column's with the level sums read back from LDS), so the bytes do not depend on the split.
+// ===========================================================================
+namespace {
+
+constexpr int kSectionBlock = 64;  // one wave per column
+constexpr int kSectionTag = 1;     // remap_stencil's instantiations of the section kernel's own
+
+struct SectionArgs {
+    RemapArgs r;        // W, mesh and field arrays, pts [W][3], cells [W], min_depth, i_step, attr0 / attr1, img0 / img1
+    const double* nrm;  // [W][3] unit normals, or NULL (across = 0.0)
+    int H;
+    int n_attr;         // 0..2; img1 is written iff >= 1
+};
+
+template <int MAXV>
+__global__ void __launch_bounds__(kSectionBlock) remap_section_kernel(SectionArgs sa) {
+    __shared__ double zs[kMaxLevels];  // the column's weighted zTop, clamped in place (L <= kMaxLevels: host check)
+    const RemapArgs& a = sa.r;
+    const int jw = (int)blockIdx.x;
+    const int lane = (int)threadIdx.x;
+    const int L = a.L;
+    const double nan = __builtin_nan("");
+    const int cell = a.cells[jw];
+    const double px = a.pts[3 * (int64_t)jw], py = a.pts[3 * (int64_t)jw + 1], pz = a.pts[3 * (int64_t)jw + 2];
+    RemapStencil<MAXV> s;
+    bool col_ok = cell >= 0 && cell < a.C;                                  // :545
+    if (col_ok) col_ok = remap_stencil<MAXV, true, kSectionTag>(a, cell, px, py, pz, s);  // :551-570
+    if (col_ok) {
+        for (int k = lane; k < L; k += kSectionBlock) {  // :573-580, one level per lane
+            double acc = 0.0;
+#pragma unroll
+            for (int v = 0; v < MAXV; ++v)
+                if (v < s.nv) acc += s.w[v] * a.zt[(int64_t)s.vid[v] * L + k];
+            zs[k] = acc;
+        }
+    }
+    __syncthreads();
+    if (col_ok && lane == 0) {  // :581-587, z[k] = z[k-1] - 1e-9 on the previous clamped value
+        double prev = zs[0];
+        for (int k = 1; k < L; ++k) {
+            double acc = zs[k];
+            if (acc > prev) { acc = prev - 1e-9; zs[k] = acc; }
+            prev = acc;
+        }
+    }
+    __syncthreads();
+    double nx = 0.0, ny = 0.0, nz = 0.0;
+    if (sa.nrm) { nx = sa.nrm[3 * (int64_t)jw]; ny = sa.nrm[3 * (int64_t)jw + 1]; nz = sa.nrm[3 * (int64_t)jw + 2]; }
+    const double EPSILON = 1e-6;
+    for (int ih = lane; ih < sa.H; ih += kSectionBlock) {
+        const int64_t g = (int64_t)ih * a.W + jw;
+        const double depth_plot = a.min_depth + ih * a.i_step;  // :536
+        const double DEPTH = -fabs(depth_plot);
+        bool ok = col_ok;
+        if (ok && (DEPTH > zs[0] + EPSILON || DEPTH < zs[L - 1] - EPSILON)) ok = false;  // :592
+        int layer = -1;
+        double up = 0.0, dn = 0.0;
+        if (ok) {
+            for (int k = 1; k < L; ++k) {  // :597-607
+                const double prev = zs[k - 1], acc = zs[k];
+                double topI = prev, botI = acc;
+                if (topI < botI) { const double t = topI; topI = botI; botI = t; }
+                if (DEPTH <= topI + EPSILON && DEPTH >= botI - EPSILON) { layer = k; up = prev; dn = acc; break; }
+            }
+            if (layer == -1) ok = false;  // :609
+        }
+        double denom = 0.0;
+        if (ok) {
+            if (up < dn) { const double t = up; up = dn; dn = t; }
+            denom = up - dn;
+            if (fabs(denom) < 1e-30) ok = false;  // :621
+        }
+        if (!ok) {
+            remap_set_pixel(a.img0, g, nan, nan, nan);
+            if (sa.n_attr >= 1) remap_set_pixel(a.img1, g, nan, nan, nan);
+            continue;
+        }
+        const double t = (DEPTH - dn) / denom;
+        double ux, uy, uz, dx, dy, dz;
+        remap_velocity<MAXV>(a, s, layer - 1, ux, uy, uz);
+        remap_velocity<MAXV>(a, s, layer, dx, dy, dz);
+        const double c = 1.0 - t;
+        const double fx = c * dx + t * ux, fy = c * dy + t * uy, fz = c * dz + t * uz;
+        double zonal, meridional;
+        remap_enu(px, py, pz, fx, fy, fz, zonal, meridional);
+        const double across = sa.nrm ? (fx * nx + fy * ny) + fz * nz : 0.0;
+        remap_set_pixel(a.img0, g, zonal, meridional, across);
+        if (sa.n_attr >= 1) {
+            const double up0 = remap_attribute<MAXV>(a, s, layer - 1, a.attr0);
+            const double dn0 = remap_attribute<MAXV>(a, s, layer, a.attr0);
+            double v1 = 0.0;
+            if (sa.n_attr >= 2) {
+                const double up1 = remap_attribute<MAXV>(a, s, layer - 1, a.attr1);
+                const double dn1 = remap_attribute<MAXV>(a, s, layer, a.attr1);
+                v1 = c * dn1 + t * up1;
+            }
+            remap_set_pixel(a.img1, g, c * dn0 + t * up0, v1, 0.0);
+        }
+    }
+}
+
+void launch_remap_section(int maxv, const SectionArgs& sa, hipStream_t s) {
+    const unsigned grid = (unsigned)sa.r.W;
+    if (maxv <= 7) remap_section_kernel<7><<<grid, kSectionBlock, 0, s>>>(sa);
+    else if (maxv <= 12) remap_section_kernel<12><<<grid, kSectionBlock, 0, s>>>(sa);
+    else remap_section_kernel<20><<<grid, kSectionBlock, 0, s>>>(sa);
+}
+
+inline bool section_finite(double x) { return std::isfinite(x); }
+
+}  // namespace
+
+extern "C" {
+
+mops_status mops_section_points(int32_t n_way, const double* h_waypoints, int32_t width, double* h_points,
+                                double* h_normals, double* h_dist) {
+    if (!h_waypoints || !h_points || !h_normals || !h_dist)
+        return fail(MOPS_ERR_INVALID, "mops_section_points: null argument");
+    if (n_way < 2 || width < 2) return fail(MOPS_ERR_INVALID, "mops_section_points: need two waypoints and two columns");
+    const int n_leg = n_way - 1;
+    std::vector<double> u(3 * (size_t)n_way), tg(3 * (size_t)n_leg), ang(n_leg), cum((size_t)n_leg + 1);
+    for (int i = 0; i < n_way; ++i) {
+        const double lat = h_waypoints[2 * i], lon = h_waypoints[2 * i + 1];
+        if (!section_finite(lat) || !section_finite(lon) || std::fabs(lat) > 90.0)
+            return fail(MOPS_ERR_INVALID, "mops_section_points: invalid waypoint");
+        const double theta = lat * (M_PI / 180.0), phi = lon * (M_PI / 180.0);
+        const double ct = std::cos(theta), st = std::sin(theta), cp = std::cos(phi), sp = std::sin(phi);
+        u[3 * i] = ct * cp; u[3 * i + 1] = ct * sp; u[3 * i + 2] = st;
+    }
+    cum[0] = 0.0;
+    for (int i = 0; i < n_leg; ++i) {
+        const double* a = &u[3 * i];
+        const double* b = a + 3;
+        const double d = (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
+        const double qx = b[0] - d * a[0], qy = b[1] - d * a[1], qz = b[2] - d * a[2];
+        const double lq = std::sqrt((qx * qx + qy * qy) + qz * qz);
+        ang[i] = std::atan2(lq, d);
+        if (!(ang[i] >= 1e-12)) return fail(MOPS_ERR_INVALID, "mops_section_points: a leg of zero length");
+        if (ang[i] > M_PI - 1e-9)
+            return fail(MOPS_ERR_INVALID, "mops_section_points: a leg between antipodal waypoints");
+        tg[3 * i] = qx / lq; tg[3 * i + 1] = qy / lq; tg[3 * i + 2] = qz / lq;
+        cum[i + 1] = cum[i] + ang[i];
+    }
+    const double total = cum[n_leg];
+    for (int j = 0; j < width; ++j) {
+        int leg;
+        double s, phi;
+        if (j == 0) {
+            leg = 0; s = 0.0; phi = 0.0;
+        } else if (j == width - 1) {
+            leg = n_leg - 1; s = total; phi = ang[leg];
+        } else {
+            s = (static_cast<double>(j) * total) / static_cast<double>(width - 1);
+            leg = 0;
+            while (leg < n_leg - 1 && s > cum[leg + 1]) ++leg;
+            phi = s - cum[leg];
+            if (phi > ang[leg]) phi = ang[leg];
+        }
+        const double* a = &u[3 * leg];
+        const double* t = &tg[3 * leg];
+        const double c = std::cos(phi), sn = std::sin(phi);
+        const double px = c * a[0] + sn * t[0], py = c * a[1] + sn * t[1], pz = c * a[2] + sn * t[2];
+        const double tx = c * t[0] - sn * a[0], ty = c * t[1] - sn * a[1], tz = c * t[2] - sn * a[2];
+        h_points[3 * j] = kRemapRadius * px; h_points[3 * j + 1] = kRemapRadius * py; h_points[3 * j + 2] = kRemapRadius * pz;
+        h_normals[3 * j] = py * tz - pz * ty;
+        h_normals[3 * j + 1] = pz * tx - px * tz;
+        h_normals[3 * j + 2] = px * ty - py * tx;
+        h_dist[j] = kRemapRadius * s;
+    }
+    return MOPS_OK;
+}
+
+mops_status mops_remap_section(const mops_mesh* mesh, const mops_field* field, int32_t width, int32_t height,
+                               double min_depth, double max_depth, const double* h_points, const double* h_normals,
+                               int32_t n_attr, const double* d_attr0, const double* d_attr1, double* d_image0,
+                               double* d_image1, int32_t* d_cells, void* stream) {
+    if (!mesh || !field || !h_points || !d_image0) return fail(MOPS_ERR_INVALID, "mops_remap_section: null argument");
+    if (width < 1 || height < 1 || (int64_t)width * height > 0x7fffffffLL)
+        return fail(MOPS_ERR_INVALID, "mops_remap_section: invalid image size");
+    if (n_attr < 0 || n_attr > 2) return fail(MOPS_ERR_INVALID, "mops_remap_section: n_attr must be 0..2");
+    if ((n_attr >= 1 && (!d_attr0 || !d_image1)) || (n_attr >= 2 && !d_attr1))
+        return fail(MOPS_ERR_INVALID, "mops_remap_section: null attribute array or image");
+    if (!section_finite(min_depth) || !section_finite(max_depth))
+        return fail(MOPS_ERR_INVALID, "mops_remap_section: non-finite depth range");
+    if (field->mesh != mesh) return fail(MOPS_ERR_INVALID, "mops_remap_section: the field belongs to another mesh");
+    if (mesh->L < 1 || mesh->L > kMaxLevels) return fail(MOPS_ERR_INVALID, "mops_remap_section: invalid level count");
+    hipStream_t s = (hipStream_t)stream;
+    const int W = width, H = height;
+    const size_t np3 = 3 * (size_t)W;
+    mops_remap_cfg cfg{};
+    cfg.width = W; cfg.height = H;
+    cfg.layer_rule = MOPS_LAYER_REFERENCE;
+    SectionArgs sa{};
+    sa.r = remap_args(mesh, field, &cfg);
+    sa.r.n = (int64_t)W * H;
+    sa.r.min_depth = min_depth;
+    sa.r.i_step = (H > 1) ? (max_depth - min_depth) / (H - 1) : 0.0;  // :513
+    sa.r.img0 = d_image0;
+    sa.r.img1 = n_attr >= 1 ? d_image1 : nullptr;
+    sa.r.attr0 = n_attr >= 1 ? d_attr0 : nullptr;
+    sa.r.attr1 = n_attr >= 2 ? d_attr1 : nullptr;
+    sa.H = H;
+    sa.n_attr = n_attr;
+    double* scratch = nullptr;  // points [W][3] | normals [W][3]
+    int32_t* own_cells = nullptr;
+    mops_status st = MOPS_OK;
+    do {
+        if ((st = dmalloc(&scratch, (h_normals ? 2 : 1) * np3, nullptr)) != MOPS_OK) break;
+        if (!d_cells) {
+            if ((st = dmalloc(&own_cells, (size_t)W, nullptr)) != MOPS_OK) break;
+            d_cells = own_cells;
+        }
+        hipError_t e = hipMemcpyAsync(scratch, h_points, np3 * sizeof(double), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess && h_normals)
+            e = hipMemcpyAsync(scratch + np3, h_normals, np3 * sizeof(double), hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) { st = fail(MOPS_ERR_HIP, std::string("mops_remap_section: ") + hipGetErrorString(e)); break; }
+        if ((st = mops_locate_cells(mesh, W, scratch, d_cells, s)) != MOPS_OK) break;
+        sa.r.pts = scratch; sa.r.cells = d_cells;
+        sa.nrm = h_normals ? scratch + np3 : nullptr;
+        launch_remap_section(mesh->maxv, sa, s);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { st = fail(MOPS_ERR_HIP, std::string("mops_remap_section: ") + hipGetErrorString(e)); break; }
+    } while (0);
+    if (st != MOPS_OK) (void)hipStreamSynchronize(s);  // the host arrays and the scratch are in flight until then
+    (void)hipFree(scratch);
+    (void)hipFree(own_cells);
+    return st;
+}
+
+mops_status mops_section_transport(int32_t width, int32_t height, const double* h_image0, const double* h_dist,
+                                   double min_depth, double max_depth, double* h_sverdrup, double* h_valid_area) {
+    if (!h_image0 || !h_dist || !h_sverdrup || !h_valid_area)
+        return fail(MOPS_ERR_INVALID, "mops_section_transport: null argument");
+    if (width < 2 || height < 2 || (int64_t)width * height > 0x7fffffffLL)
+        return fail(MOPS_ERR_INVALID, "mops_section_transport: needs at least 2 x 2 pixels");
+    if (!section_finite(min_depth) || !section_finite(max_depth))
+        return fail(MOPS_ERR_INVALID, "mops_section_transport: non-finite depth range");
+    const int W = width, H = height;
+    std::vector<double> ds(W);
+    for (int j = 0; j < W; ++j) {
+        const double lo = h_dist[j > 0 ? j - 1 : 0], hi = h_dist[j < W - 1 ? j + 1 : W - 1];
+        ds[j] = 0.5 * (hi - lo);
+    }
+    const double dz = (max_depth - min_depth) / (H - 1);
+    double sum = 0.0, area = 0.0;
+    for (int i = 0; i < H; ++i) {
+        const double dzi = (i == 0 || i == H - 1) ? 0.5 * dz : dz;
+        for (int j = 0; j < W; ++j) {
+            const double across = h_image0[4 * ((size_t)i * W + j) + 2];
+            if (across != across) continue;
+            sum += (across * ds[j]) * dzi;
+            area += ds[j] * dzi;
+        }
+    }
+    *h_sverdrup = sum / 1.0e6;
+    *h_valid_area = area;
+    return MOPS_OK;
 }
 
 }  // extern "C"

@@ -110,9 +110,12 @@ class DeviceMesh:
 
     @classmethod
     def from_mesh(cls, m, stream=None):
-        return cls(nCells=m.nCells, nVertices=m.nVertices, maxEdges=m.maxEdges, nVertLevels=m.nVertLevels,
-                   nEdgesOnCell=m.nEdgesOnCell, verticesOnCell=m.verticesOnCell, cellsOnCell=m.cellsOnCell,
-                   cellsOnVertex=m.cellsOnVertex, cellCoord=m.cellCoord, vertexCoord=m.vertexCoord, stream=stream)
+        dm = cls(nCells=m.nCells, nVertices=m.nVertices, maxEdges=m.maxEdges, nVertLevels=m.nVertLevels,
+                 nEdgesOnCell=m.nEdgesOnCell, verticesOnCell=m.verticesOnCell, cellsOnCell=m.cellsOnCell,
+                 cellsOnVertex=m.cellsOnVertex, cellCoord=m.cellCoord, vertexCoord=m.vertexCoord, stream=stream)
+        ref = getattr(m, "refBottomDepth", None)  # the default depth range of remap_section
+        dm.refBottomDepth = None if ref is None else np.array(ref, dtype=np.float64).reshape(-1)
+        return dm
 
     def set_edges(self, nEdges, edgesOnCell, cellsOnEdge, edgeCoord, stream=None):
         """Upload the mesh's edges for the RBF velocity reconstruction (mops_mesh_set_edges)."""
@@ -1120,6 +1123,105 @@ def remap_fixed_layer(mesh: DeviceMesh, field: DeviceField, width: int, height: 
                                             None if cells is None else C.c_void_p(cells.data_ptr()),
                                             _stream_handle(h)), "mops_remap_fixed_layer")
     return (image, cells) if return_cells else image
+
+
+def _waypoints(path) -> np.ndarray:
+    try:
+        way = np.ascontiguousarray([(float(lat), float(lon)) for lat, lon in path], dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("path: expected a sequence of (lat, lon) waypoints in degrees") from None
+    return way.reshape(-1, 2)
+
+
+def section_points(path, width: int):
+    """The columns of a section along great-circle legs through the (lat, lon) waypoints of ``path``
+    (mops_section_points; host only): (points [width, 3] on the remapping's sphere, unit normals [width, 3] to
+    the left of the direction of travel, distance [width] in metres from the first waypoint), numpy float64.
+    ValueError where the entry refuses: fewer than two waypoints or columns, a non-finite waypoint, |lat| > 90,
+    a leg of zero length or between antipodal waypoints."""
+    way = _waypoints(path)
+    width = int(width)
+    if not -2**31 <= width < 2**31:
+        raise ValueError(f"invalid column count {width}")
+    n = max(width, 0)
+    pts, nrm, dist = np.empty((n, 3)), np.empty((n, 3)), np.empty(n)
+    st = L.load().mops_section_points(len(way), _ptr(way), width, _ptr(pts), _ptr(nrm), _ptr(dist))
+    if st == L.MOPS_ERR_INVALID:
+        raise ValueError(L.load().mops_last_error().decode(errors="replace"))
+    L.check(st, "mops_section_points")
+    return pts, nrm, dist
+
+
+def section_transport(image, distance, depth_range):
+    """Volume transport through a section (mops_section_transport; host only): ``image`` is image 0 of
+    ``remap_section`` ([height, width, 4], a tensor or an array), ``distance`` its columns' [width] metres,
+    ``depth_range`` its rows' (first, last) depth.  Returns (Sverdrups, valid area in m^2): the across channel
+    times ds * dz over the non-NaN pixels, one fixed-order FP64 sum (include/mops_traj.h)."""
+    if hasattr(image, "detach"):
+        image = image.detach().cpu().numpy()
+    img = np.ascontiguousarray(image, dtype=np.float64)
+    dist = np.ascontiguousarray(distance, dtype=np.float64).reshape(-1)
+    if img.ndim != 3 or img.shape[2] != 4 or img.shape[1] != dist.size:
+        raise ValueError("section_transport: expected an image [height, width, 4] and distance [width]")
+    sv, area = C.c_double(), C.c_double()
+    st = L.load().mops_section_transport(img.shape[1], img.shape[0], _ptr(img), _ptr(dist), float(depth_range[0]),
+                                         float(depth_range[1]), C.byref(sv), C.byref(area))
+    if st == L.MOPS_ERR_INVALID:
+        raise ValueError(L.load().mops_last_error().decode(errors="replace"))
+    L.check(st, "mops_section_transport")
+    return sv.value, area.value
+
+
+def remap_section(mesh: DeviceMesh, field: DeviceField, path, width: int, height: int, depth_range=None,
+                  vertex_attrs=(), return_cells: bool = False, columns=None, stream=None):
+    """A vertical section (mops_remap_section): depth by distance along great-circle legs through the
+    (lat, lon) waypoints of ``path``.  Returns (images, distance): a float64 CUDA tensor [1 + (1 if
+    vertex_attrs else 0), height, width, 4] and the columns' distance [width] in metres (numpy).
+
+    Image 0 is {zonal, meridional, across, 1}: the fixed-latitude curtain's pixel at each column's position and
+    row's depth, and the velocity across the section, positive to the left of the direction of travel.  Image 1
+    (with one or two ``vertex_attrs``, vertex arrays from ``cell_to_vertex_attr``) is {attr0, attr1 or 0, 0, 1},
+    blended in depth as the velocity is.  Failed pixels are NaN.  ``depth_range`` None: the mesh's
+    (refBottomDepth[0], refBottomDepth[-1]) (a ``DeviceMesh.from_mesh`` of a mesh that has them).
+    ``return_cells``: also the int32 [width] cell of each column, as a third value.  ``columns`` = (points
+    [width, 3], normals [width, 3] or None) replaces ``path`` (then None) by explicit column positions; the
+    distance returned is None, and without normals the across channel is 0."""
+    import torch
+    width, height = int(width), int(height)
+    if width <= 0 or height <= 0 or width * height > 0x7fffffff:
+        raise ValueError(f"invalid image size {width} x {height}")
+    if columns is None:
+        pts, nrm, dist = section_points(path, width)
+    else:
+        if path is not None:
+            raise ValueError("remap_section: give either path or columns")
+        pts = np.ascontiguousarray(columns[0], dtype=np.float64)
+        nrm = None if columns[1] is None else np.ascontiguousarray(columns[1], dtype=np.float64)
+        dist = None
+        if pts.shape != (width, 3) or (nrm is not None and nrm.shape != (width, 3)):
+            raise ValueError("remap_section: columns must be [width, 3] arrays")
+    if depth_range is None:
+        ref = getattr(mesh, "refBottomDepth", None)
+        if ref is None or len(ref) == 0:
+            raise ValueError("remap_section: depth_range is needed for a mesh without refBottomDepth")
+        depth_range = (float(ref[0]), float(ref[-1]))
+    d0, d1 = float(depth_range[0]), float(depth_range[1])
+    if not (np.isfinite(d0) and np.isfinite(d1)):
+        raise ValueError("remap_section: non-finite depth range")
+    n_attr = len(vertex_attrs)
+    if n_attr > 2:
+        raise ValueError("remap_section: at most two vertex attributes")
+    a = [_vertex_attr_ptr(mesh, vertex_attrs[k], f"vertex_attrs[{k}]") if k < n_attr else None for k in range(2)]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    images = torch.empty((2 if n_attr else 1, height, width, 4), dtype=torch.float64, device=dev)
+    cells = torch.empty((width,), dtype=torch.int32, device=dev) if return_cells else None
+    h = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    L.check(L.load().mops_remap_section(mesh.handle, field.handle, width, height, d0, d1, _ptr(pts), _ptr(nrm), n_attr,
+                                        a[0], a[1], C.c_void_p(images[0].data_ptr()),
+                                        C.c_void_p(images[1].data_ptr()) if n_attr else None,
+                                        None if cells is None else C.c_void_p(cells.data_ptr()),
+                                        _stream_handle(h)), "mops_remap_section")
+    return (images, dist, cells) if return_cells else (images, dist)
 
 
 def colormap_rgba(image_cuda, channels=(0, 1, 2), return_minmax: bool = False, stream=None):

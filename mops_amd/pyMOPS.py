@@ -27,6 +27,10 @@ and, beyond the pybind module, the image output of the reference's C++ side:
     MOPS_LatticeSeeds(config)                  extension: one seed per pixel of the window, (H*W, 3)
     MOPS_RunFTLE(lines, config, horizon)       extension: the FTLE image of lines seeded on that lattice,
                                                (H, W, 4) float64 {ftle, lambda_max, lambda_min, 1}
+    MOPS_RunRemappingSection(config)           extension: a vertical section along config.SectionPath,
+                                               [ (H, W, 4) float64 ] {zonal, meridional, across, 1} and
+                                               {attr0, attr1, 0, 1}
+    MOPS_SectionTransport(image, config)       extension: its volume transport in Sverdrups
 
 Every trajectory and every image goes through the HIP engine
 (``engine.run_trajectories`` / ``engine.remap_fixed_depth`` /
@@ -320,6 +324,9 @@ class VisualizationSettings:
         self.PositionType = CalcPositionType.kPoint
         self.SaveType = SaveType.kNone
         self.layerRule = "reference"
+        # the waypoints (lat, lon) in degrees of MOPS_RunRemappingSection's great-circle path (this engine's
+        # extension); its rows span DepthRange, or the reference bottom depths while that is (0, 0)
+        self.SectionPath = []
 
     def __setattr__(self, name, value):
         if name in ("imageSize", "LatRange", "LonRange", "DepthRange"):
@@ -676,6 +683,83 @@ def MOPS_RunRemappingFixedLayer(config: VisualizationSettings):
         image = _E.remap_fixed_layer(_app.mesh, _app.front, w, h, config.LatRange, config.LonRange,
                                      float(config.FixedLayer))
         return image.cpu().numpy()
+
+
+def _section_inputs(config, who: str):
+    """(width, height, waypoints, depth range) of a section, or None after Error() for invalid inputs."""
+    w, h = (int(config.imageSize[0]), int(config.imageSize[1])) if config is not None else (0, 0)
+    if config is None or w <= 0 or h <= 0:
+        _error(f"[MI355X::{who}] invalid inputs")
+        return None
+    try:
+        path = [(float(lat), float(lon)) for lat, lon in getattr(config, "SectionPath", [])]
+    except (TypeError, ValueError):
+        _error(f"[MI355X::{who}] SectionPath must be a list of (lat, lon)")
+        return None
+    drange = tuple(config.DepthRange)
+    if drange == (0.0, 0.0):
+        ref = np.zeros(0) if _app.grid is None else \
+            np.asarray(_app.grid.cellRefBottomDepth_vec, dtype=np.float64).reshape(-1)
+        if ref.size == 0:
+            _error(f"[MI355X::{who}] refBottomDepth is empty")
+            return None
+        drange = (float(ref[0]), float(ref[-1]))
+    return w, h, path, drange
+
+
+def MOPS_RunRemappingSection(config: VisualizationSettings):
+    """Extension: a vertical section of the active front solution (engine.remap_section) along the great-circle
+    legs through ``config.SectionPath``, ``imageSize`` = (columns, rows), rows over ``config.DepthRange`` (the
+    reference bottom depths' first and last while it is (0, 0)).  Returns [image0] or, with double attributes,
+    [image0, image1], [H, W, 4] float64 arrays: image0 = {zonal, meridional, across, 1}, image1 = the first two
+    attributes in name order (as MOPS_RunRemapping chooses them), {attr0, attr1 or 0, 0, 1}.  Invalid inputs
+    (no solution, a bad image size or path): Error() and an empty list."""
+    images = _section_device(config)
+    if images is None:
+        return []
+    host = images.cpu().numpy()
+    return [host[k] for k in range(host.shape[0])]
+
+
+def _section_device(config: VisualizationSettings):
+    """MOPS_RunRemappingSection's images where the kernel wrote them: one float64 CUDA tensor [1 or 2, H, W, 4],
+    or None after Error() for invalid inputs (the CLI colours these in place, as _remap_device's)."""
+    with _Timer("GPUKernel::Section", "GPUKernel"):
+        got = _section_inputs(config, "Section")
+        if got is None:
+            return None
+        if _app.mesh is None or _app.front is None:
+            _error("[MI355X::Section] invalid inputs")
+            return None
+        w, h, path, drange = got
+        sol = _app.sols.get(_app.front_id)
+        names = sorted(sol.mDoubleAttributes)[:2] if sol is not None else []
+        try:
+            images, _ = _E.remap_section(_app.mesh, _app.front, path, w, h, drange,
+                                         vertex_attrs=tuple(_vertex_attr(_app.front_id, k) for k in names))
+        except ValueError as e:
+            _error(f"[MI355X::Section] {e}")
+            return None
+        return images
+
+
+def MOPS_SectionTransport(image, config: VisualizationSettings):
+    """Extension: the volume transport in Sverdrups (1e6 m^3/s) through a section image of
+    MOPS_RunRemappingSection(config) -- its across channel times ds * dz over the non-NaN pixels, one fixed-order
+    FP64 sum on the host (engine.section_transport), positive to the left of the direction of travel.  Invalid
+    inputs: Error() and NaN."""
+    with _Timer("Section::Transport", "GPUKernel"):
+        got = _section_inputs(config, "SectionTransport")
+        if got is None:
+            return float("nan")
+        w, h, path, drange = got
+        try:
+            _, _, dist = _E.section_points(path, w)
+            sv, _ = _E.section_transport(image, dist, drange)
+        except ValueError as e:
+            _error(f"[MI355X::SectionTransport] {e}")
+            return float("nan")
+        return sv
 
 
 def MOPS_RunDensity(lines, config: VisualizationSettings, value=None):
