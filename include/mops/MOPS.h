@@ -299,6 +299,13 @@ std::vector<ImageBuffer<double>> MOPS_RunRemappingSection(VisualizationSettings*
 // channel times ds * dz over the non-NaN pixels, one fixed-order FP64 sum on the host (mops_section_transport).
 // Invalid inputs: Error() and NaN.
 double MOPS_SectionTransport(const ImageBuffer<double>& image, VisualizationSettings* config);
+// Extension ("velocity gradient", mops_traj.h): the relative vorticity and the Okubo-Weiss parameter of the
+// active front solution at config->FixedDepth, one image {vorticity, okubo_weiss, 0} (alpha 1).  It is image 1 of
+// the fixed-depth remapping with the two signed vertex arrays (mops_velocity_gradient, then
+// mops_cell_to_vertex_signed; kept per solution id) as its attributes: MOPS_RunRemapping's window, FixedDepth
+// and layerRule, so it overlays the velocity, density and FTLE images.  NaN where a pixel fails.  Invalid inputs
+// (null config, no solution, image size below 1): Error() and an empty vector.
+std::vector<ImageBuffer<double>> MOPS_RunEddyMap(VisualizationSettings* config);
 void MOPS_GenerateSamplePoints(SamplingSettings* config, std::vector<CartesianCoord>& sample_points);
 
 // SaveToPNG (src/Common/ImageBuffer.hpp:91-136) for the double image (the one instantiation the reference

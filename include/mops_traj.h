@@ -725,6 +725,61 @@ mops_status mops_remap_section(const mops_mesh* mesh, const mops_field* field, i
 mops_status mops_section_transport(int32_t width, int32_t height, const double* h_image0, const double* h_dist,
                                    double min_depth, double max_depth, double* h_sverdrup, double* h_valid_area);
 
+/* ---- velocity gradient: vorticity, divergence, strain, Okubo-Weiss --------- */
+
+/* Relative vorticity, horizontal divergence, strain rate and the Okubo-Weiss
+ * parameter of every cell and level, from the field's vertex velocities (no
+ * reference counterpart).  Wachspress interpolation is linear along polygon
+ * edges, so in the planar approximation the Green-Gauss contour sum over a
+ * cell's vertex velocities is the cell mean of the gradient of the field the
+ * engine interpolates everywhere else.
+ *
+ * FP64, no contraction; every expression as written here, left to right; every
+ * sum starts from 0.0 and runs over k = 0 .. n-1 in order; only + - * / and
+ * sqrt.  Cell c: centre (cx, cy, cz) = cellCoord, n = nEdgesOnCell[c],
+ * vertices p_k in verticesOnCell order, U_k the vertex velocity at level l
+ * (cellVertexVelocity, the doubles mops_field_export returns).
+ *   frame (convertXYZVelocityToENU's expressions):
+ *     Rxy = sqrt(cx*cx + cy*cy), Rxyz = sqrt((cx*cx + cy*cy) + cz*cz),
+ *     clon = cx/Rxy, slon = cy/Rxy, slat = cz/Rxyz, clat = Rxy/Rxyz,
+ *     e = (-slon, clon, 0), nn = (-slat*clon, -slat*slon, clat);
+ *     Rxy == 0 (a centre on the axis): e = (1, 0, 0), nn = (0, 1, 0) for
+ *     cz > 0 and (0, -1, 0) otherwise
+ *   plane:  d_k = p_k - c per component, xi_k = (d.x*e.x + d.y*e.y) + d.z*e.z,
+ *     eta_k the same with nn
+ *   geometry (indices modulo n):
+ *     A2 = sum_k (xi_k*eta_k+1 - xi_k+1*eta_k)     (twice the signed area)
+ *     gx_k = eta_k+1 - eta_k-1,  gy_k = xi_k-1 - xi_k+1
+ *   level:  u_k = (U.x*e.x + U.y*e.y) + U.z*e.z, v_k the same with nn,
+ *     ux = (sum_k u_k*gx_k) / A2,  uy = (sum_k u_k*gy_k) / A2,
+ *     vx = (sum_k v_k*gx_k) / A2,  vy = (sum_k v_k*gy_k) / A2
+ *     (the trapezoid Green-Gauss sum with its halves cancelled; the signed A2
+ *     makes the result independent of the polygon's orientation)
+ *   outputs:  vorticity = vx - uy, divergence = ux + vy, sn = ux - vy,
+ *     ss = vx + uy, s2 = sn*sn + ss*ss, strain = sqrt(s2),
+ *     okubo_weiss = s2 - vorticity*vorticity
+ * All four are invariant under a rotation of the frame; the frame is fixed so
+ * that the bits are.  A cell with n < 3, A2 == 0 or a non-finite A2 gets NaN
+ * at every level; nothing else is special-cased (NaN in, NaN out).
+ * Consequences: boundary vertices carry zero velocity (quirk Q10), so coastal
+ * cells see a no-slip wall; levels below the bottom hold whatever the field
+ * holds there.
+ *
+ * Each output is a device array [C*L] in the caller's cell order; any may be
+ * NULL, not all.  Enqueues on `stream` and does not synchronise.
+ * MOPS_ERR_INVALID before any device work: a null mesh or field, all outputs
+ * NULL, a field of another mesh. */
+mops_status mops_velocity_gradient(const mops_mesh* mesh, const mops_field* field, double* d_vorticity,
+                                   double* d_divergence, double* d_strain, double* d_okubo_weiss, void* stream);
+
+/* mops_cell_to_vertex_attr without the clamp: the same barycentric weights of
+ * the three cellsOnVertex centres, b.x*a0 + b.y*a1 + b.z*a2, the caller's
+ * vertex order, 0 at boundary vertices; negative results stay.  For signed
+ * cell arrays such as mops_velocity_gradient's.  Device pointers [C*L] ->
+ * [V*L]; enqueues on `stream`.  MOPS_ERR_INVALID for a null argument or a mesh
+ * without cellsOnVertex. */
+mops_status mops_cell_to_vertex_signed(const mops_mesh* mesh, const double* d_cell, double* d_vertex, void* stream);
+
 /* ---- colour mapping ------------------------------------------------------ */
 
 /* MOPS::SaveToPNG's pixel work (src/Common/ImageBuffer.hpp:91-136) on the

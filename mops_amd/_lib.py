@@ -31,6 +31,7 @@ EXPORTED = (
     "mops_remap_num_images", "mops_remap_tables", "mops_remap_fixed_depth", "mops_remap_fixed_latitude",
     "mops_remap_fixed_layer", "mops_colormap_rgba8", "mops_colormap_image",
     "mops_section_points", "mops_remap_section", "mops_section_transport",
+    "mops_velocity_gradient", "mops_cell_to_vertex_signed",
     "mops_density_bytes", "mops_density_accumulate", "mops_density_image",
     "mops_flowmap_lattice", "mops_ftle_image",
     # include/mops_io.h
@@ -227,6 +228,9 @@ def load(path: str | None = None):
         lib.mops_remap_section.argtypes = [P, P, I32, I32, D, D, P, P, I32, P, P, P, P, P, P]
         lib.mops_remap_section.restype = st
         lib.mops_section_transport.argtypes = [I32, I32, P, P, D, D, P, P]; lib.mops_section_transport.restype = st
+    if hasattr(lib, "mops_velocity_gradient"):  # (older engine builds timed as variants lack the eddy fields)
+        lib.mops_velocity_gradient.argtypes = [P, P, P, P, P, P, P]; lib.mops_velocity_gradient.restype = st
+        lib.mops_cell_to_vertex_signed.argtypes = [P, P, P, P]; lib.mops_cell_to_vertex_signed.restype = st
     lib.mops_colormap_rgba8.argtypes = [P, I32, I32, I32, P, P, P]; lib.mops_colormap_rgba8.restype = st
     lib.mops_colormap_image.argtypes = [P, I32, I32, I32, P, P, P]; lib.mops_colormap_image.restype = st
     lib.mops_density_bytes.argtypes = [I32, I32]; lib.mops_density_bytes.restype = I64

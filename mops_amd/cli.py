@@ -19,6 +19,9 @@ Mirrors the reference's command-line driver (CLI/main.cpp) option for option:
                    waypoints (3601 columns x 201 rows over the reference bottom depths; the YAML carries no image
                    size), written as ``section_output_<i>_ch<c>.png`` (with ``--vti`` also
                    ``section_timestep_<t>_tile_0_fixed_depth_0.000000.vti``), and its transport, printed
+    --eddy         extension: per timestep also the relative vorticity and Okubo-Weiss image at the fixed depth, on
+                   the remap's window and size, written as ``eddy_output_0_ch<c>.png`` (with ``--vti`` also
+                   ``eddy_timestep_<t>_tile_0_fixed_depth_<depth>.vti``)
 
 and its run (CLI/main.cpp:94-262): grid and one solution per timestep from the
 YAML (initGrid_DemoLoading / initSolution_DemoLoading, with temperature and
@@ -63,6 +66,7 @@ def parse_command_line(argv):
     p.add_argument("--kh", type=float, default=0.0, help="Horizontal eddy diffusivity in m^2/s (needs --layer)")
     p.add_argument("--seed", type=int, default=0, help="Seed of the random walk")
     p.add_argument("--section", default=None, help='Vertical section along "lat,lon;lat,lon[;...]"')
+    p.add_argument("--eddy", action="store_true", help="Also write the vorticity / Okubo-Weiss image")
     p.add_argument("-h", "--help", action="store_true", help="Print this information")
     argv = list(argv)
     for i in range(len(argv) - 1):  # a path that begins with a southern latitude ("-30,...") is a value, not an option
@@ -187,6 +191,38 @@ def run_section_stage(M, mio, timestep, path, vti=False, width=SECTION_WIDTH, he
     return written, sv
 
 
+EDDY_VTI_NAMES = ("Relative Vorticity", "Okubo-Weiss", "None")
+
+
+def run_eddy_stage(M, mio, timestep, depth, vti=False, width=REMAP_WIDTH, height=REMAP_HEIGHT):
+    """The extension ``--eddy``: the relative vorticity and the Okubo-Weiss parameter of the active timestep on
+    the remapping stage's window, size and depth (``MOPS_RunEddyMap``), written beside its files in its naming
+    with an ``eddy_`` prefix -- ``eddy_output_0_ch<c>.png`` (channel 2 is the image's zero channel) and, with
+    ``vti``, ``eddy_timestep_<t>_tile_0_fixed_depth_<depth>.vti``.  Returns the files written."""
+    from . import engine
+    cfg = M.VisualizationSettings()
+    cfg.imageSize = (float(width), float(height))
+    cfg.LatRange = (-90.0, 90.0)
+    cfg.LonRange = (-180.0, 180.0)
+    cfg.FixedDepth = depth
+    cfg.TimeStep = timestep
+    cfg.SaveType = M.SaveType.kVTI if vti else M.SaveType.kPNG
+    image = M._eddy_device(cfg)
+    if image is None:
+        return []
+    written = []
+    planes = engine.colormap_rgba(image, channels=(0, 1, 2)).cpu().numpy()
+    for ch in range(3):
+        name = f"eddy_output_0_ch{ch}.png"
+        mio.write_png_rgba8(name, planes[ch])
+        written.append(name)
+    if vti:
+        written.append(M.SaveVTI(image.cpu().numpy()[None], cfg, EDDY_VTI_NAMES,
+                                 f"eddy_timestep_{timestep}_tile_{cfg.tile_index}"))
+    print(f"[MOPS_CLI] timestep {timestep}: eddy images written: " + " ".join(written))
+    return written
+
+
 def main(argv=None) -> int:
     args = parse_command_line(sys.argv[1:] if argv is None else argv)
     if args is None:
@@ -226,6 +262,8 @@ def main(argv=None) -> int:
         run_remapping_stage(M, mio, t, args.depth, args.vti)
         if args.section is not None:
             run_section_stage(M, mio, t, args.section, args.vti)
+        if args.eddy:
+            run_eddy_stage(M, mio, t, args.depth, args.vti)
 
     # 7. sample points: 31 x 31 lattice request in [35, 45] x [-90, -15] (exclusive upper bounds)
     print("== generate sample points ==")

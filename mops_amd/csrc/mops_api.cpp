@@ -65,8 +65,11 @@ struct App {
     mops_field* back = nullptr;
     int front_id = 0;  // the solution behind `front` (its attributes feed the remapping)
     int back_id = 0;   // the solution behind `back` (attribute sampling along pathlines)
+    std::map<int, double*> eddy;  // solID -> vorticity | okubo_weiss vertex arrays [2][V*L] (MOPS_RunEddyMap)
 
     void release() {
+        for (auto& kv : eddy) (void)hipFree(kv.second);
+        eddy.clear();
         for (auto& kv : fields) mops_field_destroy(kv.second);
         fields.clear();
         if (mesh) mops_mesh_destroy(mesh);
@@ -538,6 +541,56 @@ std::vector<ImageBuffer<double>> MOPS_RunRemapping(VisualizationSettings* config
         hip(hipMemcpy(img_vec[(size_t)k].mPixels.data(), d_img + px * k, px * sizeof(double), hipMemcpyDeviceToHost),
             "hipMemcpy image");
     return img_vec;
+}
+
+std::vector<ImageBuffer<double>> MOPS_RunEddyMap(VisualizationSettings* config) {
+    ScopedTimer t("GPUKernel::EddyMap", "GPUKernel");
+    const int W = config ? (int)config->imageSize.x : 0, H = config ? (int)config->imageSize.y : 0;
+    if (config == nullptr || g_app.mesh == nullptr || g_app.front == nullptr || W <= 0 || H <= 0) {
+        Error("[MI355X::EddyMap] invalid inputs");
+        return {};
+    }
+    auto hip = [](hipError_t e, const char* what) {
+        if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+    };
+    const size_t px = (size_t)W * H * 4, VL = (size_t)g_app.grid->mVertexSize * g_app.grid->mVertLevels,
+                 CL = (size_t)g_app.grid->mCellsSize * g_app.grid->mVertLevels;
+    struct DevBuf {
+        void* p = nullptr;
+        ~DevBuf() { (void)hipFree(p); }
+    };
+    auto cached = g_app.eddy.find(g_app.front_id);
+    if (cached == g_app.eddy.end()) {  // the signed vertex arrays of this solution, once
+        DevBuf cell, vert;  // vorticity | okubo_weiss per cell; the same per vertex
+        hip(hipMalloc(&cell.p, 2 * CL * sizeof(double)), "MOPS_RunEddyMap: hipMalloc");
+        hip(hipMalloc(&vert.p, 2 * VL * sizeof(double)), "MOPS_RunEddyMap: hipMalloc");
+        double* d_cell = static_cast<double*>(cell.p);
+        double* d_vert = static_cast<double*>(vert.p);
+        check(mops_velocity_gradient(g_app.mesh, g_app.front, d_cell, nullptr, nullptr, d_cell + CL, nullptr),
+              "mops_velocity_gradient");
+        for (int k = 0; k < 2; ++k)
+            check(mops_cell_to_vertex_signed(g_app.mesh, d_cell + (size_t)k * CL, d_vert + (size_t)k * VL, nullptr),
+                  "mops_cell_to_vertex_signed");
+        hip(hipDeviceSynchronize(), "MOPS_RunEddyMap");
+        cached = g_app.eddy.emplace(g_app.front_id, d_vert).first;
+        vert.p = nullptr;
+    }
+    mops_remap_cfg cfg{};
+    cfg.width = W; cfg.height = H;
+    cfg.min_lat = config->LatRange.x; cfg.max_lat = config->LatRange.y;
+    cfg.min_lon = config->LonRange.x; cfg.max_lon = config->LonRange.y;
+    cfg.fixed_depth = config->FixedDepth;
+    cfg.layer_rule = (int32_t)config->layerRule;
+    DevBuf img;  // image 0 (the velocity) | image 1 {vorticity, okubo_weiss, 0, 1}
+    hip(hipMalloc(&img.p, 2 * px * sizeof(double)), "MOPS_RunEddyMap: hipMalloc");
+    double* d_img = static_cast<double*>(img.p);
+    check(mops_remap_fixed_depth(g_app.mesh, g_app.front, &cfg, 2, cached->second, cached->second + VL, d_img, nullptr,
+                                 nullptr, nullptr),
+          "mops_remap_fixed_depth");
+    std::vector<ImageBuffer<double>> out;
+    out.emplace_back(W, H);
+    hip(hipMemcpy(out[0].mPixels.data(), d_img + px, px * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy image");
+    return out;
 }
 
 namespace {

@@ -7231,6 +7231,176 @@ mops_status mops_section_transport(int32_t width, int32_t height, const double* 
 }  // extern "C"
 
 // ===========================================================================
+// velocity gradient per cell and level (mops_velocity_gradient; no reference counterpart; the operator is
+// stated in include/mops_traj.h): relative vorticity, horizontal divergence, strain rate and the Okubo-Weiss
+// parameter from the Green-Gauss contour sum over a cell's vertex velocities in the cell centre's east / north
+// frame.  The frame, the plane coordinates xi / eta, the contour coefficients gx / gy and the signed area A2
+// depend on the cell alone, the velocities on the level, and a vertex's consecutive levels are contiguous.  So
+// a group of `lpc` lanes of one wave (the smallest power of two >= L, 8 at the least, the whole wave from 33
+// levels on) owns one cell: its lanes share out the cell's vertices to form xi / eta and then gx / gy into LDS,
+// every lane runs the A2 sum over them, and then each lane takes levels l = ll, ll + lpc, ... and runs the
+// sequential k loop of its level with the coefficients read back from LDS (every lane of a group reads the
+// same word: a broadcast).  The k sums keep their stated order -- the lanes split the levels, never k -- so the
+// bytes do not depend on the split.  The vertex velocities are read from the vertex array [V][L][3], a lane's
+// level next to its neighbour's; after the fused derivation, which leaves that array stale, the entry first
+// rebuilds it from the level-pair records (records_to_vertex_kernel, as mops_field_export does: the same
+// doubles).  Reading the level-major records in place measured twice as slow as rebuilding and then reading
+// (DESIGN.md section 3.22).
+// ===========================================================================
+namespace {
+
+constexpr int kEddyBlock = 64;    // one wave per block
+constexpr int kEddyMinLanes = 8;  // lanes per cell at the least: at most 8 cells per wave
+
+struct EddyArgs {
+    int64_t C;
+    int L, rec_ints;
+    int lpc;                   // lanes per cell: a power of two, kEddyMinLanes..kEddyBlock
+    const int* cellrec;
+    const double4* cxyz;
+    const double4* vxyz;
+    const double* vel;         // [V][L][3]
+    double* vort;              // [C][L] each, or NULL
+    double* div;
+    double* strain;
+    double* ow;
+};
+
+template <int MAXV>
+__global__ void __launch_bounds__(kEddyBlock) velocity_gradient_kernel(EddyArgs a) {
+    constexpr int kCells = kEddyBlock / kEddyMinLanes;
+    __shared__ double s_xi[kCells][MAXV], s_eta[kCells][MAXV], s_gx[kCells][MAXV], s_gy[kCells][MAXV];
+    __shared__ int s_vid[kCells][MAXV];
+    const int lane = (int)threadIdx.x;
+    const int lpc = a.lpc;
+    const int sub = lane / lpc;        // the cell of this lane within the wave
+    const int ll = lane - sub * lpc;   // the lane within its cell's group
+    const int64_t c = (int64_t)blockIdx.x * (kEddyBlock / lpc) + sub;
+    const bool live = c < a.C;
+    const int L = a.L;
+    int n = 0;
+    double ex = 1.0, ey = 0.0, ez = 0.0, nx = 0.0, ny = 1.0, nz = 0.0;
+    if (live) {
+        const int* r = a.cellrec + c * a.rec_ints;
+        n = r[0];
+        if (n > MAXV) n = 0;  // (mops_mesh_create admits no such cell)
+        const double4 q = a.cxyz[c];
+        const double cx = q.x, cy = q.y, cz = q.z;
+        const double Rxy = sqrt(cx * cx + cy * cy);
+        if (Rxy == 0.0) {
+            ny = cz > 0.0 ? 1.0 : -1.0;
+        } else {
+            const double Rxyz = sqrt((cx * cx + cy * cy) + cz * cz);
+            const double clon = cx / Rxy, slon = cy / Rxy, slat = cz / Rxyz, clat = Rxy / Rxyz;
+            ex = -slon; ey = clon; ez = 0.0;
+            nx = -slat * clon; ny = -slat * slon; nz = clat;
+        }
+        for (int k = ll; k < n; k += lpc) {
+            const int v = r[1 + k];  // 0 <= v < V for k < n (mops_mesh_create)
+            const double4 p = a.vxyz[v];
+            const double dx = p.x - cx, dy = p.y - cy, dz = p.z - cz;
+            s_vid[sub][k] = v;
+            s_xi[sub][k] = (dx * ex + dy * ey) + dz * ez;
+            s_eta[sub][k] = (dx * nx + dy * ny) + dz * nz;
+        }
+    }
+    __syncthreads();
+    double A2 = 0.0;
+    if (live) {
+        for (int k = ll; k < n; k += lpc) {
+            const int kp = k + 1 == n ? 0 : k + 1, km = k == 0 ? n - 1 : k - 1;
+            s_gx[sub][k] = s_eta[sub][kp] - s_eta[sub][km];
+            s_gy[sub][k] = s_xi[sub][km] - s_xi[sub][kp];
+        }
+        for (int k = 0; k < n; ++k) {
+            const int kp = k + 1 == n ? 0 : k + 1;
+            A2 += s_xi[sub][k] * s_eta[sub][kp] - s_xi[sub][kp] * s_eta[sub][k];
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+    const bool valid = n >= 3 && A2 != 0.0 && isfinite(A2);
+    const double nan = __builtin_nan("");
+    for (int l = ll; l < L; l += lpc) {
+        const int64_t o = c * L + l;
+        double vort = nan, dvg = nan, strain = nan, ow = nan;
+        if (valid) {
+            double sux = 0.0, suy = 0.0, svx = 0.0, svy = 0.0;
+#pragma unroll 4
+            for (int k = 0; k < n; ++k) {
+                const int v = s_vid[sub][k];
+                const double* p = a.vel + ((int64_t)v * L + l) * 3;
+                const double Ux = p[0], Uy = p[1], Uz = p[2];
+                const double u = (Ux * ex + Uy * ey) + Uz * ez;
+                const double w = (Ux * nx + Uy * ny) + Uz * nz;
+                const double gx = s_gx[sub][k], gy = s_gy[sub][k];
+                sux += u * gx;
+                suy += u * gy;
+                svx += w * gx;
+                svy += w * gy;
+            }
+            const double ux = sux / A2, uy = suy / A2, vx = svx / A2, vy = svy / A2;
+            vort = vx - uy;
+            dvg = ux + vy;
+            const double sn = ux - vy, ss = vx + uy;
+            const double s2 = sn * sn + ss * ss;
+            strain = sqrt(s2);
+            ow = s2 - vort * vort;
+        }
+        if (a.vort) a.vort[o] = vort;
+        if (a.div) a.div[o] = dvg;
+        if (a.strain) a.strain[o] = strain;
+        if (a.ow) a.ow[o] = ow;
+    }
+}
+
+void launch_velocity_gradient(int maxv, const EddyArgs& a, hipStream_t s) {
+    const int cells_per_block = kEddyBlock / a.lpc;
+    const unsigned grid = (unsigned)((a.C + cells_per_block - 1) / cells_per_block);
+    if (maxv <= 7) velocity_gradient_kernel<7><<<grid, kEddyBlock, 0, s>>>(a);
+    else if (maxv <= 12) velocity_gradient_kernel<12><<<grid, kEddyBlock, 0, s>>>(a);
+    else velocity_gradient_kernel<20><<<grid, kEddyBlock, 0, s>>>(a);
+}
+
+}  // namespace
+
+extern "C" {
+
+mops_status mops_velocity_gradient(const mops_mesh* mesh, const mops_field* field, double* d_vorticity,
+                                   double* d_divergence, double* d_strain, double* d_okubo_weiss, void* stream) {
+    if (!mesh || !field) return fail(MOPS_ERR_INVALID, "mops_velocity_gradient: null argument");
+    if (!d_vorticity && !d_divergence && !d_strain && !d_okubo_weiss)
+        return fail(MOPS_ERR_INVALID, "mops_velocity_gradient: no output requested");
+    if (field->mesh != mesh) return fail(MOPS_ERR_INVALID, "mops_velocity_gradient: the field belongs to another mesh");
+    hipStream_t s = (hipStream_t)stream;
+    EddyArgs a{};
+    a.C = mesh->C; a.L = mesh->L; a.rec_ints = mesh->rec_ints;
+    a.lpc = kEddyMinLanes;
+    while (a.lpc < kEddyBlock && a.lpc < mesh->L) a.lpc *= 2;
+    a.cellrec = mesh->d_cellrec; a.cxyz = mesh->d_cxyz; a.vxyz = mesh->d_vxyz;
+    if (!field->vtx_full && mesh->L >= 2)  // fused field: rebuild the vertex arrays from the records first
+        records_to_vertex_kernel<<<grid_for(mesh->V * mesh->L), kBlock, 0, s>>>(mesh->V, mesh->L, field->d_pr,
+                                                                                field->d_vel, field->d_w);
+    a.vel = field->d_vel;
+    a.vort = d_vorticity; a.div = d_divergence; a.strain = d_strain; a.ow = d_okubo_weiss;
+    launch_velocity_gradient(mesh->maxv, a, s);
+    HIP_TRY(hipGetLastError());
+    return MOPS_OK;
+}
+
+mops_status mops_cell_to_vertex_signed(const mops_mesh* mesh, const double* d_cell, double* d_vertex, void* stream) {
+    if (!mesh || !d_cell || !d_vertex || !mesh->d_cov)
+        return fail(MOPS_ERR_INVALID, "mops_cell_to_vertex_signed: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    cell_to_vertex_bary_kernel<1><<<grid_for(mesh->V * mesh->L), kBlock, 0, s>>>(
+        mesh->V, mesh->L, mesh->d_cov, mesh->d_bary, d_cell, d_vertex, 0, mesh->d_vold);
+    HIP_TRY(hipGetLastError());
+    return MOPS_OK;
+}
+
+}  // extern "C"
+
+// ===========================================================================
 // colour mapping: MOPS::SaveToPNG's pixel work (src/Common/ImageBuffer.hpp:91-136) for an [H][W][4]
 // float64 device image, channels together.  Two passes over the image: the float range of every channel
 // (per-block partials, then one block reduces them -- min / max do not depend on the order, so no atomics and

@@ -1033,9 +1033,11 @@ def remap_tables(width, height, lat_range=(0.0, 0.0), lon_range=(0.0, 0.0), lati
     return rc, rs, cc, cs
 
 
-def cell_to_vertex_attr(mesh: DeviceMesh, cell_attr):
+def cell_to_vertex_attr(mesh: DeviceMesh, cell_attr, signed: bool = False):
     """CalcCellCenterToVertex for one double attribute (mops_cell_to_vertex_attr): a [C*L] array (numpy or
-    CUDA tensor) -> a [V, L] float64 CUDA tensor in the caller's vertex order, on torch's current stream."""
+    CUDA tensor) -> a [V, L] float64 CUDA tensor in the caller's vertex order, on torch's current stream.
+    Negative results are clamped to 0, the reference's rule for temperature and salinity; ``signed`` keeps them
+    (mops_cell_to_vertex_signed), for signed fields such as ``velocity_gradient``'s."""
     import torch
     dev = torch.device("cuda", torch.cuda.current_device())
     if not isinstance(cell_attr, torch.Tensor):
@@ -1044,9 +1046,47 @@ def cell_to_vertex_attr(mesh: DeviceMesh, cell_attr):
     if src.numel() != mesh.nCells * mesh.nVertLevels:
         raise ValueError("attribute is not [nCells * nVertLevels]")
     out = torch.empty((mesh.nVertices, mesh.nVertLevels), dtype=torch.float64, device=dev)
-    L.check(L.load().mops_cell_to_vertex_attr(mesh.handle, C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()),
-                                              _stream_handle(torch.cuda.current_stream(dev).cuda_stream)),
-            "mops_cell_to_vertex_attr")
+    name = "mops_cell_to_vertex_signed" if signed else "mops_cell_to_vertex_attr"
+    L.check(getattr(L.load(), name)(mesh.handle, C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()),
+                                    _stream_handle(torch.cuda.current_stream(dev).cuda_stream)), name)
+    return out
+
+
+EDDY_FIELDS = ("vorticity", "divergence", "strain", "okubo_weiss")
+
+
+def velocity_gradient(mesh: DeviceMesh, field: DeviceField, which=EDDY_FIELDS, vertex: bool = False, stream=None):
+    """Relative vorticity, horizontal divergence, strain rate and the Okubo-Weiss parameter of every cell and
+    level (mops_velocity_gradient; the operator is stated in include/mops_traj.h): a dict of float64 CUDA
+    tensors [nCells, nVertLevels] for the names in ``which``.  ``vertex``: [nVertices, nVertLevels] instead,
+    through the signed cell-to-vertex interpolation (``cell_to_vertex_attr(signed=True)``), ready to pass as
+    ``vertex_attrs`` / ``attrs=`` to the remapping, section and pathline entries.  A cell the operator refuses
+    (fewer than three vertices, zero area) is NaN at every level.  ValueError for an unknown or missing name."""
+    import torch
+    if isinstance(which, str):
+        which = (which,)
+    names = tuple(which)
+    bad = [w for w in names if w not in EDDY_FIELDS]
+    if bad or not names:
+        raise ValueError(f"which: expected names out of {EDDY_FIELDS}, not {tuple(which)!r}")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    cur = torch.cuda.current_stream(dev).cuda_stream
+    h = stream if stream is not None else cur
+    out = {w: torch.empty((mesh.nCells, mesh.nVertLevels), dtype=torch.float64, device=dev) for w in names}
+    ptr = [C.c_void_p(out[w].data_ptr()) if w in out else None for w in EDDY_FIELDS]
+    L.check(L.load().mops_velocity_gradient(mesh.handle, field.handle, *ptr, _stream_handle(h)),
+            "mops_velocity_gradient")
+    if vertex:
+        lib = L.load()
+        for w in names:
+            vt = torch.empty((mesh.nVertices, mesh.nVertLevels), dtype=torch.float64, device=dev)
+            L.check(lib.mops_cell_to_vertex_signed(mesh.handle, C.c_void_p(out[w].data_ptr()),
+                                                   C.c_void_p(vt.data_ptr()), _stream_handle(h)),
+                    "mops_cell_to_vertex_signed")
+            if stream is not None:  # the cell array is released here while `stream` may still read it
+                out[w].record_stream(stream if isinstance(stream, torch.cuda.Stream)
+                                     else torch.cuda.ExternalStream(int(stream)))
+            out[w] = vt
     return out
 
 

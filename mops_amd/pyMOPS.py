@@ -31,6 +31,8 @@ and, beyond the pybind module, the image output of the reference's C++ side:
                                                [ (H, W, 4) float64 ] {zonal, meridional, across, 1} and
                                                {attr0, attr1, 0, 1}
     MOPS_SectionTransport(image, config)       extension: its volume transport in Sverdrups
+    MOPS_RunEddyMap(config)                    extension: relative vorticity and Okubo-Weiss at FixedDepth,
+                                               (H, W, 4) float64 {vorticity, okubo_weiss, 0, 1}
 
 Every trajectory and every image goes through the HIP engine
 (``engine.run_trajectories`` / ``engine.remap_fixed_depth`` /
@@ -426,6 +428,7 @@ class _App:
         self.front_id = None
         self.back_id = None
         self.vertex_attrs = {}  # solID -> {name: the attribute's vertex array (device)}, built on first use
+        self.eddy_attrs = {}    # solID -> (vorticity, okubo_weiss) vertex arrays (device), built on first use
 
 
 _app = _App()
@@ -669,6 +672,39 @@ def _remap_device(config: VisualizationSettings):
         return _E.remap_fixed_depth(_app.mesh, _app.front, w, h, config.LatRange, config.LonRange,
                                     float(config.FixedDepth), n_attr=n_attr, vertex_attrs=vattrs,
                                     layer_rule=getattr(config, "layerRule", "reference"))
+
+
+def _eddy_vertex_attrs(sol_id):
+    """(vorticity, okubo_weiss) of one solution as signed vertex arrays on the device
+    (``engine.velocity_gradient(vertex=True)``), built once per solution id, like ``_vertex_attr``."""
+    if sol_id not in _app.eddy_attrs:
+        g = _E.velocity_gradient(_app.mesh, _app.fields[sol_id], which=("vorticity", "okubo_weiss"), vertex=True)
+        _app.eddy_attrs[sol_id] = (g["vorticity"], g["okubo_weiss"])
+    return _app.eddy_attrs[sol_id]
+
+
+def MOPS_RunEddyMap(config: VisualizationSettings):
+    """Extension (no reference counterpart): the relative vorticity and the Okubo-Weiss parameter of the active
+    front solution at ``config.FixedDepth`` -> one [H, W, 4] float64 array {vorticity, okubo_weiss, 0, 1}.  It is
+    image 1 of the fixed-depth remapping with the two signed vertex arrays as its attributes: the window,
+    ``FixedDepth`` and ``layerRule`` of ``MOPS_RunRemapping``, so it overlays the velocity, density and FTLE
+    images.  Invalid inputs answer Error() and return []."""
+    image = _eddy_device(config)
+    return [] if image is None else image.cpu().numpy()
+
+
+def _eddy_device(config: VisualizationSettings):
+    """MOPS_RunEddyMap's image where the kernel wrote it: a float64 CUDA tensor [H, W, 4], or None."""
+    with _Timer("GPUKernel::EddyMap", "GPUKernel"):
+        w, h = (int(config.imageSize[0]), int(config.imageSize[1])) if config is not None else (0, 0)
+        if config is None or _app.mesh is None or _app.front is None or w <= 0 or h <= 0:
+            _error("[MI355X::EddyMap] invalid inputs")
+            return None
+        images = _E.remap_fixed_depth(_app.mesh, _app.front, w, h, config.LatRange, config.LonRange,
+                                      float(config.FixedDepth), n_attr=2,
+                                      vertex_attrs=_eddy_vertex_attrs(_app.front_id),
+                                      layer_rule=getattr(config, "layerRule", "reference"))
+        return images[1]
 
 
 def MOPS_RunRemappingFixedLayer(config: VisualizationSettings):
