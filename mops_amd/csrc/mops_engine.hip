@@ -766,12 +766,12 @@ __device__ __forceinline__ int nverts(const Cell<MAXV>& c) { return NV > 0 ? NV 
 // 12 / 20) trajectory kernels.  With a set of its own the sampling kernel leaves every trajectory kernel's
 // device code as it was profiled (tools/asm_compare.py).
 constexpr int kNvSample = -1;
-// ... and NV = kNvReloc likewise for the relocating RK4 kernel (traj_rk4_reloc_kernel); the brackets' TAG is -NV, so
-// the two sets do not meet there either.  dev::walk has a TAG for the same reason: as one more caller of walk<7> that
-// kernel moved 8 SGPR spills in the capture variant of the plain pathline Euler kernel (found by giving it a copy of
-// one shared helper at a time); with walk<MAXV, 1> every existing kernel's resource report is the parent's (DESIGN
-// section 3.15).
-constexpr int kNvReloc = -2;
+// ... and NV = kNvLane likewise for the per-lane kernel (traj_lane_kernel), one set for all its forms; the brackets'
+// TAG is -NV, so the two sets do not meet there either.  dev::walk has a TAG for the same reason: as one more caller
+// of walk<7> the relocating RK4 moved 8 SGPR spills in the capture variant of the plain pathline Euler kernel (found
+// by giving it a copy of one shared helper at a time); with walk<MAXV, 1> every other kernel's resource report is
+// what it was (DESIGN sections 3.15, 3.23).
+constexpr int kNvLane = -2;
 
 template <int MAXV, int NV>
 __device__ __forceinline__ bool weights_finite(const Cell<MAXV>& c, const double* w) {
@@ -1132,7 +1132,7 @@ __device__ unsigned long long g_prof[16];
 __device__ unsigned long long g_prof_ext[8];
 #endif
 
-template <int MAXV, int TAG = 0>  // (TAG: instantiations of the relocating RK4 kernel's own, see kNvReloc)
+template <int MAXV, int TAG = 0>  // (TAG: instantiations of the per-lane kernel's own, see kNvLane)
 __device__ __forceinline__ int walk(Cell<MAXV>& c, int cell, double x, double y, double z,
                                     const int* __restrict__ cellrec, const double4* __restrict__ cxyz, int C) {
     MOPS_CNT(4, 1);
@@ -2266,9 +2266,11 @@ traj_kernel(std::conditional_t<CAP, TrajArgsCap, TrajArgs> a) {
 }
 
 // ===========================================================================
-// pathline RK4 with stage relocation (MOPS_RK4_RELOCATE)
+// the per-lane trajectory kernel, traj_lane_kernel: RK4 with stage relocation (3.15),
+// fixed-layer streamlines and pathlines (3.18) and the random-walk kick (3.20)
 // ===========================================================================
-// The opt-out of quirk Q1.  Kernel::PathLine's RK4 (MPASOVisualizerKernels.cpp:1329-1483) evaluates stages 2-4 in
+// MOPS_RK4_RELOCATE, the opt-out of quirk Q1.
+// Kernel::PathLine's RK4 (MPASOVisualizerKernels.cpp:1329-1483) evaluates stages 2-4 in
 // the step's start cell, so a stage point across a cell edge fails IsInMesh and the particle dies.  Here each of
 // those stages is first located by the step's own one-hop walk (:1361-1381) -- always from the step's cell, over its
 // candidate list (the neighbours in cellsOnCell order, then the cell; strict <, first minimum, ids outside [0, C)
@@ -2286,176 +2288,8 @@ traj_kernel(std::conditional_t<CAP, TrajArgsCap, TrajArgs> a) {
 // every point inside it -- the statement does not care whether its centre was a step or a stage position.  So the
 // step's anchor stays valid, and a stage ball (centred ahead of the particle) serves the next steps' points too.  A
 // walk that leaves c returns before it touches the anchor.
-#ifndef MOPS_NBR_RELOC
-#define MOPS_NBR_RELOC 1  // dev::nbr_stay before a walk (MAXV 7), for the step and the stage points
-#endif
-template <int MAXV>
-struct RelocWaves {
-    static constexpr int value = MAXV <= 7 ? 2 : 1;  // (as the plain RK4 kernels; the resource report: DESIGN 3.15)
-};
-
-namespace dev {
-// The cell of point (x, y, z) by the one-hop walk from `cell`, whose stencil is c: the stay ball, then the
-// neighbour table, then the walk itself -- the first two are exact shortcuts of the third (dev::walk, dev::nbr_stay)
-template <int MAXV>
-__device__ __forceinline__ int relocate(Cell<MAXV>& c, int cell, double x, double y, double z, const TrajArgs& a) {
-    const double ex = x - c.cx, ey = y - c.cy, ez = z - c.cz;
-    if (ex * ex + ey * ey + ez * ez < c.rs2) return cell;
-    if constexpr (MOPS_NBR_TEST && MOPS_NBR_RELOC && MAXV == 7) {
-        if (nbr_stay<MAXV>(c, cell, x, y, z, a.nbr)) return cell;
-    }
-    return walk<MAXV, 1>(c, cell, x, y, z, a.cellrec, a.cxyz, a.C);  // (its own instantiation: see kNvReloc)
-}
-}  // namespace dev
-
-template <int MAXV>
-__global__ void __launch_bounds__(kTrajBlock, (RelocWaves<MAXV>::value)) traj_rk4_reloc_kernel(TrajArgs a) {
-    // the XCD block remap over the live slots (traj_kernel)
-    unsigned nblk = gridDim.x;
-    int64_t n = a.n;
-    if (a.n_live) {
-        const int64_t nl = *a.n_live;
-        n = nl < n ? nl : n;
-        nblk = (unsigned)((n + blockDim.x - 1) / blockDim.x);
-    }
-    const unsigned b = blockIdx.x;
-    if (b >= nblk) return;
-    const unsigned xcd = b % 8u, q = nblk / 8u, r8 = nblk % 8u;
-    const unsigned blk = (xcd < r8 ? xcd * (q + 1u) : r8 * (q + 1u) + (xcd - r8) * q) + b / 8u;
-    const int64_t slot = (int64_t)blk * blockDim.x + threadIdx.x;
-    if (slot >= n) return;
-    const int64_t pid = a.order ? (int64_t)a.order[slot] : slot;
-    const int sb = (int)a.step_begin, step_end = (int)a.step_end;  // (32-bit in here: mops_traj_advance checks)
-    if (a.death[pid] >= 0) {  // the reference's lambda has returned
-        if (a.step_begin == 0) dev::clear_records(a.rec, a.rec_stride, pid, 0, a.K);
-        return;
-    }
-    double x = a.px[pid], y = a.py[pid], z = a.pz[pid];
-    float dep = a.depth[pid];
-    int cell = a.cell[pid];
-    int died = -1;
-    int hint0 = -1, hint1 = -1;  // previous layer per field (speed only)
-    dev::Cell<MAXV> c, cs;
-    c.id = -1; c.nv = 0; c.V = a.V; c.cpolyr = a.cpolyr; c.crank = a.crank; c.C = (uint32_t)a.C;
-    c.nrm = nullptr; c.lds_n = false;
-    cs = c;
-    const int C = a.C;
-    const int rec_period = (int)a.rec_period;
-    uint32_t rec_next = ~(uint32_t)0;
-    int rec_k = 0;
-    bool rec0 = sb > 0;  // record 0's step-0 part (seed position, zero velocity) written
-    if (rec_period > 0) {
-        rec_k = sb / rec_period;
-        rec_next = (uint32_t)(rec_k + 1) * (uint32_t)rec_period - 1u;
-    }
-    constexpr int GR = PairGroup<true, false>::value;
-    const double dt = (double)a.delta_t;
-    for (int step = sb; step < step_end; ++step) {
-        if (step == 0) {  // first_loop (:1351-1360)
-            if (cell < 0 || cell >= C) { died = 0; break; }
-            dev::load_cell<MAXV, false, false>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly);
-            double* r0 = a.rec;
-            r0[0 * a.rec_stride + pid] = x;
-            r0[1 * a.rec_stride + pid] = y;
-            r0[2 * a.rec_stride + pid] = z;
-            r0[3 * a.rec_stride + pid] = 0.0;  // (first_vel below, once step 0 evaluates)
-            r0[4 * a.rec_stride + pid] = 0.0;
-            r0[5 * a.rec_stride + pid] = 0.0;
-            rec0 = true;
-        } else {  // one-hop nearest-centre walk (:1361-1381)
-            if (cell < 0 || cell >= C) { died = step; break; }
-            if (c.id != cell) dev::load_cell<MAXV, false, false>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly);
-            cell = dev::relocate<MAXV>(c, cell, x, y, z, a);
-            if (c.id != cell) {
-                if (cs.id == cell) c = cs;  // (the cell a stage was evaluated in: its anchor is load_cell's)
-                else dev::load_cell<MAXV, false, false>(c, cell, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly);
-            }
-        }
-        const double d = -1.0 * (double)dep;
-        const double r = dev::len3(x, y, z);
-        const double a1 = a.alpha_tab ? a.alpha_tab[step] : (double)step / (double)a.n_steps;  // (the same bits)
-        const double a2 = dev::dclamp(a1 + 0.5 * a.dalpha, 0.0, 1.0), a4 = dev::dclamp(a1 + a.dalpha, 0.0, 1.0);
-        // The four stages, one evaluation in a loop, each in `cs`: stage 1 at the position in the step's cell,
-        // stages 2-3 half a step along the previous stage's velocity, stage 4 a whole step, each in its own cell;
-        // the stage velocities summed as they come in the reference's association ((s1 + 2 s2) + 2 s3) + s4
-        // (:1430-1432), as traj_kernel
-        double hx = 0, hy = 0, hz = 0, wv = 0;
-        double sx = 0, sy = 0, sz = 0, sw = 0;
-        double qx = x, qy = y, qz = z;
-        bool ok = true;
-#pragma unroll 1
-        for (int st = 0; st < 4; ++st) {
-            int sc = cell;
-            if (st > 0) {
-                dev::advect((unsigned)step, x, y, z, sx, sy, sz, st == 3 ? dt : dt * 0.5, qx, qy, qz);
-                sc = dev::relocate<MAXV>(c, cell, qx, qy, qz, a);
-            }
-            if (cs.id != sc) {
-                if (sc == cell) cs = c;
-                else dev::load_cell<MAXV, false, false>(cs, sc, a.cellrec, a.vxyz, a.mono0, a.mono1, a.cxyz, a.cpoly);
-            }
-            const double as = st == 0 ? a1 : (st == 3 ? a4 : a2);
-            // (the general vertex count in instantiations of this kernel's own, dev::kNvReloc: the lanes of a wave
-            // sit in different stage cells, and the trajectory kernels' instantiations stay theirs alone)
-            ok = dev::eval_path<MAXV, GR, dev::kNvReloc>(cs, a.L, a.V, a.f0, a.f1, qx, qy, qz, d, as, hint0, hint1, sx, sy,
-                                                         sz, sw);
-            if (!ok) break;
-            if (st == 0) { hx = sx; hy = sy; hz = sz; wv = sw; }
-            else if (st < 3) { hx = hx + sx * 2.0; hy = hy + sy * 2.0; hz = hz + sz * 2.0; wv = wv + 2.0 * sw; }
-            else { hx = (hx + sx) / 6.0; hy = (hy + sy) / 6.0; hz = (hz + sz) / 6.0; wv = (wv + sw) / 6.0; }
-        }
-        if (!ok) { died = step; break; }
-        double nx, ny, nz;
-        const double tx = x + hx * dt, ty = y + hy * dt, tz = z + hz * dt;
-        const double tl = dev::len3(tx, ty, tz);
-        if (tl > 1e-12) {
-            dev::xdiv_norm3(tx, ty, tz, tl, nx, ny, nz);
-            nx *= r; ny *= r; nz *= r;
-        }
-        else { nx = x; ny = y; nz = z; }
-        // vertical update (:1458-1467)
-        const double old_depth = (double)dep;
-        double nd = old_depth - wv * (double)a.delta_t;
-        nd = dev::dmax(0.0, nd);
-        const double r_new = dev::dmax(1.0, r + wv * (double)a.delta_t);
-        dep = (float)nd;
-        const double nl = dev::len3(nx, ny, nz);
-        if (nl > 1e-12) {
-            dev::xdiv_norm3(nx, ny, nz, nl, nx, ny, nz);
-            nx *= r_new; ny *= r_new; nz *= r_new;
-        }
-        if (step == 0) {  // first_vel
-            a.rec[3 * a.rec_stride + pid] = hx;
-            a.rec[4 * a.rec_stride + pid] = hy;
-            a.rec[5 * a.rec_stride + pid] = hz;
-        }
-        x = nx; y = ny; z = nz;
-        if ((uint32_t)step == rec_next) {  // (step + 1) % rec_period == 0, record k = (step + 1) / rec_period - 1
-            const int k = rec_k;
-            rec_next += (uint32_t)rec_period;
-            ++rec_k;
-            if (k < (int)a.K) {
-                double* rk = a.rec + (int64_t)k * 6 * a.rec_stride;
-                rk[0 * a.rec_stride + pid] = x;
-                rk[1 * a.rec_stride + pid] = y;
-                rk[2 * a.rec_stride + pid] = z;
-                rk[3 * a.rec_stride + pid] = hx;
-                rk[4 * a.rec_stride + pid] = hy;
-                rk[5 * a.rec_stride + pid] = hz;
-            }
-        }
-    }
-    a.px[pid] = x; a.py[pid] = y; a.pz[pid] = z;
-    a.depth[pid] = dep;
-    a.cell[pid] = cell;
-    if (died >= 0) a.death[pid] = died;
-    // slots never sampled: after a death (traj_kernel)
-    if (died >= 0 || step_end == (int)a.n_steps) dev::clear_records(a.rec, a.rec_stride, pid, (rec_k == 0 && rec0) ? 1 : rec_k, a.K);
-}
-
-// ===========================================================================
-// fixed-layer streamlines and pathlines (mops_traj_advance_layer)
-// ===========================================================================
+//
+// Fixed-layer streamlines and pathlines (mops_traj_advance_layer).
 // The StreamLine / PathLine loop of traj_kernel with calc_velocity_at replaced by the layer evaluation: the cell
 // guards, IsInMesh and the Wachspress weights (dev::weights), then TBBKernel::CalcVelocity's sum at ONE layer
 // (TBBKernel.h:128-147) per field, the pathline blend h_b * alpha + h_f * (1 - alpha), failure where |h| < 1e-12,
@@ -2464,17 +2298,41 @@ __global__ void __launch_bounds__(kTrajBlock, (RelocWaves<MAXV>::value)) traj_rk
 // The vertical-update lines stay with w = 0 (the depth is stored back as it came; the position is renormalised
 // to its radius each step, as the reference does).
 //
-// METHOD: MOPS_RK4 (stages in the step's cell, quirk Q1), MOPS_EULER, MOPS_RK4_RELOCATE (each of stages 2-4
-// located by the step's one-hop walk as traj_rk4_reloc_kernel does, for streamlines too).  One lane per particle,
-// no tile, no hand-off, no capture, no LDS normals; untuned.  Instantiations of its own everywhere a shared helper
-// has a tag (dev::kNvLayer, walk<MAXV, 2>), so no existing kernel's code moves.
-struct TrajLayerArgs : TrajArgs {
-    const double4* __restrict__ s0;  // the front snapshot's layer slice [V]
+// Random-walk horizontal diffusion (mops_traj_advance_diffuse, mops_traj_advance_layer_diffuse).
+// ONE kick per live particle per step after the step's position update (vertical update and renormalisation
+// included) and before the record test.  The kick (include/mops_traj.h has the full statement): two uniform
+// deviates R1, R2 in (-1, 1) from Philox4x32-10 keyed by the run's seed with the counter (particle id lo, hi, step,
+// epoch), a displacement d = R1 s e + R2 s n in the local east / north frame with s = sqrt(6 Kh |dt|), and the Euler
+// step's rotation of p about p x d by |d| / max(1e-12, |p|).  No renormalisation after it; a particle that dies at
+// a step gets no kick.
+//
+// MODE: layer streamline, layer pathline, depth-mode pathline.  METHOD: MOPS_RK4 (stages in the step's cell, quirk
+// Q1), MOPS_EULER, MOPS_RK4_RELOCATE (for layer streamlines too).  KICK: with the kick, in all nine forms; without
+// it the six layer forms and the depth-mode relocating RK4 -- the other depth-mode forms are traj_kernel's.
+// Untuned.  Instantiations of its own everywhere a shared helper has a tag (dev::kNvLane, walk<MAXV, 1>).
+struct TrajLaneArgs : TrajArgs {
+    const double4* __restrict__ s0;  // layer modes: the front snapshot's layer slice [V]
     const double4* __restrict__ s1;  // the back snapshot's (a streamline: s0 again, never read)
+    // KICK (zero without it)
+    double kick_s;                  // sqrt(6 Kh |delta_t|), formed once on the host
+    uint32_t key0, key1;            // seed & 0xffffffff, seed >> 32
+    uint32_t epoch;                 // counter word 3
+    int64_t id_base;                // gid = id_base + id[pid]
+    const int32_t* __restrict__ id;  // per particle (NULL: pid)
 };
 
 namespace dev {
-constexpr int kNvLayer = -3;  // the general vertex count in instantiations of the layer kernel's own (see kNvSample)
+// The cell of point (x, y, z) by the one-hop walk from `cell`, whose stencil is c: the stay ball, then the
+// neighbour table, then the walk itself -- the first two are exact shortcuts of the third (dev::walk, dev::nbr_stay)
+template <int MAXV>
+__device__ __forceinline__ int locate(Cell<MAXV>& c, int cell, double x, double y, double z, const TrajArgs& a) {
+    const double ex = x - c.cx, ey = y - c.cy, ez = z - c.cz;
+    if (ex * ex + ey * ey + ez * ez < c.rs2) return cell;
+    if constexpr (MOPS_NBR_TEST && MAXV == 7) {
+        if (nbr_stay<MAXV>(c, cell, x, y, z, a.nbr)) return cell;
+    }
+    return walk<MAXV, 1>(c, cell, x, y, z, a.cellrec, a.cxyz, a.C);  // (its own instantiation: see kNvLane)
+}
 
 // load_cell<MAXV, false, false> without the fields' fast-path words (a layer run has no mops_field)
 template <int MAXV>
@@ -2503,17 +2361,6 @@ __device__ __forceinline__ void load_cell_layer(Cell<MAXV>& c, int cell, const i
     if constexpr (MOPS_CPOLY_RANK && MAXV == 7) c.rank = c.crank[cell];
 }
 
-// dev::relocate with the layer kernel's own walk instantiation
-template <int MAXV>
-__device__ __forceinline__ int locate_layer(Cell<MAXV>& c, int cell, double x, double y, double z, const TrajArgs& a) {
-    const double ex = x - c.cx, ey = y - c.cy, ez = z - c.cz;
-    if (ex * ex + ey * ey + ez * ez < c.rs2) return cell;
-    if constexpr (MOPS_NBR_TEST && MAXV == 7) {
-        if (nbr_stay<MAXV>(c, cell, x, y, z, a.nbr)) return cell;
-    }
-    return walk<MAXV, 2>(c, cell, x, y, z, a.cellrec, a.cxyz, a.C);
-}
-
 // The layer evaluation: false where the reference's guards or IsInMesh fail, or where |h| < 1e-12 (the
 // streamline's own rule, MPASOVisualizerKernels.cpp:838-852; for pathlines this engine's choice, mops_traj.h)
 template <int MAXV, bool PATH>
@@ -2522,7 +2369,7 @@ __device__ __forceinline__ bool eval_layer(const Cell<MAXV>& c, int L, int V, co
                                            double alpha, double& hx, double& hy, double& hz) {
     double w[MAXV];
     bool wfin;
-    if (!weights<MAXV, kNvLayer>(c, L, V, px, py, pz, w, wfin)) return false;
+    if (!weights<MAXV, kNvLane>(c, L, V, px, py, pz, w, wfin)) return false;
     double fx = 0.0, fy = 0.0, fz = 0.0, gx = 0.0, gy = 0.0, gz = 0.0;
 #pragma unroll
     for (int v = 0; v < MAXV; ++v) {
@@ -2546,190 +2393,6 @@ __device__ __forceinline__ bool eval_layer(const Cell<MAXV>& c, int L, int V, co
     }
     return !(len3(hx, hy, hz) < 1e-12);
 }
-}  // namespace dev
-
-template <int MAXV, int METHOD>
-struct LayerWaves {
-    static constexpr int value = MAXV <= 7 ? 2 : 1;  // (untuned; the resource report: DESIGN 3.18)
-};
-
-template <int MAXV, bool PATH, int METHOD>
-__global__ void __launch_bounds__(kTrajBlock, (LayerWaves<MAXV, METHOD>::value)) traj_layer_kernel(TrajLayerArgs a) {
-    constexpr bool EULER = METHOD == MOPS_EULER, RELOC = METHOD == MOPS_RK4_RELOCATE;
-    // the XCD block remap over the live slots (traj_kernel)
-    unsigned nblk = gridDim.x;
-    int64_t n = a.n;
-    if (a.n_live) {
-        const int64_t nl = *a.n_live;
-        n = nl < n ? nl : n;
-        nblk = (unsigned)((n + blockDim.x - 1) / blockDim.x);
-    }
-    const unsigned b = blockIdx.x;
-    if (b >= nblk) return;
-    const unsigned xcd = b % 8u, q = nblk / 8u, r8 = nblk % 8u;
-    const unsigned blk = (xcd < r8 ? xcd * (q + 1u) : r8 * (q + 1u) + (xcd - r8) * q) + b / 8u;
-    const int64_t slot = (int64_t)blk * blockDim.x + threadIdx.x;
-    if (slot >= n) return;
-    const int64_t pid = a.order ? (int64_t)a.order[slot] : slot;
-    const int sb = (int)a.step_begin, step_end = (int)a.step_end;  // (32-bit in here: mops_traj_advance_layer checks)
-    if (a.death[pid] >= 0) {  // the reference's lambda has returned
-        if (a.step_begin == 0) dev::clear_records(a.rec, a.rec_stride, pid, 0, a.K);
-        return;
-    }
-    double x = a.px[pid], y = a.py[pid], z = a.pz[pid];
-    float dep = a.depth[pid];
-    int cell = a.cell[pid];
-    int died = -1;
-    dev::Cell<MAXV> c, cs;  // the step's cell; RELOC: the cell the current stage is evaluated in
-    c.id = -1; c.nv = 0; c.V = a.V; c.cpolyr = a.cpolyr; c.crank = a.crank; c.C = (uint32_t)a.C;
-    c.nrm = nullptr; c.lds_n = false;
-    if constexpr (RELOC) cs = c;
-    const int C = a.C;
-    const int rec_period = (int)a.rec_period;
-    uint32_t rec_next = ~(uint32_t)0;
-    int rec_k = 0;
-    bool rec0 = sb > 0;  // record 0's step-0 part (seed position, zero velocity) written
-    if (rec_period > 0) {
-        rec_k = sb / rec_period;
-        rec_next = (uint32_t)(rec_k + 1) * (uint32_t)rec_period - 1u;
-    }
-    const double dt = (double)a.delta_t;
-    for (int step = sb; step < step_end; ++step) {
-        if (step == 0) {  // first_loop (:892-901, :1351-1360)
-            if (cell < 0 || cell >= C) { died = 0; break; }
-            dev::load_cell_layer<MAXV>(c, cell, a.cellrec, a.cxyz, a.cpoly);
-            double* r0 = a.rec;
-            r0[0 * a.rec_stride + pid] = x;
-            r0[1 * a.rec_stride + pid] = y;
-            r0[2 * a.rec_stride + pid] = z;
-            r0[3 * a.rec_stride + pid] = 0.0;  // (first_vel below, once step 0 evaluates)
-            r0[4 * a.rec_stride + pid] = 0.0;
-            r0[5 * a.rec_stride + pid] = 0.0;
-            rec0 = true;
-        } else {  // one-hop nearest-centre walk (:902-922, :1361-1381)
-            if (cell < 0 || cell >= C) { died = step; break; }
-            if (c.id != cell) dev::load_cell_layer<MAXV>(c, cell, a.cellrec, a.cxyz, a.cpoly);
-            cell = dev::locate_layer<MAXV>(c, cell, x, y, z, a);
-            if (c.id != cell) {
-                bool have = false;
-                if constexpr (RELOC) {
-                    if (cs.id == cell) { c = cs; have = true; }  // (the cell a stage was evaluated in)
-                }
-                if (!have) dev::load_cell_layer<MAXV>(c, cell, a.cellrec, a.cxyz, a.cpoly);
-            }
-        }
-        const double r = dev::len3(x, y, z);
-        double a1 = 0.0;
-        if constexpr (PATH) a1 = a.alpha_tab ? a.alpha_tab[step] : (double)step / (double)a.n_steps;  // (the same bits)
-        double hx = 0, hy = 0, hz = 0;
-        double nx, ny, nz;
-        if constexpr (EULER) {
-            if (!dev::eval_layer<MAXV, PATH>(c, a.L, a.V, a.s0, a.s1, x, y, z, a1, hx, hy, hz)) { died = step; break; }
-            const double ax = y * hz - z * hy, ay = z * hx - x * hz, az = x * hy - y * hx;
-            const double speed = dev::len3(hx, hy, hz);
-            const double th = (speed * a.delta_t) / dev::dmax(1e-12, r);
-            dev::rotate((unsigned)step, x, y, z, ax, ay, az, th, nx, ny, nz);
-        } else {
-            const double a2 = PATH ? dev::dclamp(a1 + 0.5 * a.dalpha, 0.0, 1.0) : 0.0;
-            const double a4 = PATH ? dev::dclamp(a1 + a.dalpha, 0.0, 1.0) : 0.0;
-            // the four stages, one evaluation in a loop (traj_rk4_reloc_kernel), summed in the reference's
-            // association ((s1 + 2 s2) + 2 s3) + s4
-            double sx = 0, sy = 0, sz = 0;
-            double qx = x, qy = y, qz = z;
-            bool ok = true;
-#pragma unroll 1
-            for (int st = 0; st < 4; ++st) {
-                if (st > 0) dev::advect((unsigned)step, x, y, z, sx, sy, sz, st == 3 ? dt : dt * 0.5, qx, qy, qz);
-                const double as = st == 0 ? a1 : (st == 3 ? a4 : a2);
-                if constexpr (RELOC) {
-                    int sc = cell;
-                    if (st > 0) sc = dev::locate_layer<MAXV>(c, cell, qx, qy, qz, a);
-                    if (cs.id != sc) {
-                        if (sc == cell) cs = c;
-                        else dev::load_cell_layer<MAXV>(cs, sc, a.cellrec, a.cxyz, a.cpoly);
-                    }
-                    ok = dev::eval_layer<MAXV, PATH>(cs, a.L, a.V, a.s0, a.s1, qx, qy, qz, as, sx, sy, sz);
-                } else {
-                    ok = dev::eval_layer<MAXV, PATH>(c, a.L, a.V, a.s0, a.s1, qx, qy, qz, as, sx, sy, sz);
-                }
-                if (!ok) break;
-                if (st == 0) { hx = sx; hy = sy; hz = sz; }
-                else if (st < 3) { hx = hx + sx * 2.0; hy = hy + sy * 2.0; hz = hz + sz * 2.0; }
-                else { hx = (hx + sx) / 6.0; hy = (hy + sy) / 6.0; hz = (hz + sz) / 6.0; }
-            }
-            if (!ok) { died = step; break; }
-            const double tx = x + hx * dt, ty = y + hy * dt, tz = z + hz * dt;
-            const double tl = dev::len3(tx, ty, tz);
-            if (tl > 1e-12) {
-                dev::xdiv_norm3(tx, ty, tz, tl, nx, ny, nz);
-                nx *= r; ny *= r; nz *= r;
-            }
-            else { nx = x; ny = y; nz = z; }
-        }
-        // vertical update (:977-986, :1458-1467) with w = 0: the depth keeps its value (max(0, (double)dep - 0 * dt)
-        // is dep for every dep >= 0 and 0 below, as the reference gives), the radius is max(1, r + 0 * dt)
-        const double wv = 0.0;
-        double nd = (double)dep - wv * (double)a.delta_t;
-        nd = dev::dmax(0.0, nd);
-        const double r_new = dev::dmax(1.0, r + wv * (double)a.delta_t);
-        dep = (float)nd;
-        const double nl = dev::len3(nx, ny, nz);
-        if (nl > 1e-12) {
-            dev::xdiv_norm3(nx, ny, nz, nl, nx, ny, nz);
-            nx *= r_new; ny *= r_new; nz *= r_new;
-        }
-        if (step == 0) {  // first_vel
-            a.rec[3 * a.rec_stride + pid] = hx;
-            a.rec[4 * a.rec_stride + pid] = hy;
-            a.rec[5 * a.rec_stride + pid] = hz;
-        }
-        x = nx; y = ny; z = nz;
-        if ((uint32_t)step == rec_next) {  // (step + 1) % rec_period == 0, record k = (step + 1) / rec_period - 1
-            const int k = rec_k;
-            rec_next += (uint32_t)rec_period;
-            ++rec_k;
-            if (k < (int)a.K) {
-                double* rk = a.rec + (int64_t)k * 6 * a.rec_stride;
-                rk[0 * a.rec_stride + pid] = x;
-                rk[1 * a.rec_stride + pid] = y;
-                rk[2 * a.rec_stride + pid] = z;
-                rk[3 * a.rec_stride + pid] = hx;
-                rk[4 * a.rec_stride + pid] = hy;
-                rk[5 * a.rec_stride + pid] = hz;
-            }
-        }
-    }
-    a.px[pid] = x; a.py[pid] = y; a.pz[pid] = z;
-    a.depth[pid] = dep;
-    a.cell[pid] = cell;
-    if (died >= 0) a.death[pid] = died;
-    // slots never sampled: after a death, and past the last record step (traj_kernel)
-    if (died >= 0 || step_end == (int)a.n_steps) dev::clear_records(a.rec, a.rec_stride, pid, (rec_k == 0 && rec0) ? 1 : rec_k, a.K);
-}
-
-// ===========================================================================
-// random-walk horizontal diffusion (mops_traj_advance_diffuse, mops_traj_advance_layer_diffuse; DESIGN.md
-// section 3.20)
-// ===========================================================================
-// The per-lane step loops above -- the layer step (traj_layer_kernel) and the depth-mode pathline step (the Euler
-// rotation, RK4 in the step's cell, RK4 with relocated stages as traj_rk4_reloc_kernel) -- with ONE kick per live
-// particle per step after the step's position update (vertical update and renormalisation included) and before the
-// record test.  The kick (include/mops_traj.h has the full statement): two uniform deviates R1, R2 in (-1, 1) from
-// Philox4x32-10 keyed by the run's seed with the counter (particle id lo, hi, step, epoch), a displacement
-// d = R1 s e + R2 s n in the local east / north frame with s = sqrt(6 Kh |dt|), and the Euler step's rotation of p
-// about p x d by |d| / max(1e-12, |p|).  No renormalisation after it; a particle that dies at a step gets no kick.
-// One lane per particle, no tile, no hand-off, no capture, no LDS normals; instantiations of its own wherever a
-// shared helper has a tag (dev::kNvDiff, walk<MAXV, 3>), so no existing kernel's code moves.
-struct TrajDiffuseArgs : TrajLayerArgs {
-    double kick_s;                  // sqrt(6 Kh |delta_t|), formed once on the host
-    uint32_t key0, key1;            // seed & 0xffffffff, seed >> 32
-    uint32_t epoch;                 // counter word 3
-    int64_t id_base;                // gid = id_base + id[pid]
-    const int32_t* __restrict__ id;  // per particle (NULL: pid)
-};
-
-namespace dev {
-constexpr int kNvDiff = -4;  // the general vertex count in instantiations of the diffusion kernel's own (see kNvSample)
 
 __device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0,
                                              uint32_t k1) {
@@ -2771,62 +2434,19 @@ __device__ __forceinline__ void kick(unsigned salt, double s, double R1, double 
     rotate(salt, x, y, z, ax, ay, az, th, ox, oy, oz);
     x = ox; y = oy; z = oz;
 }
-
-// dev::relocate / dev::locate_layer with the diffusion kernel's own walk instantiation
-template <int MAXV>
-__device__ __forceinline__ int locate_diffuse(Cell<MAXV>& c, int cell, double x, double y, double z, const TrajArgs& a) {
-    const double ex = x - c.cx, ey = y - c.cy, ez = z - c.cz;
-    if (ex * ex + ey * ey + ez * ez < c.rs2) return cell;
-    if constexpr (MOPS_NBR_TEST && MAXV == 7) {
-        if (nbr_stay<MAXV>(c, cell, x, y, z, a.nbr)) return cell;
-    }
-    return walk<MAXV, 3>(c, cell, x, y, z, a.cellrec, a.cxyz, a.C);
-}
-
-// eval_layer with the diffusion kernel's own weights instantiation
-template <int MAXV, bool PATH>
-__device__ __forceinline__ bool eval_layer_diffuse(const Cell<MAXV>& c, int L, int V, const double4* __restrict__ s0,
-                                                   const double4* __restrict__ s1, double px, double py, double pz,
-                                                   double alpha, double& hx, double& hy, double& hz) {
-    double w[MAXV];
-    bool wfin;
-    if (!weights<MAXV, kNvDiff>(c, L, V, px, py, pz, w, wfin)) return false;
-    double fx = 0.0, fy = 0.0, fz = 0.0, gx = 0.0, gy = 0.0, gz = 0.0;
-#pragma unroll
-    for (int v = 0; v < MAXV; ++v) {
-        if (v < c.nv) {
-            const double2* q = reinterpret_cast<const double2*>(s0 + c.vid[v]);
-            const double2 a = q[0], b = q[1];
-            fx += w[v] * a.x; fy += w[v] * a.y; fz += w[v] * b.x;
-            if constexpr (PATH) {
-                const double2* qb = reinterpret_cast<const double2*>(s1 + c.vid[v]);
-                const double2 e = qb[0], f = qb[1];
-                gx += w[v] * e.x; gy += w[v] * e.y; gz += w[v] * f.x;
-            }
-        }
-    }
-    if constexpr (PATH) {
-        hx = gx * alpha + fx * (1.0 - alpha);
-        hy = gy * alpha + fy * (1.0 - alpha);
-        hz = gz * alpha + fz * (1.0 - alpha);
-    } else {
-        hx = fx; hy = fy; hz = fz;
-    }
-    return !(len3(hx, hy, hz) < 1e-12);
-}
 }  // namespace dev
 
-constexpr int kDiffLayerStream = 0, kDiffLayerPath = 1, kDiffDepthPath = 2;  // traj_diffuse_kernel's MODE
+constexpr int kLaneLayerStream = 0, kLaneLayerPath = 1, kLaneDepthPath = 2;  // traj_lane_kernel's MODE
 
 template <int MAXV>
-struct DiffuseWaves {
-    static constexpr int value = MAXV <= 7 ? 2 : 1;  // (as the layer and relocating kernels; the resource report: DESIGN 3.20)
+struct LaneWaves {
+    static constexpr int value = MAXV <= 7 ? 2 : 1;  // (as the plain RK4 kernels; the resource report: DESIGN 3.23)
 };
 
-template <int MAXV, int MODE, int METHOD>
-__global__ void __launch_bounds__(kTrajBlock, (DiffuseWaves<MAXV>::value)) traj_diffuse_kernel(TrajDiffuseArgs a) {
+template <int MAXV, int MODE, int METHOD, bool KICK>
+__global__ void __launch_bounds__(kTrajBlock, (LaneWaves<MAXV>::value)) traj_lane_kernel(TrajLaneArgs a) {
     constexpr bool EULER = METHOD == MOPS_EULER, RELOC = METHOD == MOPS_RK4_RELOCATE;
-    constexpr bool DEPTH = MODE == kDiffDepthPath, PATH = MODE != kDiffLayerStream;
+    constexpr bool DEPTH = MODE == kLaneDepthPath, PATH = MODE != kLaneLayerStream;
     // the XCD block remap over the live slots (traj_kernel)
     unsigned nblk = gridDim.x;
     int64_t n = a.n;
@@ -2847,7 +2467,8 @@ __global__ void __launch_bounds__(kTrajBlock, (DiffuseWaves<MAXV>::value)) traj_
         if (a.step_begin == 0) dev::clear_records(a.rec, a.rec_stride, pid, 0, a.K);
         return;
     }
-    const uint64_t gid = (uint64_t)(a.id_base + (a.id ? (int64_t)a.id[pid] : pid));  // the only per-lane counter words
+    // KICK: the only per-lane counter words
+    const uint64_t gid = KICK ? (uint64_t)(a.id_base + (a.id ? (int64_t)a.id[pid] : pid)) : 0;
     const uint32_t gid_lo = (uint32_t)gid, gid_hi = (uint32_t)(gid >> 32);
     double x = a.px[pid], y = a.py[pid], z = a.pz[pid];
     float dep = a.depth[pid];
@@ -2888,7 +2509,7 @@ __global__ void __launch_bounds__(kTrajBlock, (DiffuseWaves<MAXV>::value)) traj_
         } else {  // one-hop nearest-centre walk
             if (cell < 0 || cell >= C) { died = step; break; }
             if (c.id != cell) load(c, cell);
-            cell = dev::locate_diffuse<MAXV>(c, cell, x, y, z, a);
+            cell = dev::locate<MAXV>(c, cell, x, y, z, a);
             if (c.id != cell) {
                 bool have = false;
                 if constexpr (RELOC) {
@@ -2905,11 +2526,11 @@ __global__ void __launch_bounds__(kTrajBlock, (DiffuseWaves<MAXV>::value)) traj_
         auto eval = [&](const dev::Cell<MAXV>& t, double ex, double ey, double ez, double al, double& ox, double& oy,
                         double& oz, double& ow) -> bool {
             if constexpr (DEPTH) {
-                return dev::eval_path<MAXV, GR, dev::kNvDiff>(t, a.L, a.V, a.f0, a.f1, ex, ey, ez, d, al, hint0, hint1, ox,
+                return dev::eval_path<MAXV, GR, dev::kNvLane>(t, a.L, a.V, a.f0, a.f1, ex, ey, ez, d, al, hint0, hint1, ox,
                                                               oy, oz, ow);
             } else {
                 ow = 0.0;
-                return dev::eval_layer_diffuse<MAXV, PATH>(t, a.L, a.V, a.s0, a.s1, ex, ey, ez, al, ox, oy, oz);
+                return dev::eval_layer<MAXV, PATH>(t, a.L, a.V, a.s0, a.s1, ex, ey, ez, al, ox, oy, oz);
             }
         };
         double hx = 0, hy = 0, hz = 0, wv = 0;
@@ -2923,7 +2544,7 @@ __global__ void __launch_bounds__(kTrajBlock, (DiffuseWaves<MAXV>::value)) traj_
         } else {
             const double a2 = PATH ? dev::dclamp(a1 + 0.5 * a.dalpha, 0.0, 1.0) : 0.0;
             const double a4 = PATH ? dev::dclamp(a1 + a.dalpha, 0.0, 1.0) : 0.0;
-            // the four stages, one evaluation in a loop (traj_rk4_reloc_kernel), summed in the reference's
+            // the four stages, one evaluation in a loop, summed as they come in the reference's
             // association ((s1 + 2 s2) + 2 s3) + s4
             double sx = 0, sy = 0, sz = 0, sw = 0;
             double qx = x, qy = y, qz = z;
@@ -2934,7 +2555,7 @@ __global__ void __launch_bounds__(kTrajBlock, (DiffuseWaves<MAXV>::value)) traj_
                 const double as = st == 0 ? a1 : (st == 3 ? a4 : a2);
                 if constexpr (RELOC) {
                     int sc = cell;
-                    if (st > 0) sc = dev::locate_diffuse<MAXV>(c, cell, qx, qy, qz, a);
+                    if (st > 0) sc = dev::locate<MAXV>(c, cell, qx, qy, qz, a);
                     if (cs.id != sc) {
                         if (sc == cell) cs = c;
                         else load(cs, sc);
@@ -2978,7 +2599,7 @@ __global__ void __launch_bounds__(kTrajBlock, (DiffuseWaves<MAXV>::value)) traj_
             a.rec[5 * a.rec_stride + pid] = hz;
         }
         x = nx; y = ny; z = nz;
-        {  // the kick: counter (gid lo, gid hi, step, epoch), deviates from output words 0 and 1
+        if constexpr (KICK) {  // counter (gid lo, gid hi, step, epoch), deviates from output words 0 and 1
             uint32_t c0 = gid_lo, c1 = gid_hi, c2 = (uint32_t)step, c3 = a.epoch;
             dev::philox4x32_10(c0, c1, c2, c3, a.key0, a.key1);
             dev::kick((unsigned)step, a.kick_s, dev::philox_deviate(c0), dev::philox_deviate(c1), x, y, z);
@@ -4590,50 +4211,44 @@ void launch_traj(const TrajArgs& a, bool path, bool euler, hipStream_t s) {
     }
 }
 
-// MOPS_RK4_RELOCATE: the per-lane relocating kernel (pathlines only; no cooperative selection, no hand-off)
-static mops_status launch_traj_reloc(int maxv, const TrajArgs& a, hipStream_t s) {
+// The per-lane kernel of the mesh's MAXV, the mode, the method and the kick (no cooperative selection, no hand-off).
+// Each run-time choice picks a compile-time constant and passes it on; the forms that exist are traj_lane_kernel's.
+static mops_status launch_traj_lane(int maxv, int mode, int method, bool kick, const TrajLaneArgs& a, hipStream_t s) {
     const unsigned g = (unsigned)((a.n + kTrajBlock - 1) / kTrajBlock);
+    bool launched = false;
+    auto launch = [&](auto MAXV, auto MODE, auto METHOD, auto KICK) {
+        // (without a kick the other depth-mode forms are traj_kernel's: never instantiated here)
+        if constexpr (KICK() || MODE() != kLaneDepthPath || METHOD() == MOPS_RK4_RELOCATE) {
+            traj_lane_kernel<MAXV(), MODE(), METHOD(), KICK()><<<g, kTrajBlock, 0, s>>>(a);
+            launched = true;
+        }
+    };
+    auto by_kick = [&](auto MAXV, auto MODE, auto METHOD) {
+        if (kick) launch(MAXV, MODE, METHOD, std::true_type{});
+        else launch(MAXV, MODE, METHOD, std::false_type{});
+    };
+    auto by_method = [&](auto MAXV, auto MODE) {
+        if (method == MOPS_EULER) by_kick(MAXV, MODE, std::integral_constant<int, MOPS_EULER>{});
+        else if (method == MOPS_RK4_RELOCATE) by_kick(MAXV, MODE, std::integral_constant<int, MOPS_RK4_RELOCATE>{});
+        else by_kick(MAXV, MODE, std::integral_constant<int, MOPS_RK4>{});
+    };
+    auto by_mode = [&](auto MAXV) {
+        if (mode == kLaneDepthPath) by_method(MAXV, std::integral_constant<int, kLaneDepthPath>{});
+        else if (mode == kLaneLayerPath) by_method(MAXV, std::integral_constant<int, kLaneLayerPath>{});
+        else by_method(MAXV, std::integral_constant<int, kLaneLayerStream>{});
+    };
     switch (maxv) {
-        case 7: traj_rk4_reloc_kernel<7><<<g, kTrajBlock, 0, s>>>(a); break;
-#if !defined(MOPS_ONLY7)
-        case 12: traj_rk4_reloc_kernel<12><<<g, kTrajBlock, 0, s>>>(a); break;
-        default: traj_rk4_reloc_kernel<20><<<g, kTrajBlock, 0, s>>>(a); break;
+        case 7: by_mode(std::integral_constant<int, 7>{}); break;
+#if !defined(MOPS_ONLY7)  // experiment builds: MAXV 7 instantiations only
+        case 12: by_mode(std::integral_constant<int, 12>{}); break;
+        default: by_mode(std::integral_constant<int, 20>{}); break;
 #else
         default: return fail(MOPS_ERR_UNSUPPORTED, "experiment build: MAXV 7 only");
 #endif
     }
+    if (!launched) return fail(MOPS_ERR_UNSUPPORTED, "launch_traj_lane: no per-lane kernel of this form");
+    HIP_TRY(hipGetLastError());
     return MOPS_OK;
-}
-
-// mops_traj_advance_layer: the per-lane layer kernel of the run's kind and method
-template <int MAXV>
-static void launch_traj_layer(const TrajLayerArgs& a, bool path, int method, hipStream_t s) {
-    const unsigned g = (unsigned)((a.n + kTrajBlock - 1) / kTrajBlock);
-    if (path) {
-        if (method == MOPS_EULER) traj_layer_kernel<MAXV, true, MOPS_EULER><<<g, kTrajBlock, 0, s>>>(a);
-        else if (method == MOPS_RK4_RELOCATE) traj_layer_kernel<MAXV, true, MOPS_RK4_RELOCATE><<<g, kTrajBlock, 0, s>>>(a);
-        else traj_layer_kernel<MAXV, true, MOPS_RK4><<<g, kTrajBlock, 0, s>>>(a);
-    } else {
-        if (method == MOPS_EULER) traj_layer_kernel<MAXV, false, MOPS_EULER><<<g, kTrajBlock, 0, s>>>(a);
-        else if (method == MOPS_RK4_RELOCATE) traj_layer_kernel<MAXV, false, MOPS_RK4_RELOCATE><<<g, kTrajBlock, 0, s>>>(a);
-        else traj_layer_kernel<MAXV, false, MOPS_RK4><<<g, kTrajBlock, 0, s>>>(a);
-    }
-}
-
-// mops_traj_advance_diffuse / mops_traj_advance_layer_diffuse: the per-lane diffusion kernel of the mode and method
-template <int MAXV, int MODE>
-static void launch_traj_diffuse(const TrajDiffuseArgs& a, int method, hipStream_t s) {
-    const unsigned g = (unsigned)((a.n + kTrajBlock - 1) / kTrajBlock);
-    if (method == MOPS_EULER) traj_diffuse_kernel<MAXV, MODE, MOPS_EULER><<<g, kTrajBlock, 0, s>>>(a);
-    else if (method == MOPS_RK4_RELOCATE) traj_diffuse_kernel<MAXV, MODE, MOPS_RK4_RELOCATE><<<g, kTrajBlock, 0, s>>>(a);
-    else traj_diffuse_kernel<MAXV, MODE, MOPS_RK4><<<g, kTrajBlock, 0, s>>>(a);
-}
-
-template <int MAXV>
-static void launch_traj_diffuse_mode(const TrajDiffuseArgs& a, int mode, int method, hipStream_t s) {
-    if (mode == kDiffDepthPath) launch_traj_diffuse<MAXV, kDiffDepthPath>(a, method, s);
-    else if (mode == kDiffLayerPath) launch_traj_diffuse<MAXV, kDiffLayerPath>(a, method, s);
-    else launch_traj_diffuse<MAXV, kDiffLayerStream>(a, method, s);
 }
 
 // launch_traj's pathline MAXV 7 branch with the CAP instantiations (a.cap set; mops_traj_advance_captured)
@@ -5516,50 +5131,53 @@ struct CapWindow {
     int first, slots;
 };
 
-// mops_traj_advance; `cw` (pathline, maxv 7 only): the launch's CAP instantiations with that capture window
-static mops_status traj_advance_impl(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
-                                     const mops_traj_cfg* cfg, const mops_particles* p, int64_t step_begin,
-                                     int64_t step_end, double* d_records, int64_t record_stride, void* stream,
-                                     const CapWindow* cw) {
-    if (!mesh || !front || !cfg || !p) return fail(MOPS_ERR_INVALID, "mops_traj_advance: invalid inputs");
-    if (cfg->method == MOPS_RK4_RELOCATE && !back)  // (never silently the plain RK4)
-        return fail(MOPS_ERR_UNSUPPORTED, "mops_traj_advance: MOPS_RK4_RELOCATE is for pathlines only (back == NULL)");
+// What every trajectory entry does between its own argument checks and its launch: the settings checks, the step
+// and record counts, the particle checks, the clamped step range and the TrajArgs fill (no cooperative selection, no
+// hand-off).  `who` names the entry in the errors; `path`: a pathline run; front / back: the depth-mode fields
+// (back NULL: a streamline), both NULL in layer mode.  *go stays false where there is nothing to launch.
+static mops_status traj_prepare(const char* who, const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                bool path, const mops_traj_cfg* cfg, const mops_particles* p, int64_t step_begin,
+                                int64_t step_end, double* d_records, int64_t record_stride, TrajArgs& a, bool* go) {
+    const std::string w(who);
+    *go = false;
     if (cfg->delta_t <= 0 || cfg->record_t <= 0 || cfg->simulation_duration <= 0)
         return fail(MOPS_ERR_INVALID, "invalid trajectory settings");  // :666-669
     const int64_t K = mops_traj_num_records(cfg), n_steps = mops_traj_num_steps(cfg);
     if (K <= 0 || n_steps <= 0) return fail(MOPS_ERR_INVALID, "invalid integration steps");  // :709-712
-    // the kernel counts steps, records and the record period in 32 bits (settings only: checked before any handle
+    // the kernels count steps, records and the record period in 32 bits (settings only: checked before any handle
     // is read)
-    const int64_t rec_period = back ? cfg->record_t / cfg->delta_t                          // record_interval (:1470)
+    const int64_t rec_period = path ? cfg->record_t / cfg->delta_t                          // record_interval (:1470)
                                     : cfg->record_t / gcd64(cfg->record_t, cfg->delta_t);  // run_time % recordT == 0 (:994)
     if (n_steps > INT32_MAX || K > INT32_MAX || rec_period > INT32_MAX)
-        return fail(MOPS_ERR_INVALID, "mops_traj_advance: the number of steps, the number of records and the record "
-                                      "period in steps must each be below 2^31");
-    if (front->mesh != mesh || (back && back->mesh != mesh)) return fail(MOPS_ERR_INVALID, "field/mesh mismatch");
+        return fail(MOPS_ERR_INVALID, w + ": the number of steps, the number of records and the record period in "
+                                          "steps must each be below 2^31");
+    if (front && (front->mesh != mesh || (back && back->mesh != mesh)))
+        return fail(MOPS_ERR_INVALID, "field/mesh mismatch");
     if (p->n < 0 || record_stride < p->n) return fail(MOPS_ERR_INVALID, "record_stride < n");
     if (p->n == 0) return MOPS_OK;
     if (!p->d_x || !p->d_y || !p->d_z || !p->d_depth || !p->d_cell || !p->d_death_step || !d_records)
-        return fail(MOPS_ERR_INVALID, "mops_traj_advance: null device pointer");
+        return fail(MOPS_ERR_INVALID, w + ": null device pointer");
     step_begin = std::max<int64_t>(step_begin, 0);
     step_end = std::min<int64_t>(step_end, n_steps);
     if (step_begin >= step_end) return MOPS_OK;
     if (cfg->delta_t > INT32_MAX) return fail(MOPS_ERR_INVALID, "deltaT too large");
-    TrajArgsCap a;  // (launch_traj takes its TrajArgs part)
     a.cellrec = mesh->d_cellrec; a.cxyz = mesh->d_cxyz; a.vxyz = mesh->d_vxyz;
     a.C = (int)mesh->C; a.V = (int)mesh->V; a.L = mesh->L;
-    a.f0 = dev::Field{front->d_zt, front->d_pr};
+    a.f0 = front ? dev::Field{front->d_zt, front->d_pr} : dev::Field{nullptr, nullptr};
     a.f1 = back ? dev::Field{back->d_zt, back->d_pr} : a.f0;
-    a.mono0 = front->d_mono;
-    a.mono1 = back ? back->d_mono : front->d_mono;
+    a.mono0 = front ? front->d_mono : nullptr;
+    a.mono1 = back ? back->d_mono : a.mono0;
     a.order = p->d_order;
     a.n_live = p->d_n_live;
     a.cpoly = mesh->d_cpoly;
     a.cnrm = mesh->d_cnrm;
     a.alpha_tab = nullptr;
-    if (back) MOPS_TRY(alpha_table(mesh, n_steps, &a.alpha_tab));
+    if (path) MOPS_TRY(alpha_table(mesh, n_steps, &a.alpha_tab));
     a.nbr = mesh->d_nbr;
     a.cpolyr = mesh->d_cpolyr;
     a.crank = mesh->d_cell_rank;
+    a.coop_sel = nullptr;
+    a.handoff = 0;
     a.px = p->d_x; a.py = p->d_y; a.pz = p->d_z; a.depth = p->d_depth; a.cell = p->d_cell; a.death = p->d_death_step;
     a.n = p->n;
     a.step_begin = step_begin; a.step_end = step_end; a.n_steps = n_steps;
@@ -5570,16 +5188,30 @@ static mops_status traj_advance_impl(const mops_mesh* mesh, const mops_field* fr
     a.K = K;
     a.rec = d_records;
     a.rec_stride = record_stride;
+    *go = true;
+    return MOPS_OK;
+}
+
+// mops_traj_advance; `cw` (pathline, maxv 7 only): the launch's CAP instantiations with that capture window
+static mops_status traj_advance_impl(const mops_mesh* mesh, const mops_field* front, const mops_field* back,
+                                     const mops_traj_cfg* cfg, const mops_particles* p, int64_t step_begin,
+                                     int64_t step_end, double* d_records, int64_t record_stride, void* stream,
+                                     const CapWindow* cw) {
+    if (!mesh || !front || !cfg || !p) return fail(MOPS_ERR_INVALID, "mops_traj_advance: invalid inputs");
+    if (cfg->method == MOPS_RK4_RELOCATE && !back)  // (never silently the plain RK4)
+        return fail(MOPS_ERR_UNSUPPORTED, "mops_traj_advance: MOPS_RK4_RELOCATE is for pathlines only (back == NULL)");
+    TrajArgsCap a;  // (launch_traj takes its TrajArgs part)
+    bool go;
+    MOPS_TRY(traj_prepare("mops_traj_advance", mesh, front, back, back != nullptr, cfg, p, step_begin, step_end,
+                          d_records, record_stride, a, &go));
+    if (!go) return MOPS_OK;
     const bool euler = (cfg->method == MOPS_EULER);
     hipStream_t s = (hipStream_t)stream;
-    a.coop_sel = nullptr;
     if (cfg->method == MOPS_RK4_RELOCATE) {  // (back != NULL: checked above)
         if (cw) return fail(MOPS_ERR_UNSUPPORTED, "mops_traj_advance: no capture with MOPS_RK4_RELOCATE");
-        a.handoff = 0;
-        a.cap = nullptr; a.cap_stride = 0; a.cap_first = 0; a.cap_slots = 0;
-        MOPS_TRY(launch_traj_reloc(mesh->maxv, a, s));
-        HIP_TRY(hipGetLastError());
-        return MOPS_OK;
+        TrajLaneArgs la{};  // (no layer slices, no kick)
+        static_cast<TrajArgs&>(la) = a;
+        return launch_traj_lane(mesh->maxv, kLaneDepthPath, MOPS_RK4_RELOCATE, false, la, s);
     }
     if ((euler ? MOPS_COOP_PE : MOPS_COOP_PR) && back && mesh->maxv == 7 && !p->d_order) {
         int* sel = nullptr;
@@ -5638,6 +5270,33 @@ mops_status mops_field_layer_velocity(const mops_mesh* mesh, const mops_field* f
     return MOPS_OK;
 }
 
+// The layer entry and both diffusive entries past their own checks: the per-lane kernel of the mode (layer: sl0
+// set, sl1 NULL = a streamline; depth: front and back), with the kick of `dif` (NULL: none)
+static mops_status traj_advance_lane(const char* who, const mops_mesh* mesh, const mops_field* front,
+                                     const mops_field* back, const void* sl0, const void* sl1, const mops_traj_cfg* cfg,
+                                     const mops_particles* p, const mops_diffusion* dif, int64_t step_begin,
+                                     int64_t step_end, double* d_records, int64_t record_stride, void* stream) {
+    const bool layer = sl0 != nullptr, path = layer ? sl1 != nullptr : true;
+    TrajLaneArgs a{};
+    bool go;
+    MOPS_TRY(traj_prepare(who, mesh, front, back, path, cfg, p, step_begin, step_end, d_records, record_stride, a,
+                          &go));
+    if (!go) return MOPS_OK;
+    a.s0 = static_cast<const double4*>(sl0);
+    a.s1 = sl1 ? static_cast<const double4*>(sl1) : a.s0;
+    if (dif) {
+        a.kick_s = mops_diffusion_scale(dif->kh, cfg->delta_t);
+        a.key0 = (uint32_t)(dif->seed & 0xffffffffu);
+        a.key1 = (uint32_t)(dif->seed >> 32);
+        a.epoch = dif->epoch;
+        a.id_base = dif->id_base;
+        a.id = dif->d_id;
+    }
+    const int method = (cfg->method == MOPS_EULER || cfg->method == MOPS_RK4_RELOCATE) ? cfg->method : MOPS_RK4;
+    const int mode = layer ? (path ? kLaneLayerPath : kLaneLayerStream) : kLaneDepthPath;
+    return launch_traj_lane(mesh->maxv, mode, method, dif != nullptr, a, (hipStream_t)stream);
+}
+
 mops_status mops_traj_advance_layer(const mops_mesh* mesh, const void* d_front_layer, const void* d_back_layer,
                                     const mops_traj_cfg* cfg, const mops_particles* p, int64_t step_begin,
                                     int64_t step_end, double* d_records, int64_t record_stride, void* stream) {
@@ -5645,62 +5304,8 @@ mops_status mops_traj_advance_layer(const mops_mesh* mesh, const void* d_front_l
     if (!d_front_layer) return fail(MOPS_ERR_INVALID, "mops_traj_advance_layer: null layer slice");
     if ((((uintptr_t)d_front_layer | (uintptr_t)d_back_layer) & 15u) != 0)
         return fail(MOPS_ERR_INVALID, "mops_traj_advance_layer: a layer slice must be 16-byte aligned");
-    if (cfg->delta_t <= 0 || cfg->record_t <= 0 || cfg->simulation_duration <= 0)
-        return fail(MOPS_ERR_INVALID, "invalid trajectory settings");  // :666-669
-    const int64_t K = mops_traj_num_records(cfg), n_steps = mops_traj_num_steps(cfg);
-    if (K <= 0 || n_steps <= 0) return fail(MOPS_ERR_INVALID, "invalid integration steps");  // :709-712
-    const bool path = d_back_layer != nullptr;
-    const int64_t rec_period = path ? cfg->record_t / cfg->delta_t                          // record_interval (:1470)
-                                    : cfg->record_t / gcd64(cfg->record_t, cfg->delta_t);  // run_time % recordT == 0 (:994)
-    if (n_steps > INT32_MAX || K > INT32_MAX || rec_period > INT32_MAX)
-        return fail(MOPS_ERR_INVALID, "mops_traj_advance_layer: the number of steps, the number of records and the "
-                                      "record period in steps must each be below 2^31");
-    if (p->n < 0 || record_stride < p->n) return fail(MOPS_ERR_INVALID, "record_stride < n");
-    if (p->n == 0) return MOPS_OK;
-    if (!p->d_x || !p->d_y || !p->d_z || !p->d_depth || !p->d_cell || !p->d_death_step || !d_records)
-        return fail(MOPS_ERR_INVALID, "mops_traj_advance_layer: null device pointer");
-    step_begin = std::max<int64_t>(step_begin, 0);
-    step_end = std::min<int64_t>(step_end, n_steps);
-    if (step_begin >= step_end) return MOPS_OK;
-    if (cfg->delta_t > INT32_MAX) return fail(MOPS_ERR_INVALID, "deltaT too large");
-    TrajLayerArgs a;
-    a.cellrec = mesh->d_cellrec; a.cxyz = mesh->d_cxyz; a.vxyz = mesh->d_vxyz;
-    a.C = (int)mesh->C; a.V = (int)mesh->V; a.L = mesh->L;
-    a.f0 = dev::Field{nullptr, nullptr};
-    a.f1 = a.f0;
-    a.mono0 = nullptr; a.mono1 = nullptr;
-    a.order = p->d_order;
-    a.n_live = p->d_n_live;
-    a.cpoly = mesh->d_cpoly;
-    a.cnrm = mesh->d_cnrm;
-    a.alpha_tab = nullptr;
-    if (path) MOPS_TRY(alpha_table(mesh, n_steps, &a.alpha_tab));
-    a.nbr = mesh->d_nbr;
-    a.cpolyr = mesh->d_cpolyr;
-    a.crank = mesh->d_cell_rank;
-    a.coop_sel = nullptr;
-    a.handoff = 0;
-    a.px = p->d_x; a.py = p->d_y; a.pz = p->d_z; a.depth = p->d_depth; a.cell = p->d_cell; a.death = p->d_death_step;
-    a.n = p->n;
-    a.step_begin = step_begin; a.step_end = step_end; a.n_steps = n_steps;
-    const int dt_sign = (cfg->direction == MOPS_FORWARD) ? 1 : -1;
-    a.delta_t = dt_sign * (int)cfg->delta_t;
-    a.dalpha = (double)a.delta_t / (double)cfg->simulation_duration;
-    a.rec_period = rec_period;
-    a.K = K;
-    a.rec = d_records;
-    a.rec_stride = record_stride;
-    a.s0 = static_cast<const double4*>(d_front_layer);
-    a.s1 = path ? static_cast<const double4*>(d_back_layer) : a.s0;
-    const int method = (cfg->method == MOPS_EULER || cfg->method == MOPS_RK4_RELOCATE) ? cfg->method : MOPS_RK4;
-    hipStream_t s = (hipStream_t)stream;
-    switch (mesh->maxv) {
-        case 7: launch_traj_layer<7>(a, path, method, s); break;
-        case 12: launch_traj_layer<12>(a, path, method, s); break;
-        default: launch_traj_layer<20>(a, path, method, s); break;
-    }
-    HIP_TRY(hipGetLastError());
-    return MOPS_OK;
+    return traj_advance_lane("mops_traj_advance_layer", mesh, nullptr, nullptr, d_front_layer, d_back_layer, cfg, p,
+                             nullptr, step_begin, step_end, d_records, record_stride, stream);
 }
 
 // ---- random-walk horizontal diffusion ------------------------------------------
@@ -5712,81 +5317,6 @@ static bool diffusion_valid(const char* who, const mops_diffusion* dif) {
         return false;
     }
     return true;
-}
-
-// Both diffusive entries past their Kh == 0 dispatch: the checks of mops_traj_advance / mops_traj_advance_layer,
-// then the per-lane diffusion kernel of the mode (layer: sl0 set, sl1 NULL = a streamline; depth: front and back)
-static mops_status traj_advance_diffuse_impl(const char* who, const mops_mesh* mesh, const mops_field* front,
-                                             const mops_field* back, const void* sl0, const void* sl1,
-                                             const mops_traj_cfg* cfg, const mops_particles* p,
-                                             const mops_diffusion* dif, int64_t step_begin, int64_t step_end,
-                                             double* d_records, int64_t record_stride, void* stream) {
-    const std::string w(who);
-    const bool layer = sl0 != nullptr;
-    if (cfg->delta_t <= 0 || cfg->record_t <= 0 || cfg->simulation_duration <= 0)
-        return fail(MOPS_ERR_INVALID, "invalid trajectory settings");
-    const int64_t K = mops_traj_num_records(cfg), n_steps = mops_traj_num_steps(cfg);
-    if (K <= 0 || n_steps <= 0) return fail(MOPS_ERR_INVALID, "invalid integration steps");
-    const bool path = layer ? sl1 != nullptr : true;
-    const int64_t rec_period = path ? cfg->record_t / cfg->delta_t : cfg->record_t / gcd64(cfg->record_t, cfg->delta_t);
-    if (n_steps > INT32_MAX || K > INT32_MAX || rec_period > INT32_MAX)
-        return fail(MOPS_ERR_INVALID, w + ": the number of steps, the number of records and the record period in "
-                                          "steps must each be below 2^31");
-    if (!layer && (front->mesh != mesh || back->mesh != mesh)) return fail(MOPS_ERR_INVALID, "field/mesh mismatch");
-    if (p->n < 0 || record_stride < p->n) return fail(MOPS_ERR_INVALID, "record_stride < n");
-    if (p->n == 0) return MOPS_OK;
-    if (!p->d_x || !p->d_y || !p->d_z || !p->d_depth || !p->d_cell || !p->d_death_step || !d_records)
-        return fail(MOPS_ERR_INVALID, w + ": null device pointer");
-    step_begin = std::max<int64_t>(step_begin, 0);
-    step_end = std::min<int64_t>(step_end, n_steps);
-    if (step_begin >= step_end) return MOPS_OK;
-    if (cfg->delta_t > INT32_MAX) return fail(MOPS_ERR_INVALID, "deltaT too large");
-    TrajDiffuseArgs a;
-    a.cellrec = mesh->d_cellrec; a.cxyz = mesh->d_cxyz; a.vxyz = mesh->d_vxyz;
-    a.C = (int)mesh->C; a.V = (int)mesh->V; a.L = mesh->L;
-    a.f0 = layer ? dev::Field{nullptr, nullptr} : dev::Field{front->d_zt, front->d_pr};
-    a.f1 = layer ? a.f0 : dev::Field{back->d_zt, back->d_pr};
-    a.mono0 = layer ? nullptr : front->d_mono;
-    a.mono1 = layer ? nullptr : back->d_mono;
-    a.order = p->d_order;
-    a.n_live = p->d_n_live;
-    a.cpoly = mesh->d_cpoly;
-    a.cnrm = mesh->d_cnrm;
-    a.alpha_tab = nullptr;
-    if (path) MOPS_TRY(alpha_table(mesh, n_steps, &a.alpha_tab));
-    a.nbr = mesh->d_nbr;
-    a.cpolyr = mesh->d_cpolyr;
-    a.crank = mesh->d_cell_rank;
-    a.coop_sel = nullptr;
-    a.handoff = 0;
-    a.px = p->d_x; a.py = p->d_y; a.pz = p->d_z; a.depth = p->d_depth; a.cell = p->d_cell; a.death = p->d_death_step;
-    a.n = p->n;
-    a.step_begin = step_begin; a.step_end = step_end; a.n_steps = n_steps;
-    const int dt_sign = (cfg->direction == MOPS_FORWARD) ? 1 : -1;
-    a.delta_t = dt_sign * (int)cfg->delta_t;
-    a.dalpha = (double)a.delta_t / (double)cfg->simulation_duration;
-    a.rec_period = rec_period;
-    a.K = K;
-    a.rec = d_records;
-    a.rec_stride = record_stride;
-    a.s0 = static_cast<const double4*>(sl0);
-    a.s1 = sl1 ? static_cast<const double4*>(sl1) : a.s0;
-    a.kick_s = mops_diffusion_scale(dif->kh, cfg->delta_t);
-    a.key0 = (uint32_t)(dif->seed & 0xffffffffu);
-    a.key1 = (uint32_t)(dif->seed >> 32);
-    a.epoch = dif->epoch;
-    a.id_base = dif->id_base;
-    a.id = dif->d_id;
-    const int method = (cfg->method == MOPS_EULER || cfg->method == MOPS_RK4_RELOCATE) ? cfg->method : MOPS_RK4;
-    const int mode = layer ? (path ? kDiffLayerPath : kDiffLayerStream) : kDiffDepthPath;
-    hipStream_t s = (hipStream_t)stream;
-    switch (mesh->maxv) {
-        case 7: launch_traj_diffuse_mode<7>(a, mode, method, s); break;
-        case 12: launch_traj_diffuse_mode<12>(a, mode, method, s); break;
-        default: launch_traj_diffuse_mode<20>(a, mode, method, s); break;
-    }
-    HIP_TRY(hipGetLastError());
-    return MOPS_OK;
 }
 
 double mops_diffusion_scale(double kh, int64_t delta_t) {
@@ -5804,8 +5334,8 @@ mops_status mops_traj_advance_diffuse(const mops_mesh* mesh, const mops_field* f
     if (!mesh || !front || !cfg || !p) return fail(MOPS_ERR_INVALID, "mops_traj_advance_diffuse: invalid inputs");
     if (!back)
         return fail(MOPS_ERR_UNSUPPORTED, "mops_traj_advance_diffuse: depth-mode streamlines have no diffusion (back == NULL)");
-    return traj_advance_diffuse_impl("mops_traj_advance_diffuse", mesh, front, back, nullptr, nullptr, cfg, p, dif,
-                                     step_begin, step_end, d_records, record_stride, stream);
+    return traj_advance_lane("mops_traj_advance_diffuse", mesh, front, back, nullptr, nullptr, cfg, p, dif, step_begin,
+                             step_end, d_records, record_stride, stream);
 }
 
 mops_status mops_traj_advance_layer_diffuse(const mops_mesh* mesh, const void* d_front_layer, const void* d_back_layer,
@@ -5820,8 +5350,8 @@ mops_status mops_traj_advance_layer_diffuse(const mops_mesh* mesh, const void* d
     if (!d_front_layer) return fail(MOPS_ERR_INVALID, "mops_traj_advance_layer_diffuse: null layer slice");
     if ((((uintptr_t)d_front_layer | (uintptr_t)d_back_layer) & 15u) != 0)
         return fail(MOPS_ERR_INVALID, "mops_traj_advance_layer_diffuse: a layer slice must be 16-byte aligned");
-    return traj_advance_diffuse_impl("mops_traj_advance_layer_diffuse", mesh, nullptr, nullptr, d_front_layer,
-                                     d_back_layer, cfg, p, dif, step_begin, step_end, d_records, record_stride, stream);
+    return traj_advance_lane("mops_traj_advance_layer_diffuse", mesh, nullptr, nullptr, d_front_layer, d_back_layer,
+                             cfg, p, dif, step_begin, step_end, d_records, record_stride, stream);
 }
 
 mops_status mops_selftest_philox(int64_t n, const uint32_t* d_in, uint32_t* d_words, double* d_r, void* stream) {

@@ -1,5 +1,5 @@
 """GPU: the random-walk horizontal diffusion (mops_traj_advance_diffuse, mops_traj_advance_layer_diffuse,
-traj_diffuse_kernel, mops_selftest_philox) against its Python restatement (tests/diffusion_reference.py, pinned to
+traj_lane_kernel with its kick, mops_selftest_philox) against its Python restatement (tests/diffusion_reference.py, pinned to
 the existing restatements at Kh = 0 by tests/test_diffusion_cpu.py).  Lines are built from the restatement's records
 by the oracle's own assembly.  Every parity assertion is bit-exact.  Kh is in m^2/s."""
 import ctypes as C
@@ -181,6 +181,29 @@ def test_wide_stencil(gpu, engine_lib, oracle_lib, key):
               f"{int((nv[ref['cells']] > 7).sum())}, kick-induced cell changes {int(ref['kick_changes'].sum())}")
         assert int((nv[ref["cells"]] > 7).sum()) >= 16
         assert int((ref["death"] < 0).sum()) >= 8
+
+
+@pytest.mark.parametrize("layer,pathline,m", [(4, False, EULER), (4, False, RK4), (4, False, RELOCATE), (4, True, RK4),
+                                              (4, True, RELOCATE), (None, True, RK4), (None, True, RELOCATE)],
+                         ids=["layer-stream-euler", "layer-stream-rk4", "layer-stream-relocate", "layer-path-rk4",
+                              "layer-path-relocate", "depth-rk4", "depth-relocate"])
+@pytest.mark.parametrize("key", ["me12", "me20"])
+def test_wide_stencil_other_forms(gpu, engine_lib, oracle_lib, key, layer, pathline, m):
+    """The seven forms of the per-lane kernel with the kick that test_wide_stencil does not launch at MAXV 12 and
+    20, on its seeds and times (the restatement keeps 63 or 64 of the 64 alive in each)."""
+    import wide_case as W
+    mesh, s0, s1 = W.world(key)
+    c = _Case(oracle_lib, mesh, s0, s1)
+    allseeds = W.seeds(key)
+    seeds = np.concatenate([allseeds[128:160], allseeds[384:416]])
+    depths = np.full(len(seeds), W.DEPTH, dtype=np.float32)
+    nv = W.degrees(mesh)
+    dt, duration, record_t = W.times(True)
+    times = dict(delta_t=dt, duration=duration // 4, record_t=record_t // 3)  # 90 steps, a record every 10: 9
+    ref = c.ref(layer, pathline, m, seeds=seeds, depths=depths, key=key, **times)
+    _check(c, ref, layer, pathline, m, **times)
+    assert int((nv[ref["cells"]] > 7).sum()) >= 16
+    assert int((ref["death"] < 0).sum()) >= 8
 
 
 # ---- invariance ----------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""GPU: fixed-layer streamlines and pathlines (mops_traj_advance_layer, traj_layer_kernel; the slice kernel behind
+"""GPU: fixed-layer streamlines and pathlines (mops_traj_advance_layer, traj_lane_kernel; the slice kernel behind
 mops_field_layer_velocity) against the Python restatement of the layer step (tests/layer_reference.py, pinned to the
 oracle by tests/test_layer_cpu.py).  Lines are built from the restatement's records by the oracle's own assembly.
 Every parity assertion is bit-exact."""
@@ -244,6 +244,26 @@ def test_wide_stencil(gpu, engine_lib, oracle_lib, key):
               f"than 7 vertices {int((nv[ref['cells']] > 7).sum())}, relocations {int(ref['relocations'].sum())}")
         assert int((nv[ref["cells"]] > 7).sum()) >= 16
         assert int((ref["death"] < 0).sum()) >= 8
+
+
+@pytest.mark.parametrize("pathline,m", [(False, RK4), (True, RELOCATE)], ids=["stream-rk4", "path-relocate"])
+@pytest.mark.parametrize("key", ["me12", "me20"])
+def test_wide_stencil_other_forms(gpu, engine_lib, oracle_lib, key, pathline, m):
+    """The two forms of the per-lane kernel that test_wide_stencil does not launch at MAXV 12 and 20, on its seeds,
+    over 90 steps with a record every 10 (the restatement keeps 63 or 64 of the 64 alive over twice as many)."""
+    import wide_case as W
+    mesh, s0, s1 = W.world(key)
+    c = _Case(oracle_lib, mesh, s0, s1)
+    allseeds = W.seeds(key)
+    seeds = np.concatenate([allseeds[128:160], allseeds[384:416]])
+    depths = np.full(len(seeds), W.DEPTH, dtype=np.float32)
+    nv = W.degrees(mesh)
+    dt, duration, record_t = W.times(True)
+    times = dict(delta_t=dt, duration=duration // 4, record_t=record_t // 3)
+    ref = c.ref(4, pathline, m, seeds=seeds, depths=depths, key=key, **times)
+    _check(c, ref, 4, pathline, m, **times)
+    assert int((nv[ref["cells"]] > 7).sum()) >= 16
+    assert int((ref["death"] < 0).sum()) >= 8
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65])

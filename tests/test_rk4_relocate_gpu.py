@@ -1,4 +1,4 @@
-"""GPU: the pathline RK4 that locates each stage in its own cell (MOPS_RK4_RELOCATE, traj_rk4_reloc_kernel) against
+"""GPU: the pathline RK4 that locates each stage in its own cell (MOPS_RK4_RELOCATE, traj_lane_kernel) against
 the Python restatement of the loop (tests/rk4_relocate_reference.py, pinned to the oracle with the switch off by
 tests/test_rk4_relocate_cpu.py).  Lines are built from the restatement's records by the oracle's own assembly.
 Every parity assertion is bit-exact."""

@@ -230,7 +230,7 @@ def test_segmented_run_with_compaction_equals_single(device, gpu, key):
 # ---- the relocating RK4 and the attribute samplers ------------------------------------------------------------
 @pytest.mark.parametrize("key", WC.KEYS)
 def test_rk4_relocate_bit_exact(device, oracle_lib, capsys, key):
-    """traj_rk4_reloc_kernel<7 / 12 / 20> against tests/rk4_relocate_reference.py: stages that land in a wide
+    """traj_lane_kernel<7 / 12 / 20>'s relocating RK4 against tests/rk4_relocate_reference.py: stages that land in a wide
     cell from a hexagon and in a hexagon from a wide cell."""
     from mops_amd.engine import run_trajectories
     d = device(key)
