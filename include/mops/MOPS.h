@@ -130,7 +130,30 @@ struct VisualizationSettings {
     // MOPS_RunRemappingSection's great-circle path (this engine's extension): waypoints (x = lat, y = lon) in
     // degrees; its rows span DepthRange, or the grid's reference bottom depths while DepthRange is (0, 0)
     std::vector<vec2> SectionPath;
+    // MOPS_RunEddyCensus (this engine's extension): the Okubo-Weiss threshold in standard deviations of the layer
+    // (the census takes -EddyThreshold * sigma) and the fewest cells an eddy may have
+    double EddyThreshold = 0.2;
+    int EddyMinCells = 4;
     VisualizationSettings() = default;
+};
+
+// One row of MOPS_RunEddyCensus's table (mops_eddy_table, mops_traj.h): lat / lon in degrees and the radius of
+// the circle of `area` (metres) are formed on the host from `centre` and `area`.
+struct Eddy {
+    int index = 0;
+    double lat = 0.0, lon = 0.0, radius = 0.0, area = 0.0;
+    int polarity = 0;  // +1 / -1: the sign of the vorticity
+    double circulation = 0.0;
+    int n_cells = 0, root = 0, core_cell = 0;
+    double ow_min = 0.0;
+    CartesianCoord centre{};
+};
+
+struct EddyCensus {
+    double threshold = 0.0;        // the Okubo-Weiss threshold used
+    std::vector<Eddy> eddies;      // ascending root cell
+    std::vector<int> labels;       // [nCells]: the eddy index of every cell, or -1
+    ImageBuffer<double> image;     // {eddy index, polarity, 0, 1} on the config's window
 };
 
 struct TrajectorySettings {
@@ -306,6 +329,16 @@ double MOPS_SectionTransport(const ImageBuffer<double>& image, VisualizationSett
 // and layerRule, so it overlays the velocity, density and FTLE images.  NaN where a pixel fails.  Invalid inputs
 // (null config, no solution, image size below 1): Error() and an empty vector.
 std::vector<ImageBuffer<double>> MOPS_RunEddyMap(VisualizationSettings* config);
+// Extension ("eddy census", mops_traj.h): the eddies of the active front solution at layer config->FixedLayer
+// (truncated and clamped into the levels as VisualizeFixedLayer does) as objects: the connected sets of at least
+// config->EddyMinCells cells whose Okubo-Weiss parameter lies below -config->EddyThreshold standard deviations
+// (population, over the layer's finite values, FP64 on the host) of the layer, split by the sign of their
+// vorticity (mops_velocity_gradient, mops_eddy_classify, mops_label_components, mops_eddy_count,
+// mops_eddy_table).  The image is built from the cell map of the fixed-layer remapping on the config's window:
+// channels 0 and 1 are NaN where the fixed-layer image is NaN or the pixel's cell is in no eddy, so it overlays
+// every other image of the window.  Invalid inputs (null config, no solution, image size below 1, a
+// non-finite EddyThreshold, EddyMinCells < 1, no finite Okubo-Weiss value): Error() and an empty result.
+EddyCensus MOPS_RunEddyCensus(VisualizationSettings* config);
 void MOPS_GenerateSamplePoints(SamplingSettings* config, std::vector<CartesianCoord>& sample_points);
 
 // SaveToPNG (src/Common/ImageBuffer.hpp:91-136) for the double image (the one instantiation the reference

@@ -780,6 +780,78 @@ mops_status mops_velocity_gradient(const mops_mesh* mesh, const mops_field* fiel
  * without cellsOnVertex. */
 mops_status mops_cell_to_vertex_signed(const mops_mesh* mesh, const double* d_cell, double* d_vertex, void* stream);
 
+/* ---- eddy census: Okubo-Weiss cores as connected components --------------- */
+
+/* The cells whose Okubo-Weiss parameter lies below a threshold, split by the
+ * sign of their vorticity, grouped into the connected components of the
+ * cellsOnCell graph, and one table row per component (no reference
+ * counterpart).  FP64, no contraction; every expression as written here, left
+ * to right; every sum starts from 0.0; only + - * / and sqrt.  All cell arrays
+ * are in the caller's cell order.
+ *
+ * mops_cell_area: area[c] = 0.5 * |A2|, A2 exactly the velocity-gradient
+ * section's: the same frame, xi_k / eta_k and sum over k = 0 .. n-1 of
+ * (xi_k*eta_k+1 - xi_k+1*eta_k); NaN where that section refuses the cell
+ * (n < 3, A2 == 0, A2 not finite).  Device array [C]; enqueues on `stream`
+ * and does not synchronise. */
+mops_status mops_cell_area(const mops_mesh* mesh, double* d_area, void* stream);
+
+/* mops_eddy_classify: for level l over arrays [C*L] as mops_velocity_gradient
+ * writes them, class[c] = +1 if ow[c*L+l] < threshold and vort[c*L+l] > 0,
+ * -1 if ow[c*L+l] < threshold and vort[c*L+l] < 0, 0 otherwise (NaN compares
+ * false: a NaN cell is class 0).  int32 [C] on the device; enqueues on
+ * `stream` and does not synchronise.  MOPS_ERR_INVALID for a null argument or
+ * a level outside 0 .. L-1. */
+mops_status mops_eddy_classify(const mops_mesh* mesh, const double* d_okubo_weiss, const double* d_vorticity,
+                               int32_t level, double threshold, int32_t* d_class, void* stream);
+
+/* mops_label_components: connected components of any int32 class[C].  Cells c
+ * and d are joined if d is in cellsOnCell[c][0 .. nEdgesOnCell[c]-1] or c in
+ * d's list, both are valid cells (an entry outside 1 .. nCells joins nothing)
+ * and class[c] == class[d] != 0.  label[c] = the smallest cell index of c's
+ * component; -1 for a class-0 cell.  The result is unique: its bytes do not
+ * depend on the launch.  Union-find with 32-bit atomic minima over d_label as
+ * the parent array (parent[x] <= x always, so every chase is bounded; no
+ * kernel waits on another workgroup); after every round the host reads one
+ * flag that a checking kernel raises while an edge still joins two roots, so
+ * the entry SYNCHRONISES `stream` (once per round; one round is the rule) and
+ * returns MOPS_ERR_UNSUPPORTED, never looping on, if 16 rounds do not
+ * converge.  h_rounds (host, may be NULL) receives the rounds used:
+ * informational.  Any maxEdges up to 20. */
+mops_status mops_label_components(const mops_mesh* mesh, const int32_t* d_class, int32_t* d_label, int32_t* h_rounds,
+                                  void* stream);
+
+/* mops_eddy_count: membership.  Components of fewer than min_cells cells are
+ * dropped, the rest numbered 0 .. E-1 in ascending order of their root cell
+ * (their label); eddy_of_cell[c] = that index or -1 (int32 [C], device);
+ * *h_n_eddies = E.  The numbering is formed on the host from a copy of the
+ * labels: SYNCHRONISES `stream`.  MOPS_ERR_INVALID for a null argument,
+ * min_cells < 1, or an array that is not a label array (a label is -1 or a
+ * cell <= c that is its own label). */
+mops_status mops_eddy_count(const mops_mesh* mesh, const int32_t* d_label, int32_t min_cells, int32_t* d_eddy_of_cell,
+                            int64_t* h_n_eddies, void* stream);
+
+/* mops_eddy_table: one row per eddy e, into HOST arrays [n_eddies] (h_centre
+ * [n_eddies*3]); every sum runs over the eddy's cells in ascending cell index,
+ * one lane per eddy:
+ *   root = the smallest member, n_cells, polarity = class[root],
+ *   area = sum area[c],  circulation = sum vort[c*L+l] * area[c],
+ *   ow_min / core_cell: w = +inf, then for each c: if ow[c*L+l] < w take it
+ *     (the first strict minimum; core_cell -1 if none),
+ *   S = sum area[c] * cellCoord[c] per component,
+ *   centre = S / sqrt((Sx*Sx + Sy*Sy) + Sz*Sz) per component.
+ * d_eddy_of_cell and n_eddies as mops_eddy_count gave them; d_class [C],
+ * d_area [C] (mops_cell_area), d_vorticity / d_okubo_weiss [C*L].
+ * SYNCHRONISES `stream` (the member lists are sorted on the host).  With
+ * n_eddies == 0 nothing is written.  MOPS_ERR_INVALID for a null argument, a
+ * level outside 0 .. L-1, n_eddies outside 0 .. C or an eddy index outside
+ * -1 .. n_eddies-1. */
+mops_status mops_eddy_table(const mops_mesh* mesh, const int32_t* d_eddy_of_cell, int64_t n_eddies,
+                            const int32_t* d_class, const double* d_area, const double* d_vorticity,
+                            const double* d_okubo_weiss, int32_t level, int32_t* h_root, int32_t* h_n_cells,
+                            int32_t* h_polarity, int32_t* h_core_cell, double* h_area, double* h_circulation,
+                            double* h_ow_min, double* h_centre, void* stream);
+
 /* ---- colour mapping ------------------------------------------------------ */
 
 /* MOPS::SaveToPNG's pixel work (src/Common/ImageBuffer.hpp:91-136) on the

@@ -32,6 +32,7 @@ EXPORTED = (
     "mops_remap_fixed_layer", "mops_colormap_rgba8", "mops_colormap_image",
     "mops_section_points", "mops_remap_section", "mops_section_transport",
     "mops_velocity_gradient", "mops_cell_to_vertex_signed",
+    "mops_cell_area", "mops_eddy_classify", "mops_label_components", "mops_eddy_count", "mops_eddy_table",
     "mops_density_bytes", "mops_density_accumulate", "mops_density_image",
     "mops_flowmap_lattice", "mops_ftle_image",
     # include/mops_io.h
@@ -231,6 +232,13 @@ def load(path: str | None = None):
     if hasattr(lib, "mops_velocity_gradient"):  # (older engine builds timed as variants lack the eddy fields)
         lib.mops_velocity_gradient.argtypes = [P, P, P, P, P, P, P]; lib.mops_velocity_gradient.restype = st
         lib.mops_cell_to_vertex_signed.argtypes = [P, P, P, P]; lib.mops_cell_to_vertex_signed.restype = st
+    if hasattr(lib, "mops_label_components"):  # (older engine builds timed as variants lack the eddy census)
+        lib.mops_cell_area.argtypes = [P, P, P]; lib.mops_cell_area.restype = st
+        lib.mops_eddy_classify.argtypes = [P, P, P, I32, C.c_double, P, P]; lib.mops_eddy_classify.restype = st
+        lib.mops_label_components.argtypes = [P, P, P, P, P]; lib.mops_label_components.restype = st
+        lib.mops_eddy_count.argtypes = [P, P, I32, P, P, P]; lib.mops_eddy_count.restype = st
+        lib.mops_eddy_table.argtypes = [P, P, I64, P, P, P, P, I32, P, P, P, P, P, P, P, P, P]
+        lib.mops_eddy_table.restype = st
     lib.mops_colormap_rgba8.argtypes = [P, I32, I32, I32, P, P, P]; lib.mops_colormap_rgba8.restype = st
     lib.mops_colormap_image.argtypes = [P, I32, I32, I32, P, P, P]; lib.mops_colormap_image.restype = st
     lib.mops_density_bytes.argtypes = [I32, I32]; lib.mops_density_bytes.restype = I64

@@ -22,6 +22,11 @@ Mirrors the reference's command-line driver (CLI/main.cpp) option for option:
     --eddy         extension: per timestep also the relative vorticity and Okubo-Weiss image at the fixed depth, on
                    the remap's window and size, written as ``eddy_output_0_ch<c>.png`` (with ``--vti`` also
                    ``eddy_timestep_<t>_tile_0_fixed_depth_<depth>.vti``)
+    --eddy-census  extension: per timestep also the eddy census of model layer ``--layer K`` (layer 0 without it):
+                   ``eddy_census_<t>.txt``, one line per eddy (index, lat, lon, radius in km, area in m^2, polarity,
+                   circulation in m^2/s, cells), the label image ``eddy_labels_output_0_ch<c>.png`` on the remap's
+                   window and size (with ``--vti`` also ``eddy_labels_timestep_<t>_tile_0_fixed_depth_<K>.vti``),
+                   and the count, printed
 
 and its run (CLI/main.cpp:94-262): grid and one solution per timestep from the
 YAML (initGrid_DemoLoading / initSolution_DemoLoading, with temperature and
@@ -67,6 +72,8 @@ def parse_command_line(argv):
     p.add_argument("--seed", type=int, default=0, help="Seed of the random walk")
     p.add_argument("--section", default=None, help='Vertical section along "lat,lon;lat,lon[;...]"')
     p.add_argument("--eddy", action="store_true", help="Also write the vorticity / Okubo-Weiss image")
+    p.add_argument("--eddy-census", dest="eddy_census", action="store_true",
+                   help="Also write the eddy census of layer --layer (default 0) and its label image")
     p.add_argument("-h", "--help", action="store_true", help="Print this information")
     argv = list(argv)
     for i in range(len(argv) - 1):  # a path that begins with a southern latitude ("-30,...") is a value, not an option
@@ -223,6 +230,50 @@ def run_eddy_stage(M, mio, timestep, depth, vti=False, width=REMAP_WIDTH, height
     return written
 
 
+CENSUS_VTI_NAMES = ("Eddy Index", "Polarity", "None")
+
+
+def run_census_stage(M, mio, timestep, layer, vti=False, width=REMAP_WIDTH, height=REMAP_HEIGHT):
+    """The extension ``--eddy-census``: the eddies of the active timestep at model layer ``layer``
+    (``MOPS_RunEddyCensus`` with the settings' defaults: 0.2 standard deviations, 4 cells), written as
+    ``eddy_census_<t>.txt`` -- one line per eddy: index, lat, lon, radius in km, area in m^2, polarity,
+    circulation in m^2/s, cells -- and their label image on the remapping stage's window and size as
+    ``eddy_labels_output_0_ch<c>.png`` and, with ``vti``, ``eddy_labels_timestep_<t>_tile_0_fixed_depth_
+    <layer>.vti``.  Prints the count.  Returns (the files written, the eddies), or ([], None) for invalid inputs."""
+    from . import engine
+    cfg = M.VisualizationSettings()
+    cfg.imageSize = (float(width), float(height))
+    cfg.LatRange = (-90.0, 90.0)
+    cfg.LonRange = (-180.0, 180.0)
+    cfg.FixedLayer = float(layer)
+    cfg.TimeStep = timestep
+    cfg.SaveType = M.SaveType.kVTI if vti else M.SaveType.kPNG
+    got = M._census_device(cfg)
+    if got is None:
+        return [], None
+    census, image = got
+    eddies = M._census_rows(census)
+    written = [f"eddy_census_{timestep}.txt"]
+    with open(written[0], "w") as f:
+        f.write("# index lat lon radius_km area_m2 polarity circulation_m2_s cells\n")
+        for e in eddies:
+            f.write(f"{e['index']} {e['lat']:.6f} {e['lon']:.6f} {e['radius'] / 1000.0:.6f} {e['area']:.9e} "
+                    f"{e['polarity']:+d} {e['circulation']:.9e} {e['n_cells']}\n")
+    planes = engine.colormap_rgba(image, channels=(0, 1, 2)).cpu().numpy()
+    for ch in range(3):
+        name = f"eddy_labels_output_0_ch{ch}.png"
+        mio.write_png_rgba8(name, planes[ch])
+        written.append(name)
+    if vti:
+        written.append(M.SaveVTI(image.cpu().numpy()[None], cfg, CENSUS_VTI_NAMES,
+                                 f"eddy_labels_timestep_{timestep}_tile_{cfg.tile_index}"))
+    n_pos = sum(1 for e in eddies if e["polarity"] > 0)
+    print(f"[MOPS_CLI] timestep {timestep}: eddy census of layer {census.layer}: {len(eddies)} eddies "
+          f"({n_pos} of positive vorticity, {len(eddies) - n_pos} of negative) below Okubo-Weiss "
+          f"{census.threshold:.6e}; written: " + " ".join(written))
+    return written, eddies
+
+
 def main(argv=None) -> int:
     args = parse_command_line(sys.argv[1:] if argv is None else argv)
     if args is None:
@@ -264,6 +315,8 @@ def main(argv=None) -> int:
             run_section_stage(M, mio, t, args.section, args.vti)
         if args.eddy:
             run_eddy_stage(M, mio, t, args.depth, args.vti)
+        if args.eddy_census:
+            run_census_stage(M, mio, t, args.layer if args.layer is not None else 0, args.vti)
 
     # 7. sample points: 31 x 31 lattice request in [35, 45] x [-90, -15] (exclusive upper bounds)
     print("== generate sample points ==")

@@ -834,6 +834,116 @@ ImageBuffer<double> MOPS_RunFTLE(const std::vector<TrajectoryLine>& lines, Visua
     return img;
 }
 
+EddyCensus MOPS_RunEddyCensus(VisualizationSettings* config) {
+    ScopedTimer t("GPUKernel::EddyCensus", "GPUKernel");
+    const int W = config ? (int)config->imageSize.x : 0, H = config ? (int)config->imageSize.y : 0;
+    if (config == nullptr || g_app.mesh == nullptr || g_app.front == nullptr || W <= 0 || H <= 0) {
+        Error("[MI355X::EddyCensus] invalid inputs");
+        return {};
+    }
+    if (!std::isfinite(config->EddyThreshold) || config->EddyMinCells < 1) {
+        Error("[MI355X::EddyCensus] EddyThreshold must be finite and EddyMinCells at least 1");
+        return {};
+    }
+    auto hip = [](hipError_t e, const char* what) {
+        if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+    };
+    struct DevBuf {
+        void* p = nullptr;
+        ~DevBuf() { (void)hipFree(p); }
+    };
+    const size_t C = g_app.grid->mCellsSize, L = g_app.grid->mVertLevels, CL = C * L, px = (size_t)W * H;
+    const double fl = config->FixedLayer;  // VisualizeFixedLayer's ClampLayer((int)FixedLayer, L)
+    const int layer = !(fl >= 1.0) ? 0 : (fl >= (double)L ? (int)L - 1 : (int)fl);
+    DevBuf grad, area, ints, img, cells;  // vorticity | okubo_weiss; area; class | component | eddy_of_cell
+    hip(hipMalloc(&grad.p, 2 * CL * sizeof(double)), "MOPS_RunEddyCensus: hipMalloc");
+    hip(hipMalloc(&area.p, C * sizeof(double)), "MOPS_RunEddyCensus: hipMalloc");
+    hip(hipMalloc(&ints.p, 3 * C * sizeof(int32_t)), "MOPS_RunEddyCensus: hipMalloc");
+    hip(hipMalloc(&img.p, px * 4 * sizeof(double)), "MOPS_RunEddyCensus: hipMalloc");
+    hip(hipMalloc(&cells.p, px * sizeof(int32_t)), "MOPS_RunEddyCensus: hipMalloc");
+    double* d_vort = static_cast<double*>(grad.p);
+    double* d_ow = d_vort + CL;
+    int32_t* d_class = static_cast<int32_t*>(ints.p);
+    int32_t* d_comp = d_class + C;
+    int32_t* d_eddy = d_class + 2 * C;
+    check(mops_velocity_gradient(g_app.mesh, g_app.front, d_vort, nullptr, nullptr, d_ow, nullptr),
+          "mops_velocity_gradient");
+    // sigma: the population standard deviation of the layer's finite Okubo-Weiss values, two passes in FP64
+    // (the layer's column alone comes to the host: a strided copy of C doubles, not the [C*L] array)
+    std::vector<double> ow(C);
+    hip(hipMemcpy2D(ow.data(), sizeof(double), d_ow + layer, L * sizeof(double), sizeof(double), C,
+                    hipMemcpyDeviceToHost),
+        "hipMemcpy2D okubo_weiss");
+    double sum = 0.0, ss = 0.0;
+    size_t n = 0;
+    for (size_t c = 0; c < C; ++c)
+        if (std::isfinite(ow[c])) { sum += ow[c]; ++n; }
+    const double mean = n ? sum / (double)n : 0.0;
+    for (size_t c = 0; c < C; ++c)
+        if (std::isfinite(ow[c])) ss += (ow[c] - mean) * (ow[c] - mean);
+    const double threshold = n ? -config->EddyThreshold * std::sqrt(ss / (double)n) : NAN;
+    if (!std::isfinite(threshold)) {
+        Error("[MI355X::EddyCensus] no finite Okubo-Weiss value in the layer: no threshold");
+        return {};
+    }
+    check(mops_eddy_classify(g_app.mesh, d_ow, d_vort, layer, threshold, d_class, nullptr), "mops_eddy_classify");
+    check(mops_label_components(g_app.mesh, d_class, d_comp, nullptr, nullptr), "mops_label_components");
+    check(mops_cell_area(g_app.mesh, static_cast<double*>(area.p), nullptr), "mops_cell_area");
+    int64_t E = 0;
+    check(mops_eddy_count(g_app.mesh, d_comp, config->EddyMinCells, d_eddy, &E, nullptr), "mops_eddy_count");
+    std::vector<int32_t> root(E), n_cells(E), polarity(E), core(E);
+    std::vector<double> sum_area(E), circ(E), ow_min(E), centre(3 * (size_t)E);
+    check(mops_eddy_table(g_app.mesh, d_eddy, E, d_class, static_cast<double*>(area.p), d_vort, d_ow, layer,
+                          root.data(), n_cells.data(), polarity.data(), core.data(), sum_area.data(), circ.data(),
+                          ow_min.data(), centre.data(), nullptr),
+          "mops_eddy_table");
+    EddyCensus out;
+    out.threshold = threshold;
+    out.eddies.resize((size_t)E);
+    const double deg = 180.0 / M_PI;
+    for (int64_t e = 0; e < E; ++e) {
+        Eddy& d = out.eddies[(size_t)e];
+        d.index = (int)e;
+        d.centre = {centre[3 * e], centre[3 * e + 1], centre[3 * e + 2]};
+        d.lat = std::asin(d.centre.z) * deg;
+        d.lon = std::atan2(d.centre.y, d.centre.x) * deg;
+        d.area = sum_area[e];
+        d.radius = std::sqrt(d.area / M_PI);
+        d.polarity = polarity[e];
+        d.circulation = circ[e];
+        d.n_cells = n_cells[e];
+        d.root = root[e];
+        d.core_cell = core[e];
+        d.ow_min = ow_min[e];
+    }
+    std::vector<int32_t> cls(C), eddy(C), cell(px);
+    hip(hipMemcpy(cls.data(), d_class, C * sizeof(int32_t), hipMemcpyDeviceToHost), "hipMemcpy classes");
+    hip(hipMemcpy(eddy.data(), d_eddy, C * sizeof(int32_t), hipMemcpyDeviceToHost), "hipMemcpy labels");
+    out.labels.assign(eddy.begin(), eddy.end());
+    // the label image from the fixed-layer remapping's cell map
+    mops_remap_cfg cfg{};
+    cfg.width = W; cfg.height = H;
+    cfg.min_lat = config->LatRange.x; cfg.max_lat = config->LatRange.y;
+    cfg.min_lon = config->LonRange.x; cfg.max_lon = config->LonRange.y;
+    cfg.fixed_layer = (double)layer;
+    check(mops_remap_fixed_layer(g_app.mesh, g_app.front, &cfg, static_cast<double*>(img.p),
+                                 static_cast<int32_t*>(cells.p), nullptr),
+          "mops_remap_fixed_layer");
+    out.image = ImageBuffer<double>(W, H);
+    hip(hipMemcpy(out.image.mPixels.data(), img.p, px * 4 * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy image");
+    hip(hipMemcpy(cell.data(), cells.p, px * sizeof(int32_t), hipMemcpyDeviceToHost), "hipMemcpy cells");
+    for (size_t i = 0; i < px; ++i) {
+        double* p = &out.image.mPixels[4 * i];
+        const int32_t c = cell[i];
+        const bool ok = c >= 0 && (size_t)c < C && !std::isnan(p[0]) && eddy[c] >= 0;
+        p[0] = ok ? (double)eddy[c] : NAN;
+        p[1] = ok ? (double)cls[c] : NAN;
+        p[2] = 0.0;
+        p[3] = 1.0;
+    }
+    return out;
+}
+
 void MPASOVisualizer::VisualizeFixedLayer(VisualizationSettings* config, ImageBuffer<double>* img) {
     ScopedTimer t("GPUKernel::FixedLayer", "GPUKernel");
     if (config == nullptr || img == nullptr || g_app.mesh == nullptr || g_app.front == nullptr) {  // :143-146

@@ -6931,6 +6931,357 @@ mops_status mops_cell_to_vertex_signed(const mops_mesh* mesh, const double* d_ce
 }  // extern "C"
 
 // ===========================================================================
+// eddy census (mops_cell_area, mops_eddy_classify, mops_label_components, mops_eddy_count, mops_eddy_table; no
+// reference counterpart; stated in include/mops_traj.h): the cells whose Okubo-Weiss parameter lies below a
+// threshold, split by the sign of their vorticity, grouped into the connected components of the cellsOnCell
+// graph, and one table row per component.
+//
+// Labelling is union-find over a parent array with 32-bit atomicMin, one lane per cell.
+// label[] itself is the parent array.  Invariants:
+//   (a) parent[x] <= x at every instant: a cell starts as its own parent and the only concurrent write is
+//       atomicMin(&parent[hi], lo) with lo < hi.  A pointer chase therefore descends strictly and ends after at
+//       most x hops whatever the other lanes do; cc_find also stops at a value that breaks (a), so a corrupted
+//       array ends the chase instead of extending it.
+//   (b) every link joins two cells of one component of the graph: a lane only ever unites the ends of an edge of
+//       equal non-zero class, or two cells already linked to them.
+//   (c) no link is lost: when atomicMin finds parent[hi] == old != hi, hi stays linked to min(old, lo) and the
+//       lane goes on to unite old with lo, so whatever was connected stays connected.  The pair's maximum
+//       falls strictly with every turn of that loop: it ends without waiting for any other lane.
+// No kernel waits on another workgroup or spins on a flag.  After the hook kernel the flatten kernel points
+// every cell at its root, and the check kernel (a launch of its own, so it sees every write) raises a flag if an
+// edge of equal class still has two roots or a parent is not a root; the host reads the flag and, if it is up,
+// runs another round, kLabelMaxRounds at the most.  With one tree per component (b, c) and (a), the root is the
+// component's smallest cell: the result is unique, so its bytes do not depend on the schedule.
+// ===========================================================================
+namespace {
+
+constexpr int kLabelMaxRounds = 16;
+
+// twice the signed area of cell c in its centre's east / north plane: velocity_gradient_kernel's frame, xi / eta
+// and A2 sum restated for one lane (sharing a device function with that kernel would re-inline it there)
+__global__ void __launch_bounds__(kBlock) cell_area_kernel(int64_t C, int rec_ints, int maxv, const int* cellrec,
+                                                           const double4* cxyz, const double4* vxyz, double* area) {
+    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= C) return;
+    const int* r = cellrec + c * rec_ints;
+    int n = r[0];
+    if (n > maxv) n = 0;  // (mops_mesh_create admits no such cell)
+    const double4 q = cxyz[c];
+    const double cx = q.x, cy = q.y, cz = q.z;
+    double ex = 1.0, ey = 0.0, ez = 0.0, nx = 0.0, ny = 1.0, nz = 0.0;
+    const double Rxy = sqrt(cx * cx + cy * cy);
+    if (Rxy == 0.0) {
+        ny = cz > 0.0 ? 1.0 : -1.0;
+    } else {
+        const double Rxyz = sqrt((cx * cx + cy * cy) + cz * cz);
+        const double clon = cx / Rxy, slon = cy / Rxy, slat = cz / Rxyz, clat = Rxy / Rxyz;
+        ex = -slon; ey = clon; ez = 0.0;
+        nx = -slat * clon; ny = -slat * slon; nz = clat;
+    }
+    double A2 = 0.0, xi0 = 0.0, eta0 = 0.0, xik = 0.0, etak = 0.0;
+    for (int k = 0; k <= n && n > 0; ++k) {  // step k forms vertex k (vertex 0 again at k == n) and adds term k-1
+        double xi = xi0, eta = eta0;
+        if (k < n) {
+            const double4 p = vxyz[r[1 + k]];  // 0 <= r[1 + k] < V for k < n (mops_mesh_create)
+            const double dx = p.x - cx, dy = p.y - cy, dz = p.z - cz;
+            xi = (dx * ex + dy * ey) + dz * ez;
+            eta = (dx * nx + dy * ny) + dz * nz;
+        }
+        if (k == 0) { xi0 = xi; eta0 = eta; }
+        else A2 += xik * eta - xi * etak;
+        xik = xi; etak = eta;
+    }
+    const bool valid = n >= 3 && A2 != 0.0 && isfinite(A2);
+    area[c] = valid ? 0.5 * fabs(A2) : __builtin_nan("");
+}
+
+__global__ void __launch_bounds__(kBlock) eddy_classify_kernel(int64_t C, int L, int l, const double* ow,
+                                                               const double* vort, double threshold, int* cls) {
+    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= C) return;
+    const double w = ow[c * L + l], z = vort[c * L + l];
+    cls[c] = w < threshold ? (z > 0.0 ? 1 : (z < 0.0 ? -1 : 0)) : 0;  // NaN compares false: class 0
+}
+
+struct LabelArgs {
+    int C, rec_ints, maxv;
+    const int* cellrec;
+    const int* cls;
+    int* parent;
+    int* flag;
+};
+
+__global__ void __launch_bounds__(kBlock) label_init_kernel(int C, int* parent) {
+    const int c = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (c < C) parent[c] = c;
+}
+
+// the root of x's tree: parent[] read at device scope, so a link made by another workgroup is seen; ends at the
+// first value that is not a smaller valid index (invariant (a): at most x hops)
+__device__ __forceinline__ int cc_find(const int* parent, int x) {
+    for (;;) {
+        const int p = __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((unsigned)p >= (unsigned)x) return x;
+        x = p;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) label_hook_kernel(LabelArgs a) {
+    const int c = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (c >= a.C) return;
+    const int k = a.cls[c];
+    if (k == 0) return;
+    const int* r = a.cellrec + (int64_t)c * a.rec_ints;
+    int n = r[0];
+    if (n > a.maxv) n = a.maxv;
+    for (int j = 0; j < n; ++j) {
+        const int d = r[1 + a.maxv + j];
+        if ((unsigned)d >= (unsigned)a.C || d == c || a.cls[d] != k) continue;
+        int x = cc_find(a.parent, c), y = cc_find(a.parent, d);
+        while (x != y) {  // max(x, y) falls strictly with every turn
+            const int hi = x > y ? x : y, lo = x > y ? y : x;
+            const int old = atomicMin(a.parent + hi, lo);
+            if (old == hi || old == lo) break;  // hi was a root and hangs under lo now, or did already
+            x = cc_find(a.parent, old);         // hi hangs under min(old, lo): unite the other one with it
+            y = lo;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) label_flatten_kernel(LabelArgs a) {
+    const int c = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (c >= a.C) return;
+    // a root keeps itself; any other cell is overwritten by a smaller value of its own tree (another lane that
+    // reads it meanwhile sees the old or the new one: both are its ancestors; the store is atomic like the chase's
+    // loads, so the two do not race).  Class 0 is never part of a chain.
+    __hip_atomic_store(a.parent + c, a.cls[c] == 0 ? -1 : cc_find(a.parent, c), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ void __launch_bounds__(kBlock) label_check_kernel(LabelArgs a) {
+    const int c = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (c >= a.C) return;
+    const int k = a.cls[c];
+    if (k == 0) return;
+    const int p = a.parent[c];
+    bool bad = (unsigned)p > (unsigned)c || a.parent[p < 0 ? c : p] != p;
+    const int* r = a.cellrec + (int64_t)c * a.rec_ints;
+    int n = r[0];
+    if (n > a.maxv) n = a.maxv;
+    for (int j = 0; j < n; ++j) {
+        const int d = r[1 + a.maxv + j];
+        if ((unsigned)d >= (unsigned)a.C || a.cls[d] != k) continue;
+        bad = bad || a.parent[d] != p;
+    }
+    if (bad) *a.flag = 1;
+}
+
+// before another round: class-0 cells back to their own parent (the hook kernel never reads them, the chase
+// never reaches them; this keeps invariant (a) literally true)
+__global__ void __launch_bounds__(kBlock) label_reopen_kernel(LabelArgs a) {
+    const int c = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (c < a.C && a.cls[c] == 0) a.parent[c] = c;
+}
+
+struct EddyTableArgs {
+    int E, L, l;
+    const int* offs;     // [E + 1]
+    const int* members;  // ascending within an eddy
+    const int* cls;
+    const double* area;
+    const double* vort;
+    const double* ow;
+    const double4* cxyz;
+    int* root; int* n_cells; int* polarity; int* core_cell;
+    double* sum_area; double* circulation; double* ow_min; double* centre;  // centre [E][3]
+};
+
+// one lane per eddy walks its members in ascending cell order: the order fixes the bits
+__global__ void __launch_bounds__(kBlock) eddy_table_kernel(EddyTableArgs a) {
+    const int e = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (e >= a.E) return;
+    const int b = a.offs[e], end = a.offs[e + 1];
+    double A = 0.0, G = 0.0, Sx = 0.0, Sy = 0.0, Sz = 0.0, wmin = INFINITY;
+    int core = -1;
+    for (int i = b; i < end; ++i) {
+        const int c = a.members[i];
+        const double ar = a.area[c];
+        const int64_t o = (int64_t)c * a.L + a.l;
+        const double w = a.ow[o];
+        const double4 q = a.cxyz[c];
+        A += ar;
+        G += a.vort[o] * ar;
+        Sx += ar * q.x;
+        Sy += ar * q.y;
+        Sz += ar * q.z;
+        if (w < wmin) { wmin = w; core = c; }
+    }
+    const double nrm = sqrt((Sx * Sx + Sy * Sy) + Sz * Sz);
+    const int first = end > b ? a.members[b] : -1;
+    a.root[e] = first;
+    a.n_cells[e] = end - b;
+    a.polarity[e] = first >= 0 ? a.cls[first] : 0;
+    a.core_cell[e] = core;
+    a.sum_area[e] = A;
+    a.circulation[e] = G;
+    a.ow_min[e] = wmin;
+    a.centre[3 * e] = Sx / nrm;
+    a.centre[3 * e + 1] = Sy / nrm;
+    a.centre[3 * e + 2] = Sz / nrm;
+}
+
+struct DevBuf {  // a temporary device allocation of one call
+    void* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+    template <typename T> T* as() const { return static_cast<T*>(p); }
+};
+
+}  // namespace
+
+extern "C" {
+
+mops_status mops_cell_area(const mops_mesh* mesh, double* d_area, void* stream) {
+    if (!mesh || !d_area) return fail(MOPS_ERR_INVALID, "mops_cell_area: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    cell_area_kernel<<<grid_for(mesh->C), kBlock, 0, s>>>(mesh->C, mesh->rec_ints, mesh->maxv, mesh->d_cellrec,
+                                                          mesh->d_cxyz, mesh->d_vxyz, d_area);
+    HIP_TRY(hipGetLastError());
+    return MOPS_OK;
+}
+
+mops_status mops_eddy_classify(const mops_mesh* mesh, const double* d_okubo_weiss, const double* d_vorticity,
+                               int32_t level, double threshold, int32_t* d_class, void* stream) {
+    if (!mesh || !d_okubo_weiss || !d_vorticity || !d_class)
+        return fail(MOPS_ERR_INVALID, "mops_eddy_classify: null argument");
+    if (level < 0 || level >= mesh->L) return fail(MOPS_ERR_INVALID, "mops_eddy_classify: level outside the levels");
+    hipStream_t s = (hipStream_t)stream;
+    eddy_classify_kernel<<<grid_for(mesh->C), kBlock, 0, s>>>(mesh->C, mesh->L, level, d_okubo_weiss, d_vorticity,
+                                                              threshold, d_class);
+    HIP_TRY(hipGetLastError());
+    return MOPS_OK;
+}
+
+mops_status mops_label_components(const mops_mesh* mesh, const int32_t* d_class, int32_t* d_label, int32_t* h_rounds,
+                                  void* stream) {
+    if (!mesh || !d_class || !d_label) return fail(MOPS_ERR_INVALID, "mops_label_components: null argument");
+    if (h_rounds) *h_rounds = 0;
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf flag;
+    HIP_TRY(flag.alloc(sizeof(int)));
+    LabelArgs a{};
+    a.C = (int)mesh->C; a.rec_ints = mesh->rec_ints; a.maxv = mesh->maxv;  // C <= 2^30 (mops_mesh_create)
+    a.cellrec = mesh->d_cellrec; a.cls = d_class; a.parent = d_label; a.flag = flag.as<int>();
+    const unsigned grid = grid_for(mesh->C);
+    if (grid == 0) return MOPS_OK;
+    label_init_kernel<<<grid, kBlock, 0, s>>>(a.C, a.parent);
+    HIP_TRY(hipGetLastError());
+    // By invariant (c) the hook kernel leaves one tree per component, so round 1's check finds nothing and the
+    // entry returns there: rounds 2 .. kLabelMaxRounds and label_reopen_kernel are a safety net that no correct
+    // run, and therefore no test, reaches.  They turn a defect in the hook kernel into more work or an error.
+    for (int round = 1; round <= kLabelMaxRounds; ++round) {
+        HIP_TRY(hipMemsetAsync(a.flag, 0, sizeof(int), s));
+        label_hook_kernel<<<grid, kBlock, 0, s>>>(a);
+        label_flatten_kernel<<<grid, kBlock, 0, s>>>(a);
+        label_check_kernel<<<grid, kBlock, 0, s>>>(a);
+        HIP_TRY(hipGetLastError());
+        int h_flag = 0;
+        HIP_TRY(hipMemcpyAsync(&h_flag, a.flag, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (h_rounds) *h_rounds = round;
+        if (!h_flag) return MOPS_OK;
+        label_reopen_kernel<<<grid, kBlock, 0, s>>>(a);
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return fail(MOPS_ERR_UNSUPPORTED, "mops_label_components: not converged after " +
+                                          std::to_string(kLabelMaxRounds) + " rounds");
+}
+
+mops_status mops_eddy_count(const mops_mesh* mesh, const int32_t* d_label, int32_t min_cells, int32_t* d_eddy_of_cell,
+                            int64_t* h_n_eddies, void* stream) {
+    if (!mesh || !d_label || !d_eddy_of_cell || !h_n_eddies)
+        return fail(MOPS_ERR_INVALID, "mops_eddy_count: null argument");
+    if (min_cells < 1) return fail(MOPS_ERR_INVALID, "mops_eddy_count: min_cells < 1");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t C = mesh->C;
+    std::vector<int32_t> lab((size_t)C), cnt((size_t)C, 0);
+    HIP_TRY(hipMemcpyAsync(lab.data(), d_label, (size_t)C * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int64_t c = 0; c < C; ++c) {
+        const int32_t r = lab[c];
+        if (r < -1 || r > c || (r >= 0 && lab[r] != r))
+            return fail(MOPS_ERR_INVALID, "mops_eddy_count: not a label array (a label is -1 or a root cell <= its cell)");
+        if (r >= 0) ++cnt[r];
+    }
+    int64_t E = 0;
+    for (int64_t c = 0; c < C; ++c)  // cnt becomes the eddy index of a root, ascending by root
+        cnt[c] = (lab[c] == c && cnt[c] >= min_cells) ? (int32_t)E++ : -1;
+    for (int64_t c = 0; c < C; ++c) lab[c] = lab[c] >= 0 ? cnt[lab[c]] : -1;
+    HIP_TRY(hipMemcpyAsync(d_eddy_of_cell, lab.data(), (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));  // lab leaves scope
+    *h_n_eddies = E;
+    return MOPS_OK;
+}
+
+mops_status mops_eddy_table(const mops_mesh* mesh, const int32_t* d_eddy_of_cell, int64_t n_eddies,
+                            const int32_t* d_class, const double* d_area, const double* d_vorticity,
+                            const double* d_okubo_weiss, int32_t level, int32_t* h_root, int32_t* h_n_cells,
+                            int32_t* h_polarity, int32_t* h_core_cell, double* h_area, double* h_circulation,
+                            double* h_ow_min, double* h_centre, void* stream) {
+    if (!mesh || !d_eddy_of_cell || !d_class || !d_area || !d_vorticity || !d_okubo_weiss)
+        return fail(MOPS_ERR_INVALID, "mops_eddy_table: null argument");
+    if (level < 0 || level >= mesh->L) return fail(MOPS_ERR_INVALID, "mops_eddy_table: level outside the levels");
+    if (n_eddies < 0 || n_eddies > mesh->C) return fail(MOPS_ERR_INVALID, "mops_eddy_table: n_eddies out of range");
+    if (n_eddies == 0) return MOPS_OK;
+    if (!h_root || !h_n_cells || !h_polarity || !h_core_cell || !h_area || !h_circulation || !h_ow_min || !h_centre)
+        return fail(MOPS_ERR_INVALID, "mops_eddy_table: null output");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t C = mesh->C;
+    const int E = (int)n_eddies;
+    std::vector<int32_t> eoc((size_t)C), offs((size_t)E + 1, 0);
+    HIP_TRY(hipMemcpyAsync(eoc.data(), d_eddy_of_cell, (size_t)C * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int64_t c = 0; c < C; ++c) {
+        if (eoc[c] < -1 || eoc[c] >= E) return fail(MOPS_ERR_INVALID, "mops_eddy_table: eddy index out of range");
+        if (eoc[c] >= 0) ++offs[eoc[c] + 1];
+    }
+    for (int e = 0; e < E; ++e) offs[e + 1] += offs[e];
+    std::vector<int32_t> members((size_t)offs[E]), fill(offs.begin(), offs.end() - 1);
+    for (int64_t c = 0; c < C; ++c)  // ascending c: every eddy's members come out in ascending cell order
+        if (eoc[c] >= 0) members[fill[eoc[c]]++] = (int32_t)c;
+    DevBuf d_offs, d_mem, d_int, d_dbl;
+    HIP_TRY(d_offs.alloc(offs.size() * sizeof(int32_t)));
+    HIP_TRY(d_mem.alloc(members.size() * sizeof(int32_t)));
+    HIP_TRY(d_int.alloc((size_t)E * 4 * sizeof(int32_t)));
+    HIP_TRY(d_dbl.alloc((size_t)E * 6 * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(d_offs.p, offs.data(), offs.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_mem.p, members.data(), members.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    EddyTableArgs a{};
+    a.E = E; a.L = mesh->L; a.l = level;
+    a.offs = d_offs.as<int>(); a.members = d_mem.as<int>();
+    a.cls = d_class; a.area = d_area; a.vort = d_vorticity; a.ow = d_okubo_weiss; a.cxyz = mesh->d_cxyz;
+    a.root = d_int.as<int>(); a.n_cells = a.root + E; a.polarity = a.root + 2 * (size_t)E;
+    a.core_cell = a.root + 3 * (size_t)E;
+    a.sum_area = d_dbl.as<double>(); a.circulation = a.sum_area + E; a.ow_min = a.sum_area + 2 * (size_t)E;
+    a.centre = a.sum_area + 3 * (size_t)E;
+    eddy_table_kernel<<<grid_for(E), kBlock, 0, s>>>(a);
+    HIP_TRY(hipGetLastError());
+    const size_t ib = (size_t)E * sizeof(int32_t), db = (size_t)E * sizeof(double);
+    HIP_TRY(hipMemcpyAsync(h_root, a.root, ib, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_n_cells, a.n_cells, ib, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_polarity, a.polarity, ib, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_core_cell, a.core_cell, ib, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_area, a.sum_area, db, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_circulation, a.circulation, db, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_ow_min, a.ow_min, db, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_centre, a.centre, 3 * db, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return MOPS_OK;
+}
+
+}  // extern "C"
+
+// ===========================================================================
 // colour mapping: MOPS::SaveToPNG's pixel work (src/Common/ImageBuffer.hpp:91-136) for an [H][W][4]
 // float64 device image, channels together.  Two passes over the image: the float range of every channel
 // (per-block partials, then one block reduces them -- min / max do not depend on the order, so no atomics and

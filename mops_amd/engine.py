@@ -1090,6 +1090,207 @@ def velocity_gradient(mesh: DeviceMesh, field: DeviceField, which=EDDY_FIELDS, v
     return out
 
 
+def _census_stream(stream):
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    return dev, (stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _cell_tensor(mesh: DeviceMesh, t, name: str, dtype, per_level: bool = False):
+    import torch
+    n = mesh.nCells * (mesh.nVertLevels if per_level else 1)
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() == n):
+        shape = "[nCells, nVertLevels]" if per_level else "[nCells]"
+        raise ValueError(f"{name}: expected a contiguous {dtype} CUDA tensor {shape}")
+    return C.c_void_p(t.data_ptr())
+
+
+def cell_area(mesh: DeviceMesh, stream=None):
+    """The planar area of every cell in its centre's east / north frame (mops_cell_area: half the magnitude of
+    the velocity-gradient operator's ``A2``): a float64 CUDA tensor [nCells], NaN where that operator refuses
+    the cell."""
+    import torch
+    dev, h = _census_stream(stream)
+    out = torch.empty((mesh.nCells,), dtype=torch.float64, device=dev)
+    L.check(L.load().mops_cell_area(mesh.handle, C.c_void_p(out.data_ptr()), _stream_handle(h)), "mops_cell_area")
+    return out
+
+
+def eddy_classify(mesh: DeviceMesh, okubo_weiss, vorticity, layer: int, threshold: float, stream=None):
+    """+1 / -1 / 0 per cell at ``layer`` (mops_eddy_classify): Okubo-Weiss below ``threshold`` and vorticity
+    positive / negative / anything else (NaN is class 0).  The arrays are ``velocity_gradient``'s
+    [nCells, nVertLevels] tensors; returns an int32 CUDA tensor [nCells]."""
+    import torch
+    import math
+    layer = int(layer)
+    if not 0 <= layer < mesh.nVertLevels:
+        raise ValueError(f"layer {layer} outside the {mesh.nVertLevels} levels")
+    if not math.isfinite(float(threshold)):
+        raise ValueError(f"threshold {threshold!r} is not finite")
+    ow = _cell_tensor(mesh, okubo_weiss, "okubo_weiss", torch.float64, per_level=True)
+    vo = _cell_tensor(mesh, vorticity, "vorticity", torch.float64, per_level=True)
+    dev, h = _census_stream(stream)
+    out = torch.empty((mesh.nCells,), dtype=torch.int32, device=dev)
+    L.check(L.load().mops_eddy_classify(mesh.handle, ow, vo, layer, float(threshold), C.c_void_p(out.data_ptr()),
+                                        _stream_handle(h)), "mops_eddy_classify")
+    return out
+
+
+def label_components(mesh: DeviceMesh, classes, return_rounds: bool = False, stream=None):
+    """Connected components of an int32 CUDA class array [nCells] over the cellsOnCell graph
+    (mops_label_components): cells are joined across an edge when their classes are equal and not 0.  Returns an
+    int32 CUDA tensor [nCells]: the smallest cell index of the cell's component, -1 for class 0.  The call
+    synchronises the stream (the host decides convergence between rounds); ``return_rounds``: also the rounds
+    used."""
+    import torch
+    cls = _cell_tensor(mesh, classes, "classes", torch.int32)
+    dev, h = _census_stream(stream)
+    out = torch.empty((mesh.nCells,), dtype=torch.int32, device=dev)
+    rounds = C.c_int32(0)
+    L.check(L.load().mops_label_components(mesh.handle, cls, C.c_void_p(out.data_ptr()), C.byref(rounds),
+                                           _stream_handle(h)), "mops_label_components")
+    return (out, int(rounds.value)) if return_rounds else out
+
+
+EDDY_COLUMNS = ("root", "n_cells", "polarity", "core_cell", "area", "circulation", "ow_min", "centre")
+
+
+def eddy_table(mesh: DeviceMesh, labels, classes, area, vorticity, okubo_weiss, layer: int, min_cells: int = 1,
+               stream=None):
+    """Membership and the census table (mops_eddy_count, mops_eddy_table) from ``label_components``'s labels:
+    components of fewer than ``min_cells`` cells are dropped, the rest numbered in ascending order of their root
+    cell.  Returns (eddy_of_cell: int32 CUDA tensor [nCells], the eddy index or -1; table: a dict of numpy
+    arrays [E] -- ``EDDY_COLUMNS``, ``centre`` being [E, 3]).  Every sum runs over an eddy's cells in ascending
+    cell index.  Both entries synchronise the stream."""
+    import torch
+    layer, min_cells = int(layer), int(min_cells)
+    if not 0 <= layer < mesh.nVertLevels:
+        raise ValueError(f"layer {layer} outside the {mesh.nVertLevels} levels")
+    if min_cells < 1:
+        raise ValueError(f"min_cells {min_cells} < 1")
+    lab = _cell_tensor(mesh, labels, "labels", torch.int32)
+    cls = _cell_tensor(mesh, classes, "classes", torch.int32)
+    ar = _cell_tensor(mesh, area, "area", torch.float64)
+    vo = _cell_tensor(mesh, vorticity, "vorticity", torch.float64, per_level=True)
+    ow = _cell_tensor(mesh, okubo_weiss, "okubo_weiss", torch.float64, per_level=True)
+    dev, h = _census_stream(stream)
+    lib = L.load()
+    eoc = torch.empty((mesh.nCells,), dtype=torch.int32, device=dev)
+    n = C.c_int64(0)
+    L.check(lib.mops_eddy_count(mesh.handle, lab, min_cells, C.c_void_p(eoc.data_ptr()), C.byref(n),
+                                _stream_handle(h)), "mops_eddy_count")
+    E = int(n.value)
+    t = {k: np.empty((E,), dtype=np.int32) for k in EDDY_COLUMNS[:4]}
+    t.update({k: np.empty((E,), dtype=np.float64) for k in EDDY_COLUMNS[4:7]})
+    t["centre"] = np.empty((E, 3), dtype=np.float64)
+    L.check(lib.mops_eddy_table(mesh.handle, C.c_void_p(eoc.data_ptr()), E, cls, ar, vo, ow, layer,
+                                *[_ptr(t[k]) for k in EDDY_COLUMNS], _stream_handle(h)), "mops_eddy_table")
+    return eoc, t
+
+
+def eddy_lat_lon_radius(centre, area):
+    """(lat, lon) in degrees of the unit vectors ``centre`` [E, 3] and the radius of the circle of ``area``,
+    with numpy on the host: lat = degrees(arcsin(z)), lon = degrees(arctan2(y, x)), radius = sqrt(area / pi)."""
+    centre = np.asarray(centre, dtype=np.float64).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        lat = np.degrees(np.arcsin(centre[:, 2]))
+        lon = np.degrees(np.arctan2(centre[:, 1], centre[:, 0]))
+        radius = np.sqrt(np.asarray(area, dtype=np.float64) / np.pi)
+    return lat, lon, radius
+
+
+class EddyCensus:
+    """The result of ``eddy_census``: ``threshold`` (the Okubo-Weiss threshold used), ``labels`` (int32 CUDA
+    tensor [nCells]: the eddy index of every cell or -1), ``table`` (numpy columns ``EDDY_COLUMNS`` plus ``lat``,
+    ``lon`` in degrees and ``radius``, one row per eddy), ``classes`` and ``components`` (the int32 CUDA class and
+    component-root arrays behind them), ``rounds`` (labelling rounds used) and ``n_eddies``."""
+
+    def __init__(self, mesh, field, layer, threshold, classes, components, rounds, labels, table):
+        self.mesh, self.field, self.layer = mesh, field, layer
+        self.threshold, self.classes, self.components, self.rounds = threshold, classes, components, rounds
+        self.labels, self.table = labels, table
+        self.n_eddies = len(table["root"])
+
+    def cells(self, e: int):
+        """The member cells of eddy ``e`` in ascending order: an int64 CUDA tensor."""
+        import torch
+        e = int(e)
+        if not 0 <= e < self.n_eddies:
+            raise ValueError(f"eddy {e} outside the {self.n_eddies} eddies")
+        return torch.nonzero(self.labels == e).reshape(-1)
+
+    def image(self, width: int, height: int, lat_range, lon_range, return_cells: bool = False, stream=None):
+        """The label image on a window: a float64 CUDA tensor [height, width, 4] = {eddy index, polarity, 0, 1}
+        from the cell map of ``remap_fixed_layer`` at the census layer.  Channels 0 and 1 are NaN where the
+        fixed-layer image is NaN or the pixel's cell is in no eddy, so it overlays every other image of the
+        window.  ``return_cells``: also the int32 cell map and the fixed-layer image."""
+        import torch
+        layer_image, cells = remap_fixed_layer(self.mesh, self.field, width, height, lat_range, lon_range,
+                                               float(self.layer), return_cells=True, stream=stream)
+        with (torch.cuda.stream(_torch_stream(stream)) if stream is not None else _nullcontext()):
+            inside = (cells >= 0) & (cells < self.mesh.nCells) & ~torch.isnan(layer_image[..., 0])
+            c = torch.where(inside, cells, torch.zeros_like(cells)).long()
+            e = self.labels[c]
+            ok = inside & (e >= 0)
+            nan = torch.full_like(layer_image[..., 0], float("nan"))
+            out = torch.empty_like(layer_image)
+            out[..., 0] = torch.where(ok, e.double(), nan)
+            out[..., 1] = torch.where(ok, self.classes[c].double(), nan)
+            out[..., 2] = 0.0
+            out[..., 3] = 1.0
+        return (out, cells, layer_image) if return_cells else out
+
+
+def eddy_census(mesh: DeviceMesh, field: DeviceField, layer: int = 0, k_sigma: float = 0.2, threshold=None,
+                min_cells: int = 4, gradient=None):
+    """The eddies of one layer as objects: the cells whose Okubo-Weiss parameter lies below ``threshold``, split
+    by the sign of their vorticity, grouped into connected components of the mesh (mops_eddy_classify,
+    mops_label_components), and one table row per component of at least ``min_cells`` cells (mops_eddy_table).
+
+    ``threshold``: as given, else ``-k_sigma * sigma`` with sigma the population standard deviation of the
+    layer's finite Okubo-Weiss values (torch, FP64); the value used is ``.threshold``.  ``gradient``: a dict
+    with ``velocity_gradient``'s "vorticity" and "okubo_weiss" tensors to reuse instead of computing them.
+    ValueError before any launch for a layer outside the levels, ``min_cells < 1``, a non-finite threshold or a
+    ``gradient`` of the wrong shape.  Returns an ``EddyCensus``; on torch's current stream, which it
+    synchronises."""
+    import math
+    import torch
+    layer, min_cells = int(layer), int(min_cells)
+    if not 0 <= layer < mesh.nVertLevels:
+        raise ValueError(f"layer {layer} outside the {mesh.nVertLevels} levels")
+    if min_cells < 1:
+        raise ValueError(f"min_cells {min_cells} < 1")
+    if threshold is not None and not math.isfinite(float(threshold)):
+        raise ValueError(f"threshold {threshold!r} is not finite")
+    if threshold is None and not math.isfinite(float(k_sigma)):
+        raise ValueError(f"k_sigma {k_sigma!r} is not finite")
+    if gradient is not None:
+        try:
+            vort, ow = gradient["vorticity"], gradient["okubo_weiss"]
+        except (KeyError, TypeError):
+            raise ValueError("gradient: expected a dict with 'vorticity' and 'okubo_weiss'") from None
+        for name, t in (("vorticity", vort), ("okubo_weiss", ow)):
+            _cell_tensor(mesh, t, f"gradient[{name!r}]", torch.float64, per_level=True)
+            if tuple(t.shape) != (mesh.nCells, mesh.nVertLevels):
+                raise ValueError(f"gradient[{name!r}]: expected shape [nCells, nVertLevels], not {tuple(t.shape)}")
+    else:
+        g = velocity_gradient(mesh, field, which=("vorticity", "okubo_weiss"))
+        vort, ow = g["vorticity"], g["okubo_weiss"]
+    if threshold is None:
+        col = ow[:, layer]
+        fin = col[torch.isfinite(col)]
+        sigma = float(torch.std(fin, unbiased=False)) if fin.numel() else float("nan")
+        threshold = -float(k_sigma) * sigma
+        if not math.isfinite(threshold):
+            raise ValueError("no finite Okubo-Weiss value in the layer: no threshold")
+    threshold = float(threshold)
+    classes = eddy_classify(mesh, ow, vort, layer, threshold)
+    components, rounds = label_components(mesh, classes, return_rounds=True)
+    labels, table = eddy_table(mesh, components, classes, cell_area(mesh), vort, ow, layer, min_cells)
+    table["lat"], table["lon"], table["radius"] = eddy_lat_lon_radius(table["centre"], table["area"])
+    return EddyCensus(mesh, field, layer, threshold, classes, components, rounds, labels, table)
+
+
 def _vertex_attr_ptr(mesh: DeviceMesh, t, name: str):
     if not (t.is_cuda and t.dtype.is_floating_point and t.element_size() == 8 and t.is_contiguous()
             and t.numel() == mesh.nVertices * mesh.nVertLevels):

@@ -33,6 +33,8 @@ and, beyond the pybind module, the image output of the reference's C++ side:
     MOPS_SectionTransport(image, config)       extension: its volume transport in Sverdrups
     MOPS_RunEddyMap(config)                    extension: relative vorticity and Okubo-Weiss at FixedDepth,
                                                (H, W, 4) float64 {vorticity, okubo_weiss, 0, 1}
+    MOPS_RunEddyCensus(config)                 extension: the eddies of layer FixedLayer as a list of dicts and
+                                               their label image (H, W, 4) float64 {eddy index, polarity, 0, 1}
 
 Every trajectory and every image goes through the HIP engine
 (``engine.run_trajectories`` / ``engine.remap_fixed_depth`` /
@@ -329,6 +331,10 @@ class VisualizationSettings:
         # the waypoints (lat, lon) in degrees of MOPS_RunRemappingSection's great-circle path (this engine's
         # extension); its rows span DepthRange, or the reference bottom depths while that is (0, 0)
         self.SectionPath = []
+        # MOPS_RunEddyCensus (this engine's extension): the Okubo-Weiss threshold in standard deviations of the
+        # layer (the census takes -EddyThreshold * sigma) and the fewest cells an eddy may have
+        self.EddyThreshold = 0.2
+        self.EddyMinCells = 4
 
     def __setattr__(self, name, value):
         if name in ("imageSize", "LatRange", "LonRange", "DepthRange"):
@@ -705,6 +711,65 @@ def _eddy_device(config: VisualizationSettings):
                                       vertex_attrs=_eddy_vertex_attrs(_app.front_id),
                                       layer_rule=getattr(config, "layerRule", "reference"))
         return images[1]
+
+
+EDDY_KEYS = ("index", "lat", "lon", "radius", "area", "polarity", "circulation", "n_cells", "root", "core_cell",
+             "ow_min", "centre")
+
+
+def _census_layer(config, n_levels: int) -> int:
+    """``config.FixedLayer`` as MOPS_RunRemappingFixedLayer reads it: truncated toward zero and clamped into the
+    levels (a NaN gives layer 0)."""
+    fl = float(config.FixedLayer)
+    return 0 if not fl >= 1.0 else (n_levels - 1 if fl >= n_levels else int(fl))
+
+
+def _census_device(config: VisualizationSettings):
+    """MOPS_RunEddyCensus where the kernels wrote it: (engine.EddyCensus, its label image as a float64 CUDA
+    tensor [H, W, 4]), or None after Error() for invalid inputs."""
+    with _Timer("GPUKernel::EddyCensus", "GPUKernel"):
+        w, h = (int(config.imageSize[0]), int(config.imageSize[1])) if config is not None else (0, 0)
+        if config is None or _app.mesh is None or _app.front is None or w <= 0 or h <= 0:
+            _error("[MI355X::EddyCensus] invalid inputs")
+            return None
+        try:
+            k_sigma, min_cells = float(config.EddyThreshold), int(config.EddyMinCells)
+        except (TypeError, ValueError):
+            k_sigma, min_cells = float("nan"), 0
+        if not np.isfinite(k_sigma) or min_cells < 1:
+            _error("[MI355X::EddyCensus] EddyThreshold must be finite and EddyMinCells at least 1")
+            return None
+        layer = _census_layer(config, _app.mesh.nVertLevels)
+        try:
+            census = _E.eddy_census(_app.mesh, _app.front, layer=layer, k_sigma=k_sigma, min_cells=min_cells)
+        except ValueError as e:  # (a layer without a finite Okubo-Weiss value)
+            _error(f"[MI355X::EddyCensus] {e}")
+            return None
+        return census, census.image(w, h, config.LatRange, config.LonRange)
+
+
+def _census_rows(census):
+    t = census.table
+    return [{"index": e, "lat": float(t["lat"][e]), "lon": float(t["lon"][e]), "radius": float(t["radius"][e]),
+             "area": float(t["area"][e]), "polarity": int(t["polarity"][e]),
+             "circulation": float(t["circulation"][e]), "n_cells": int(t["n_cells"][e]), "root": int(t["root"][e]),
+             "core_cell": int(t["core_cell"][e]), "ow_min": float(t["ow_min"][e]),
+             "centre": tuple(float(x) for x in t["centre"][e])} for e in range(census.n_eddies)]
+
+
+def MOPS_RunEddyCensus(config: VisualizationSettings):
+    """Extension (no reference counterpart): the eddies of the active front solution at layer
+    ``config.FixedLayer`` (clamped as ``MOPS_RunRemappingFixedLayer`` clamps it) -- the connected sets of at
+    least ``config.EddyMinCells`` cells whose Okubo-Weiss parameter lies below ``-config.EddyThreshold`` standard
+    deviations of the layer, split by the sign of their vorticity (``engine.eddy_census``).  Returns
+    ``(eddies, image)``: a list of dicts (``EDDY_KEYS``: lat / lon in degrees, radius in metres, area in square
+    metres, polarity +1 / -1 the sign of the vorticity, circulation in m^2/s) and the label image [H, W, 4] float64
+    {eddy index, polarity, 0, 1} on the config's window, NaN in channels 0 and 1 outside every eddy.  Invalid
+    inputs answer Error() and return ([], [])."""
+    got = _census_device(config)
+    if got is None:
+        return [], []
+    return _census_rows(got[0]), got[1].cpu().numpy()
 
 
 def MOPS_RunRemappingFixedLayer(config: VisualizationSettings):
