@@ -560,10 +560,16 @@ class ParticleSet:
             back = (L.PermArray * len(names))(*[desc(self._spare[k], getattr(self, k), k, e) for k, e in names])
             L.check(lib.mops_permute_arrays(n, None, len(names), back, _stream_handle(s)), "mops_permute_arrays")
 
-    def original(self, t):
-        """A per-slot tensor back in the particles' seed order."""
-        out = self.torch.empty_like(t)
-        out[self.ids.long()] = t
+    def original(self, t, stream=None):
+        """A per-slot tensor back in the particles' seed order.  Torch work (an allocation and an indexed store) on
+        ``stream`` -- None, a raw handle or a torch stream; default torch's current one -- without a host
+        synchronisation: ``t`` and the slot ids must be ordered on that stream, as an ``advance`` / ``compact``
+        there leaves them.  The result is allocated under that stream, so it may be dropped while the stream still
+        reads it."""
+        torch = self.torch
+        with (torch.cuda.stream(_torch_stream(stream)) if stream is not None else _nullcontext()):
+            out = torch.empty_like(t)
+            out[self.ids.long()] = t
         return out
 
     def compact(self, lo: int, hi: int, stream, records_written: int, attr_slots_written: int | None = None):
@@ -891,7 +897,8 @@ class ParticleSet:
 
     def last_points(self, stream=None):
         """Each particle's cleaned last point in seed order (mops_traj_last_points): finalize's lastPoint
-        without the lines."""
+        without the lines.  One launch on ``stream`` (default the null stream) without a host synchronisation;
+        no torch work beyond allocating the result under torch's current stream."""
         torch = self.torch
         last = torch.empty((self.n, 3), dtype=torch.float64, device=self.seeds.device)
         L.check(L.load().mops_traj_last_points(self.n, self.K, C.c_void_p(self.seeds.data_ptr()),
@@ -1526,6 +1533,8 @@ class DensityMap:
         return self.value if self.kind == L.MOPS_DENSITY_VALUES else None
 
     def reset(self):
+        """Zero the accumulator: a torch fill on torch's *current* stream (there is no ``stream=``), without a
+        host synchronisation.  A caller that accumulates on another stream orders the two itself."""
         self.accum.zero_()
 
     def _stream(self, stream):
@@ -1635,19 +1644,27 @@ class FlowMapLattice:
         """The FTLE image (mops_ftle_image) of ``last_points`` [height * width, 3] in seed order (CUDA tensor or
         host array); ``death`` [height * width] int32, >= 0 where the particle died (None: a particle counts as
         dead only through a zero or non-finite last point); ``horizon`` > 0, the integration time in the unit the
-        exponent is wanted per (days throughout the Python layer).  On ``stream`` (default torch's current one),
-        without a host synchronisation."""
+        exponent is wanted per (days throughout the Python layer).
+
+        Everything runs on ``stream`` (None, a raw handle or a torch stream; default torch's current one): the
+        kernel, and before it the torch copies that bring an input into the kernel's form (a non-contiguous
+        tensor, a ``death`` of another integer type, a tensor of another device).  CUDA inputs must be ordered on
+        that stream by the caller; with them the call does not synchronise the host.  A host array is uploaded
+        with torch's blocking copy, which waits for the stream.  The copies are allocated under ``stream``, so
+        dropping them here while the kernel may still read them is safe; the image is allocated under torch's
+        current stream, as every entry's result is."""
         torch = self.torch
         horizon = float(horizon)
         if not (np.isfinite(horizon) and horizon > 0.0):
             raise ValueError("ftle: the horizon must be finite and positive")
-        last = torch.as_tensor(last_points, dtype=torch.float64).to(self.device).contiguous()
+        with (torch.cuda.stream(_torch_stream(stream)) if stream is not None else _nullcontext()):
+            last = torch.as_tensor(last_points, dtype=torch.float64).to(self.device).contiguous()
+            if death is not None:
+                death = torch.as_tensor(death).to(device=self.device, dtype=torch.int32).contiguous()
         if last.numel() != 3 * self.n:
             raise ValueError(f"ftle: last_points must be [{self.n}, 3]")
-        if death is not None:
-            death = torch.as_tensor(death).to(device=self.device, dtype=torch.int32).contiguous()
-            if death.numel() != self.n:
-                raise ValueError(f"ftle: death must be [{self.n}]")
+        if death is not None and death.numel() != self.n:
+            raise ValueError(f"ftle: death must be [{self.n}]")
         with torch.cuda.device(self.device):
             img = torch.empty((self.height, self.width, 4), dtype=torch.float64, device=self.device)
             L.check(L.load().mops_ftle_image(C.byref(self.cfg), C.c_void_p(self.seeds.data_ptr()),
@@ -1659,8 +1676,13 @@ class FlowMapLattice:
 
     def ftle_from(self, ps: "ParticleSet", horizon: float, stream=None):
         """The FTLE image of a ParticleSet seeded with ``seeds``: its ``last_points()`` and its death steps back
-        in seed order."""
+        in seed order.  All of it -- the last points, the reordering of the death steps (torch) and the kernel --
+        runs on ``stream`` (default torch's current one) without a host synchronisation, so the call may follow
+        the set's ``advance`` / ``compact`` on that stream directly."""
         if ps.n != self.n:
             raise ValueError("ftle_from: the particle set is not this lattice's")
         h = self._stream(stream)
-        return self.ftle(ps.last_points(stream=h), ps.original(ps.death), horizon, stream=h)
+        last = ps.last_points(stream=h)
+        if stream is not None:  # allocated under torch's current stream and released here while `stream` reads it
+            last.record_stream(_torch_stream(stream))
+        return self.ftle(last, ps.original(ps.death, stream=h), horizon, stream=h)
