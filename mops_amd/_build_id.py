@@ -15,9 +15,11 @@ import os
 _PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(_PKG)
 CSRC = os.path.join(_PKG, "csrc")
-SOURCES = tuple(os.path.join(CSRC, f) for f in ("mops_engine.hip", "mops_api.cpp", "mops_io.cpp", "mops_netcdf.cpp"))
+SOURCES = tuple(os.path.join(CSRC, f) for f in ("mops_engine.hip", "mops_analysis.hip", "mops_api.cpp", "mops_io.cpp",
+                                                "mops_netcdf.cpp"))
 HEADERS = tuple(os.path.join(ROOT, "include", f) for f in ("mops_traj.h", "mops_io.h", "mops_netcdf.h",
                                                            "mops_viridis.h", os.path.join("mops", "MOPS.h")))
+HEADERS += (os.path.join(CSRC, "mops_internal.h"),)  # private to the two .hip files, hashed like the public ones
 # bit-parity with the reference's x86-64 -O2 build: no FMA contraction
 HIPCC_FLAGS = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off")
 MARKER = "mops-build-id:"

@@ -18,10 +18,6 @@ import numpy as np
 from . import _lib as L
 
 
-def _nullcontext():
-    return contextlib.nullcontext()
-
-
 def _ptr(a: np.ndarray | None):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -42,6 +38,45 @@ def _torch_stream(stream):
     if isinstance(stream, int):
         return torch.cuda.ExternalStream(stream)
     return stream
+
+
+# The stream rule of the analysis and imaging entries: the library call and the temporaries' torch work run on
+# ``stream`` when one is given, else on torch's current stream; results are allocated under torch's current stream.
+def _current_or(stream, dev=None):
+    """``stream``, or torch's current stream on ``dev`` (None: the current device): what an entry hands on as the
+    ``stream=`` of the entries it calls, where None would mean stream 0."""
+    import torch
+    return stream if stream is not None else torch.cuda.current_stream(dev)
+
+
+def _stream_or_current(stream, dev=None) -> C.c_void_p:
+    """... as the handle the library takes."""
+    return _stream_handle(_current_or(stream, dev))
+
+
+def _on_stream(stream):
+    """The context an entry's torch work runs in: ``stream`` when one is given, otherwise nothing."""
+    if stream is None:
+        return contextlib.nullcontext()
+    import torch
+    return torch.cuda.stream(_torch_stream(stream))
+
+
+def _release_on(t, stream):
+    """``t`` was allocated under torch's current stream and is released here while ``stream`` may still read it."""
+    if stream is not None:
+        t.record_stream(_torch_stream(stream))
+
+
+def _tensor_ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _image_size(width, height):
+    width, height = int(width), int(height)
+    if width < 1 or height < 1 or width * height >= 2 ** 31:
+        raise ValueError(f"invalid image size {width} x {height}")
+    return width, height
 
 
 @dataclasses.dataclass
@@ -567,7 +602,7 @@ class ParticleSet:
         there leaves them.  The result is allocated under that stream, so it may be dropped while the stream still
         reads it."""
         torch = self.torch
-        with (torch.cuda.stream(_torch_stream(stream)) if stream is not None else _nullcontext()):
+        with _on_stream(stream):
             out = torch.empty_like(t)
             out[self.ids.long()] = t
         return out
@@ -1019,9 +1054,7 @@ def _remap_cfg(width, height, lat_range=(0.0, 0.0), lon_range=(0.0, 0.0), depth=
                depth_range=(0.0, 0.0), layer_rule="reference", layer=0.0) -> L.RemapCfg:
     if layer_rule not in LAYER_RULES:
         raise ValueError(f"layer_rule must be one of {sorted(LAYER_RULES)}, not {layer_rule!r}")
-    width, height = int(width), int(height)
-    if width <= 0 or height <= 0 or width * height > 0x7fffffff:
-        raise ValueError(f"invalid image size {width} x {height}")
+    width, height = _image_size(width, height)
     return L.RemapCfg(width, height, float(lat_range[0]), float(lat_range[1]), float(lon_range[0]),
                       float(lon_range[1]), float(depth), float(latitude), float(depth_range[0]),
                       float(depth_range[1]), LAYER_RULES[layer_rule], float(layer))
@@ -1054,8 +1087,8 @@ def cell_to_vertex_attr(mesh: DeviceMesh, cell_attr, signed: bool = False):
         raise ValueError("attribute is not [nCells * nVertLevels]")
     out = torch.empty((mesh.nVertices, mesh.nVertLevels), dtype=torch.float64, device=dev)
     name = "mops_cell_to_vertex_signed" if signed else "mops_cell_to_vertex_attr"
-    L.check(getattr(L.load(), name)(mesh.handle, C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()),
-                                    _stream_handle(torch.cuda.current_stream(dev).cuda_stream)), name)
+    L.check(getattr(L.load(), name)(mesh.handle, _tensor_ptr(src), _tensor_ptr(out), _stream_or_current(None, dev)),
+            name)
     return out
 
 
@@ -1077,30 +1110,32 @@ def velocity_gradient(mesh: DeviceMesh, field: DeviceField, which=EDDY_FIELDS, v
     if bad or not names:
         raise ValueError(f"which: expected names out of {EDDY_FIELDS}, not {tuple(which)!r}")
     dev = torch.device("cuda", torch.cuda.current_device())
-    cur = torch.cuda.current_stream(dev).cuda_stream
-    h = stream if stream is not None else cur
+    h = _stream_or_current(stream, dev)
     out = {w: torch.empty((mesh.nCells, mesh.nVertLevels), dtype=torch.float64, device=dev) for w in names}
-    ptr = [C.c_void_p(out[w].data_ptr()) if w in out else None for w in EDDY_FIELDS]
-    L.check(L.load().mops_velocity_gradient(mesh.handle, field.handle, *ptr, _stream_handle(h)),
-            "mops_velocity_gradient")
+    ptr = [_tensor_ptr(out.get(w)) for w in EDDY_FIELDS]
+    L.check(L.load().mops_velocity_gradient(mesh.handle, field.handle, *ptr, h), "mops_velocity_gradient")
     if vertex:
         lib = L.load()
         for w in names:
             vt = torch.empty((mesh.nVertices, mesh.nVertLevels), dtype=torch.float64, device=dev)
-            L.check(lib.mops_cell_to_vertex_signed(mesh.handle, C.c_void_p(out[w].data_ptr()),
-                                                   C.c_void_p(vt.data_ptr()), _stream_handle(h)),
+            L.check(lib.mops_cell_to_vertex_signed(mesh.handle, _tensor_ptr(out[w]), _tensor_ptr(vt), h),
                     "mops_cell_to_vertex_signed")
-            if stream is not None:  # the cell array is released here while `stream` may still read it
-                out[w].record_stream(stream if isinstance(stream, torch.cuda.Stream)
-                                     else torch.cuda.ExternalStream(int(stream)))
+            _release_on(out[w], stream)  # the cell array
             out[w] = vt
     return out
 
 
-def _census_stream(stream):
-    import torch
-    dev = torch.device("cuda", torch.cuda.current_device())
-    return dev, (stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+def _census_args(mesh: DeviceMesh, layer, min_cells=1, threshold=None):
+    """The checks eddy_classify, eddy_table and eddy_census share; returns (layer, min_cells) as ints."""
+    import math
+    layer, min_cells = int(layer), int(min_cells)
+    if not 0 <= layer < mesh.nVertLevels:
+        raise ValueError(f"layer {layer} outside the {mesh.nVertLevels} levels")
+    if min_cells < 1:
+        raise ValueError(f"min_cells {min_cells} < 1")
+    if threshold is not None and not math.isfinite(float(threshold)):
+        raise ValueError(f"threshold {threshold!r} is not finite")
+    return layer, min_cells
 
 
 def _cell_tensor(mesh: DeviceMesh, t, name: str, dtype, per_level: bool = False):
@@ -1117,9 +1152,8 @@ def cell_area(mesh: DeviceMesh, stream=None):
     the velocity-gradient operator's ``A2``): a float64 CUDA tensor [nCells], NaN where that operator refuses
     the cell."""
     import torch
-    dev, h = _census_stream(stream)
-    out = torch.empty((mesh.nCells,), dtype=torch.float64, device=dev)
-    L.check(L.load().mops_cell_area(mesh.handle, C.c_void_p(out.data_ptr()), _stream_handle(h)), "mops_cell_area")
+    out = torch.empty((mesh.nCells,), dtype=torch.float64, device="cuda")
+    L.check(L.load().mops_cell_area(mesh.handle, _tensor_ptr(out), _stream_or_current(stream)), "mops_cell_area")
     return out
 
 
@@ -1128,18 +1162,12 @@ def eddy_classify(mesh: DeviceMesh, okubo_weiss, vorticity, layer: int, threshol
     positive / negative / anything else (NaN is class 0).  The arrays are ``velocity_gradient``'s
     [nCells, nVertLevels] tensors; returns an int32 CUDA tensor [nCells]."""
     import torch
-    import math
-    layer = int(layer)
-    if not 0 <= layer < mesh.nVertLevels:
-        raise ValueError(f"layer {layer} outside the {mesh.nVertLevels} levels")
-    if not math.isfinite(float(threshold)):
-        raise ValueError(f"threshold {threshold!r} is not finite")
+    layer, _ = _census_args(mesh, layer, threshold=threshold)
     ow = _cell_tensor(mesh, okubo_weiss, "okubo_weiss", torch.float64, per_level=True)
     vo = _cell_tensor(mesh, vorticity, "vorticity", torch.float64, per_level=True)
-    dev, h = _census_stream(stream)
-    out = torch.empty((mesh.nCells,), dtype=torch.int32, device=dev)
-    L.check(L.load().mops_eddy_classify(mesh.handle, ow, vo, layer, float(threshold), C.c_void_p(out.data_ptr()),
-                                        _stream_handle(h)), "mops_eddy_classify")
+    out = torch.empty((mesh.nCells,), dtype=torch.int32, device="cuda")
+    L.check(L.load().mops_eddy_classify(mesh.handle, ow, vo, layer, float(threshold), _tensor_ptr(out),
+                                        _stream_or_current(stream)), "mops_eddy_classify")
     return out
 
 
@@ -1151,11 +1179,10 @@ def label_components(mesh: DeviceMesh, classes, return_rounds: bool = False, str
     used."""
     import torch
     cls = _cell_tensor(mesh, classes, "classes", torch.int32)
-    dev, h = _census_stream(stream)
-    out = torch.empty((mesh.nCells,), dtype=torch.int32, device=dev)
+    out = torch.empty((mesh.nCells,), dtype=torch.int32, device="cuda")
     rounds = C.c_int32(0)
-    L.check(L.load().mops_label_components(mesh.handle, cls, C.c_void_p(out.data_ptr()), C.byref(rounds),
-                                           _stream_handle(h)), "mops_label_components")
+    L.check(L.load().mops_label_components(mesh.handle, cls, _tensor_ptr(out), C.byref(rounds),
+                                           _stream_or_current(stream)), "mops_label_components")
     return (out, int(rounds.value)) if return_rounds else out
 
 
@@ -1170,28 +1197,23 @@ def eddy_table(mesh: DeviceMesh, labels, classes, area, vorticity, okubo_weiss, 
     arrays [E] -- ``EDDY_COLUMNS``, ``centre`` being [E, 3]).  Every sum runs over an eddy's cells in ascending
     cell index.  Both entries synchronise the stream."""
     import torch
-    layer, min_cells = int(layer), int(min_cells)
-    if not 0 <= layer < mesh.nVertLevels:
-        raise ValueError(f"layer {layer} outside the {mesh.nVertLevels} levels")
-    if min_cells < 1:
-        raise ValueError(f"min_cells {min_cells} < 1")
+    layer, min_cells = _census_args(mesh, layer, min_cells)
     lab = _cell_tensor(mesh, labels, "labels", torch.int32)
     cls = _cell_tensor(mesh, classes, "classes", torch.int32)
     ar = _cell_tensor(mesh, area, "area", torch.float64)
     vo = _cell_tensor(mesh, vorticity, "vorticity", torch.float64, per_level=True)
     ow = _cell_tensor(mesh, okubo_weiss, "okubo_weiss", torch.float64, per_level=True)
-    dev, h = _census_stream(stream)
+    h = _stream_or_current(stream)
     lib = L.load()
-    eoc = torch.empty((mesh.nCells,), dtype=torch.int32, device=dev)
+    eoc = torch.empty((mesh.nCells,), dtype=torch.int32, device="cuda")
     n = C.c_int64(0)
-    L.check(lib.mops_eddy_count(mesh.handle, lab, min_cells, C.c_void_p(eoc.data_ptr()), C.byref(n),
-                                _stream_handle(h)), "mops_eddy_count")
+    L.check(lib.mops_eddy_count(mesh.handle, lab, min_cells, _tensor_ptr(eoc), C.byref(n), h), "mops_eddy_count")
     E = int(n.value)
     t = {k: np.empty((E,), dtype=np.int32) for k in EDDY_COLUMNS[:4]}
     t.update({k: np.empty((E,), dtype=np.float64) for k in EDDY_COLUMNS[4:7]})
     t["centre"] = np.empty((E, 3), dtype=np.float64)
-    L.check(lib.mops_eddy_table(mesh.handle, C.c_void_p(eoc.data_ptr()), E, cls, ar, vo, ow, layer,
-                                *[_ptr(t[k]) for k in EDDY_COLUMNS], _stream_handle(h)), "mops_eddy_table")
+    L.check(lib.mops_eddy_table(mesh.handle, _tensor_ptr(eoc), E, cls, ar, vo, ow, layer,
+                                *[_ptr(t[k]) for k in EDDY_COLUMNS], h), "mops_eddy_table")
     return eoc, t
 
 
@@ -1234,7 +1256,7 @@ class EddyCensus:
         import torch
         layer_image, cells = remap_fixed_layer(self.mesh, self.field, width, height, lat_range, lon_range,
                                                float(self.layer), return_cells=True, stream=stream)
-        with (torch.cuda.stream(_torch_stream(stream)) if stream is not None else _nullcontext()):
+        with _on_stream(stream):
             inside = (cells >= 0) & (cells < self.mesh.nCells) & ~torch.isnan(layer_image[..., 0])
             c = torch.where(inside, cells, torch.zeros_like(cells)).long()
             e = self.labels[c]
@@ -1262,13 +1284,7 @@ def eddy_census(mesh: DeviceMesh, field: DeviceField, layer: int = 0, k_sigma: f
     synchronises."""
     import math
     import torch
-    layer, min_cells = int(layer), int(min_cells)
-    if not 0 <= layer < mesh.nVertLevels:
-        raise ValueError(f"layer {layer} outside the {mesh.nVertLevels} levels")
-    if min_cells < 1:
-        raise ValueError(f"min_cells {min_cells} < 1")
-    if threshold is not None and not math.isfinite(float(threshold)):
-        raise ValueError(f"threshold {threshold!r} is not finite")
+    layer, min_cells = _census_args(mesh, layer, min_cells, threshold)
     if threshold is None and not math.isfinite(float(k_sigma)):
         raise ValueError(f"k_sigma {k_sigma!r} is not finite")
     if gradient is not None:
@@ -1327,11 +1343,9 @@ def remap_fixed_depth(mesh: DeviceMesh, field: DeviceField, width: int, height: 
                          device=dev)
     cells = torch.empty((cfg.height, cfg.width), dtype=torch.int32, device=dev) if return_cells else None
     ms = (C.c_float * 3)() if stage_ms is not None else None
-    h = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
     L.check(lib.mops_remap_fixed_depth(mesh.handle, field.handle, C.byref(cfg), n_attr, a[0], a[1],
-                                       C.c_void_p(images.data_ptr()),
-                                       None if cells is None else C.c_void_p(cells.data_ptr()), ms,
-                                       _stream_handle(h)), "mops_remap_fixed_depth")
+                                       _tensor_ptr(images), _tensor_ptr(cells), ms, _stream_or_current(stream, dev)),
+            "mops_remap_fixed_depth")
     if stage_ms is not None:
         stage_ms[:] = [float(x) for x in ms]
     return (images, cells) if return_cells else images
@@ -1347,11 +1361,9 @@ def remap_fixed_latitude(mesh: DeviceMesh, field: DeviceField, width: int, heigh
     dev = torch.device("cuda", torch.cuda.current_device())
     image = torch.empty((cfg.height, cfg.width, 4), dtype=torch.float64, device=dev)
     cells = torch.empty((cfg.width,), dtype=torch.int32, device=dev) if return_cells else None
-    h = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-    L.check(L.load().mops_remap_fixed_latitude(mesh.handle, field.handle, C.byref(cfg),
-                                               C.c_void_p(image.data_ptr()),
-                                               None if cells is None else C.c_void_p(cells.data_ptr()),
-                                               _stream_handle(h)), "mops_remap_fixed_latitude")
+    L.check(L.load().mops_remap_fixed_latitude(mesh.handle, field.handle, C.byref(cfg), _tensor_ptr(image),
+                                               _tensor_ptr(cells), _stream_or_current(stream, dev)),
+            "mops_remap_fixed_latitude")
     return (image, cells) if return_cells else image
 
 
@@ -1366,10 +1378,9 @@ def remap_fixed_layer(mesh: DeviceMesh, field: DeviceField, width: int, height: 
     dev = torch.device("cuda", torch.cuda.current_device())
     image = torch.empty((cfg.height, cfg.width, 4), dtype=torch.float64, device=dev)
     cells = torch.empty((cfg.height, cfg.width), dtype=torch.int32, device=dev) if return_cells else None
-    h = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-    L.check(L.load().mops_remap_fixed_layer(mesh.handle, field.handle, C.byref(cfg), C.c_void_p(image.data_ptr()),
-                                            None if cells is None else C.c_void_p(cells.data_ptr()),
-                                            _stream_handle(h)), "mops_remap_fixed_layer")
+    L.check(L.load().mops_remap_fixed_layer(mesh.handle, field.handle, C.byref(cfg), _tensor_ptr(image),
+                                            _tensor_ptr(cells), _stream_or_current(stream, dev)),
+            "mops_remap_fixed_layer")
     return (image, cells) if return_cells else image
 
 
@@ -1435,9 +1446,7 @@ def remap_section(mesh: DeviceMesh, field: DeviceField, path, width: int, height
     [width, 3], normals [width, 3] or None) replaces ``path`` (then None) by explicit column positions; the
     distance returned is None, and without normals the across channel is 0."""
     import torch
-    width, height = int(width), int(height)
-    if width <= 0 or height <= 0 or width * height > 0x7fffffff:
-        raise ValueError(f"invalid image size {width} x {height}")
+    width, height = _image_size(width, height)
     if columns is None:
         pts, nrm, dist = section_points(path, width)
     else:
@@ -1463,12 +1472,9 @@ def remap_section(mesh: DeviceMesh, field: DeviceField, path, width: int, height
     dev = torch.device("cuda", torch.cuda.current_device())
     images = torch.empty((2 if n_attr else 1, height, width, 4), dtype=torch.float64, device=dev)
     cells = torch.empty((width,), dtype=torch.int32, device=dev) if return_cells else None
-    h = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
     L.check(L.load().mops_remap_section(mesh.handle, field.handle, width, height, d0, d1, _ptr(pts), _ptr(nrm), n_attr,
-                                        a[0], a[1], C.c_void_p(images[0].data_ptr()),
-                                        C.c_void_p(images[1].data_ptr()) if n_attr else None,
-                                        None if cells is None else C.c_void_p(cells.data_ptr()),
-                                        _stream_handle(h)), "mops_remap_section")
+                                        a[0], a[1], _tensor_ptr(images[0]), _tensor_ptr(images[1] if n_attr else None),
+                                        _tensor_ptr(cells), _stream_or_current(stream, dev)), "mops_remap_section")
     return (images, dist, cells) if return_cells else (images, dist)
 
 
@@ -1490,9 +1496,8 @@ def colormap_rgba(image_cuda, channels=(0, 1, 2), return_minmax: bool = False, s
     out = torch.empty((len(channels), hgt, wid, 4), dtype=torch.uint8, device=t.device)
     mm = np.empty((4, 2), dtype=np.float32) if return_minmax else None
     with torch.cuda.device(t.device):
-        h = stream if stream is not None else torch.cuda.current_stream(t.device).cuda_stream
-        L.check(L.load().mops_colormap_rgba8(C.c_void_p(t.data_ptr()), wid, hgt, mask, C.c_void_p(out.data_ptr()),
-                                             _ptr(mm), _stream_handle(h)), "mops_colormap_rgba8")
+        L.check(L.load().mops_colormap_rgba8(_tensor_ptr(t), wid, hgt, mask, _tensor_ptr(out), _ptr(mm),
+                                             _stream_or_current(stream, t.device)), "mops_colormap_rgba8")
     return (out, mm[channels]) if return_minmax else out
 
 
@@ -1513,10 +1518,8 @@ class DensityMap:
         import torch
         if value is not None and not isinstance(value, str):
             raise ValueError("DensityMap: value must be None, 'speed' or an attribute name")
-        width, height = int(width), int(height)
         lat, lon = (float(lat_range[0]), float(lat_range[1])), (float(lon_range[0]), float(lon_range[1]))
-        if width < 1 or height < 1 or width * height >= 2 ** 31:
-            raise ValueError(f"invalid image size {width} x {height}")
+        width, height = _image_size(width, height)
         if not (np.isfinite(lat).all() and np.isfinite(lon).all() and lat[1] > lat[0] and lon[1] > lon[0]
                 and lon[1] - lon[0] <= 360.0):
             raise ValueError(f"invalid latitude / longitude range {lat} / {lon}")
@@ -1537,16 +1540,13 @@ class DensityMap:
         host synchronisation.  A caller that accumulates on another stream orders the two itself."""
         self.accum.zero_()
 
-    def _stream(self, stream):
-        return stream if stream is not None else self.torch.cuda.current_stream(self.device).cuda_stream
-
     def _call(self, n, k0, k1, points_ptr, sk, si, sc, seeds_ptr, values_ptr, vk, vi, stream):
         with self.torch.cuda.device(self.device):
             L.check(L.load().mops_density_accumulate(
                 C.byref(self.cfg), int(n), int(k0), int(k1), C.c_void_p(points_ptr), int(sk), int(si), int(sc),
                 None if seeds_ptr is None else C.c_void_p(seeds_ptr), self.kind,
                 None if values_ptr is None else C.c_void_p(values_ptr), int(vk), int(vi),
-                C.c_void_p(self.accum.data_ptr()), _stream_handle(self._stream(stream))), "mops_density_accumulate")
+                _tensor_ptr(self.accum), _stream_or_current(stream, self.device)), "mops_density_accumulate")
 
     def accumulate(self, ps: "ParticleSet", n_records: int | None = None, seeds: bool = False, names=None,
                    record_range=None, stream=None):
@@ -1600,9 +1600,9 @@ class DensityMap:
         torch = self.torch
         with torch.cuda.device(self.device):
             img = torch.empty((self.height, self.width, 4), dtype=torch.float64, device=self.device)
-            L.check(L.load().mops_density_image(C.byref(self.cfg), C.c_void_p(self.accum.data_ptr()),
-                                                1 if nan_empty else 0, C.c_void_p(img.data_ptr()),
-                                                _stream_handle(self._stream(stream))), "mops_density_image")
+            L.check(L.load().mops_density_image(C.byref(self.cfg), _tensor_ptr(self.accum), 1 if nan_empty else 0,
+                                                _tensor_ptr(img), _stream_or_current(stream, self.device)),
+                    "mops_density_image")
         return img
 
 
@@ -1620,10 +1620,8 @@ class FlowMapLattice:
 
     def __init__(self, width: int, height: int, lat_range, lon_range, device=None):
         import torch
-        width, height = int(width), int(height)
         lat, lon = (float(lat_range[0]), float(lat_range[1])), (float(lon_range[0]), float(lon_range[1]))
-        if width < 1 or height < 1 or width * height >= 2 ** 31:
-            raise ValueError(f"invalid image size {width} x {height}")
+        width, height = _image_size(width, height)
         if not (np.isfinite(lat).all() and np.isfinite(lon).all()):
             raise ValueError(f"invalid latitude / longitude range {lat} / {lon}")
         self.torch = torch
@@ -1634,11 +1632,8 @@ class FlowMapLattice:
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         with torch.cuda.device(self.device):
             self.seeds = torch.empty((self.n, 3), dtype=torch.float64, device=self.device)
-            L.check(L.load().mops_flowmap_lattice(C.byref(self.cfg), C.c_void_p(self.seeds.data_ptr()),
-                                                  _stream_handle(self._stream(None))), "mops_flowmap_lattice")
-
-    def _stream(self, stream):
-        return stream if stream is not None else self.torch.cuda.current_stream(self.device).cuda_stream
+            L.check(L.load().mops_flowmap_lattice(C.byref(self.cfg), _tensor_ptr(self.seeds),
+                                                  _stream_or_current(None, self.device)), "mops_flowmap_lattice")
 
     def ftle(self, last_points, death=None, horizon: float = 1.0, stream=None):
         """The FTLE image (mops_ftle_image) of ``last_points`` [height * width, 3] in seed order (CUDA tensor or
@@ -1657,7 +1652,7 @@ class FlowMapLattice:
         horizon = float(horizon)
         if not (np.isfinite(horizon) and horizon > 0.0):
             raise ValueError("ftle: the horizon must be finite and positive")
-        with (torch.cuda.stream(_torch_stream(stream)) if stream is not None else _nullcontext()):
+        with _on_stream(stream):
             last = torch.as_tensor(last_points, dtype=torch.float64).to(self.device).contiguous()
             if death is not None:
                 death = torch.as_tensor(death).to(device=self.device, dtype=torch.int32).contiguous()
@@ -1667,11 +1662,9 @@ class FlowMapLattice:
             raise ValueError(f"ftle: death must be [{self.n}]")
         with torch.cuda.device(self.device):
             img = torch.empty((self.height, self.width, 4), dtype=torch.float64, device=self.device)
-            L.check(L.load().mops_ftle_image(C.byref(self.cfg), C.c_void_p(self.seeds.data_ptr()),
-                                             C.c_void_p(last.data_ptr()),
-                                             None if death is None else C.c_void_p(death.data_ptr()), horizon,
-                                             1 if self.wrap_lon else 0, C.c_void_p(img.data_ptr()),
-                                             _stream_handle(self._stream(stream))), "mops_ftle_image")
+            L.check(L.load().mops_ftle_image(C.byref(self.cfg), _tensor_ptr(self.seeds), _tensor_ptr(last),
+                                             _tensor_ptr(death), horizon, 1 if self.wrap_lon else 0, _tensor_ptr(img),
+                                             _stream_or_current(stream, self.device)), "mops_ftle_image")
         return img
 
     def ftle_from(self, ps: "ParticleSet", horizon: float, stream=None):
@@ -1681,8 +1674,7 @@ class FlowMapLattice:
         the set's ``advance`` / ``compact`` on that stream directly."""
         if ps.n != self.n:
             raise ValueError("ftle_from: the particle set is not this lattice's")
-        h = self._stream(stream)
+        h = _current_or(stream, self.device)
         last = ps.last_points(stream=h)
-        if stream is not None:  # allocated under torch's current stream and released here while `stream` reads it
-            last.record_stream(_torch_stream(stream))
+        _release_on(last, stream)
         return self.ftle(last, ps.original(ps.death, stream=h), horizon, stream=h)

@@ -360,7 +360,7 @@ def test_build_id_is_stamped_and_checked(engine_lib, tmp_path):
     bid = _build_id.build_id()
     assert engine_lib.mops_build_id() == (_build_id.MARKER + bid).encode()
     assert _build_id.stamped_id(_lib.LIB_PATH) == bid
-    assert len(_build_id.SOURCES) == 4 and all(os.path.exists(p) for p in _build_id.SOURCES + _build_id.HEADERS)
+    assert len(_build_id.SOURCES) == 5 and all(os.path.exists(p) for p in _build_id.SOURCES + _build_id.HEADERS)
     # a stale library (other stamp) at the product path is refused
     stale = tmp_path / "libmops_traj.so"
     data = open(_lib.LIB_PATH, "rb").read().replace(bid.encode(), b"0" * 16)

@@ -2,7 +2,8 @@
 r"""Compare the kernels of two gfx950 assembly listings function by function.
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Iinclude -S --cuda-device-only \
-          -o parent.s <parent>/mops_amd/csrc/mops_engine.hip        (and the same for the new source)
+          -o engine.s mops_amd/csrc/mops_engine.hip      (and -o analysis.s mops_amd/csrc/mops_analysis.hip)
+    cat engine.s analysis.s > new.s                      (the same for the parent's sources: parent.s)
     python tools/asm_compare.py parent.s new.s [--rename REGEX REPLACEMENT]
 
 Every function of the first listing must exist in the second with the same body once comments, debug
@@ -24,10 +25,13 @@ import sys
 
 
 def functions(path):
-    out, cur, body = {}, None, []
+    out, cur, body, typed = {}, None, [], None
     for line in open(path):
+        t = re.match(r"^\s*\.type\s+(\w+),@function", line)
+        if t:
+            typed = t.group(1)
         m = re.match(r"^([A-Za-z_]\w*):\s*(;.*)?$", line)
-        if m and cur is None:
+        if m and cur is None and m.group(1) == typed:  # (not a data label: another listing's functions may follow it)
             cur, body = m.group(1), []
             continue
         if cur is not None:

@@ -1,7 +1,7 @@
 """Instruction mix between the "@@MARK <id>" comments of a -DMOPS_ISA_MARKS assembly build.
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DMOPS_ISA_MARKS -Iinclude \
-          --cuda-device-only -S -o marks.s mops_amd/csrc/mops_engine.hip
+          --cuda-device-only -S -o marks.s mops_amd/csrc/mops_engine.hip      (every marker is in this file)
     python tools/isa_marks.py marks.s [--kernel _Z11traj_kernelILi7ELb0ELb1EEv8TrajArgs] [--dump 400:410]
 
 For each marker, the instructions from it to the next marker in layout order (cold blocks the
