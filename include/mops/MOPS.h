@@ -309,6 +309,20 @@ std::vector<CartesianCoord> MOPS_LatticeSeeds(VisualizationSettings* config);
 // image.
 ImageBuffer<double> MOPS_RunFTLE(const std::vector<TrajectoryLine>& lines, VisualizationSettings* config,
                                  double horizon);
+// Extension ("path integrals and LAVD", mops_traj.h): the Lagrangian-averaged vorticity deviation over the active
+// front / back pair.  One particle per pixel of config's window (the lattice of MOPS_LatticeSeeds) at
+// config->FixedDepth runs one pathline with traj's deltaT, simulationDuration, recordT, direction and method; each
+// solution's vorticity deviation -- its vorticity minus the area-weighted mean of its level, kept per solution
+// id -- is the single sampled attribute, and the sampled line is summed with the rectangle rule: slot j, sampled
+// at the start of step (j+1)*ri - 1, times recordT seconds.  Made of mops_flowmap_lattice,
+// mops_velocity_gradient, mops_cell_area, mops_level_mean, mops_cell_to_vertex_signed, mops_run_pathline_attrs,
+// mops_path_integral_abs over the returned attribute lines and mops_path_integral_image.  One image {LAVD, mean
+// |deviation| in 1/s over K * recordT seconds, 0} (alpha 1), NaN where the particle died (land included), usable
+// with SaveToPNG and SaveVTI; it overlays the velocity, density, FTLE and eddy images of the same window.  kRK4
+// leaves a mostly-NaN map (quirk Q1).  Invalid inputs (a null argument, no back solution, fixedLayer >= 0,
+// relocateStages, diffusivity other than 0, an image size below 1, settings without a step or a record): Error()
+// and an empty image.
+ImageBuffer<double> MOPS_RunLAVD(VisualizationSettings* config, TrajectorySettings* traj);
 // Extension ("vertical sections", mops_traj.h): a depth-by-distance image of the active front solution along the
 // great-circle legs through config->SectionPath (mops_section_points, mops_remap_section): imageSize = (columns,
 // rows), rows over config->DepthRange, or over the grid's cellRefBottomDepth_vec front / back while DepthRange

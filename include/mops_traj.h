@@ -1013,6 +1013,79 @@ mops_status mops_flowmap_lattice(const mops_remap_cfg* cfg, double* d_points, vo
 mops_status mops_ftle_image(const mops_remap_cfg* cfg, const double* d_seeds, const double* d_last,
                             const int32_t* d_death, double horizon, int32_t wrap_lon, double* d_image, void* stream);
 
+/* ---- path integrals and LAVD ------------------------------------------------ */
+
+/* The Lagrangian-averaged vorticity deviation: the time integral of
+ * |vorticity - its horizontal mean| along a pathline (Haller et al. 2016), the
+ * objective detector of coherent Lagrangian eddies.  No reference counterpart.
+ * Three entries: the weighted mean of a cell field per level, the sum of
+ * |sample| * weight over a particle's record slots, and the sum as an image.
+ * The deviation itself (field - mean[l], one IEEE subtraction per element) and
+ * its cell-to-vertex interpolation (mops_cell_to_vertex_signed) are the
+ * caller's; the samples are the attribute channel's (mops_traj_advance_sampled
+ * / _captured, mops_run_pathline_attrs).
+ *
+ * The rule is a rectangle rule.  Slot j of a pair's attribute slab is sampled
+ * at the start of step (j+1)*ri - 1 (ri = record_t / delta_t steps) and stands
+ * for one record interval: the integral of a pair is the sum over its slots
+ * [0, K) of |sample| * |record_t| seconds.  A particle's slots after its death
+ * hold the reference's zeros and add nothing; a consumer masks such a particle
+ * through the death array of mops_path_integral_image.
+ *
+ * FP64, no contraction: every product below is rounded before its sum. */
+
+/* The order of mops_level_mean's sum is part of the ABI: cells in groups of
+ * this many, ascending within a group, then the groups ascending. */
+#define MOPS_MEAN_GROUP 64
+
+/* mean[l] = sum_c w[c]*x[c*L+l] / sum_c w[c] per level l over the counting
+ * cells.  Mesh-free: n_cells = C >= 1, n_levels = L >= 1, d_field [C*L],
+ * d_weight [C], d_mean [L], d_wsum [L], all device doubles.  Term (c, l) counts
+ * iff isfinite(field[c*L+l]) and isfinite(weight[c]) and weight[c] > 0.
+ *   group g = cells [64g, min(64g+64, C)):
+ *     num_g = 0.0, den_g = 0.0; for each counting cell c of the group in
+ *     ascending order: num_g = num_g + (w * x), den_g = den_g + w
+ *   level:  num = 0.0, den = 0.0; for g ascending: num = num + num_g,
+ *     den = den + den_g
+ *   mean[l] = num / den, NaN where den == 0;  wsum[l] = den
+ * A caller confines the mean to a window or basin by zeroing weights.  Lanes
+ * run over the levels (a row of [C][L] is one coalesced read): one wave per
+ * group and per 64 levels, then one block per level over the group partials.
+ * The partials are a temporary allocation of the call, so the entry
+ * SYNCHRONISES `stream` before it frees them.  MOPS_ERR_INVALID before any
+ * device work: a null pointer, C < 1, L < 1 (or more than 2^31 - 1 groups). */
+mops_status mops_level_mean(int64_t n_cells, int32_t n_levels, const double* d_field, const double* d_weight,
+                            double* d_mean, double* d_wsum, void* stream);
+
+/* One lane per slot i < n:
+ *   id = d_ids ? d_ids[i] : i
+ *   s = accum[id]
+ *   for k = k_begin .. k_end-1:  s = s + (fabs(values[k*vk + i*vi]) * weight)
+ *   accum[id] = s
+ * d_ids (int32, NULL = identity) is a permutation of 0 .. n-1 (a ParticleSet's
+ * slot -> particle array), so no two lanes write one element: no atomics, and
+ * the bytes do not depend on the schedule.  The sum starts from the
+ * accumulator, so a chain that calls the entry once per pair equals one long
+ * ascending sum.  A non-finite sample makes the sum non-finite; it is not
+ * filtered.  The strides are mops_density_accumulate's: row a of an attribute
+ * slab [K][n_attr][stride] is d_values = slab + a*stride, vk = n_attr*stride,
+ * vi = 1; finished lines [n][P] are vk = 1, vi = P.  d_accum [n] doubles.
+ * Enqueues on `stream` and does not synchronise.  MOPS_ERR_INVALID before any
+ * device work: a null d_values or d_accum, n < 1, k_begin < 0,
+ * k_end < k_begin, a non-finite weight or weight < 0.  k_begin == k_end:
+ * MOPS_OK, nothing written. */
+mops_status mops_path_integral_abs(int64_t n, int64_t k_begin, int64_t k_end, const double* d_values, int64_t vk,
+                                   int64_t vi, const int32_t* d_ids, double weight, double* d_accum, void* stream);
+
+/* Pixel i of d_image [n*4] (16-byte aligned) = {s, s / horizon, 0, 1} with
+ * s = accum[i]; {NaN, NaN, NaN, 1} where d_death (int32 [n], may be NULL) has
+ * death[i] >= 0 or s is not finite.  horizon in the unit channel 1 is wanted
+ * per (seconds for a mean |deviation| in 1/s).  Enqueues on `stream` and does
+ * not synchronise.  MOPS_ERR_INVALID before any device work: a null d_accum or
+ * d_image, n < 1, a horizon that is not finite and positive. */
+mops_status mops_path_integral_image(int64_t n, const double* d_accum, const int32_t* d_death, double horizon,
+                                     double* d_image, void* stream);
+
 /* Identity of the engine build: a hash of the engine's sources, headers,
  * compiler flags and ROCm version, stamped at compile time (no reference
  * counterpart).  The Python loader refuses a library whose id differs from

@@ -35,6 +35,7 @@ EXPORTED = (
     "mops_cell_area", "mops_eddy_classify", "mops_label_components", "mops_eddy_count", "mops_eddy_table",
     "mops_density_bytes", "mops_density_accumulate", "mops_density_image",
     "mops_flowmap_lattice", "mops_ftle_image",
+    "mops_level_mean", "mops_path_integral_abs", "mops_path_integral_image",
     # include/mops_io.h
     "mops_lines_geo", "mops_write_lines_vtp", "mops_write_lines_txt", "mops_write_pathline_binary",
     "mops_write_png_rgba8", "mops_write_images_vti", "mops_write_image_vti",
@@ -49,6 +50,7 @@ MOPS_RK4, MOPS_EULER = 0, 1
 MOPS_RK4_RELOCATE = 2  # pathline RK4 with each stage located in its own cell (the opt-out of quirk Q1; mops_traj.h)
 MOPS_LAYER_REFERENCE, MOPS_LAYER_BRACKET = 0, 1
 MOPS_DENSITY_COUNT, MOPS_DENSITY_SPEED, MOPS_DENSITY_VALUES = 0, 1, 2
+MOPS_MEAN_GROUP = 64  # cells per group of mops_level_mean's sum (include/mops_traj.h: part of the ABI)
 
 
 class MeshDesc(C.Structure):
@@ -247,6 +249,12 @@ def load(path: str | None = None):
     lib.mops_density_image.argtypes = [P, P, I32, P, P]; lib.mops_density_image.restype = st
     lib.mops_flowmap_lattice.argtypes = [P, P, P]; lib.mops_flowmap_lattice.restype = st
     lib.mops_ftle_image.argtypes = [P, P, P, P, C.c_double, I32, P, P]; lib.mops_ftle_image.restype = st
+    if hasattr(lib, "mops_level_mean"):  # (older engine builds timed as variants lack the path integrals)
+        lib.mops_level_mean.argtypes = [I64, I32, P, P, P, P, P]; lib.mops_level_mean.restype = st
+        lib.mops_path_integral_abs.argtypes = [I64, I64, I64, P, I64, I64, P, C.c_double, P, P]
+        lib.mops_path_integral_abs.restype = st
+        lib.mops_path_integral_image.argtypes = [I64, P, P, C.c_double, P, P]
+        lib.mops_path_integral_image.restype = st
     lib.mops_write_png_rgba8.argtypes = [C.c_char_p, I32, I32, P]; lib.mops_write_png_rgba8.restype = st
     lib.mops_write_images_vti.argtypes = [C.c_char_p, I32, I32, I32, P, P, P, P, I32]
     lib.mops_write_images_vti.restype = st

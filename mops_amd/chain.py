@@ -31,8 +31,8 @@ from datetime import datetime
 import numpy as np
 
 from . import _lib as L
-from .engine import (MAX_SAMPLE_ATTRS, DensityMap, DeviceField, DeviceMesh, ParticleSet, TrajectoryConfig,
-                     cell_to_vertex_attr)
+from .engine import (MAX_SAMPLE_ATTRS, DensityMap, DeviceField, DeviceMesh, ParticleSet, PathIntegral,
+                     TrajectoryConfig, cell_to_vertex_attr, vorticity_deviation)
 
 EARTH_RADIUS_M = 6_371_000.0  # pyMOPSAPI.py:46
 REORDER_SECONDS = 3 * 86400  # default launch length of long pairs (simulated time), see PathlineChain.run
@@ -120,7 +120,9 @@ class PathlineChain:
         ``run(attrs=True)``) builds snapshot i's vertex attributes for the sampling (``cell_to_vertex_attr``).
         It is called wherever snapshot i's field is built or refilled, with that stream as torch's current
         stream, and its tensors are dropped where field i is freed or recycled: they live exactly as long as
-        the field, on the prefetch, recycle and overlap paths alike."""
+        the field, on the prefetch, recycle and overlap paths alike.  A ``make_attrs`` with an attribute
+        ``wants_field`` = True derives its attributes from the snapshot's field and is called as
+        ``make_attrs(i, stream, field=fields[i])`` at every one of those places (``derived_attr_factory``)."""
         if n_snapshots < 2:
             raise ValueError("a pathline chain needs at least two snapshots")
         self.mesh = mesh
@@ -152,7 +154,7 @@ class PathlineChain:
             record_stride: int | None = None, defer_lines: bool = False, compact: bool | None = None,
             compact_chunks: int = 6, on_lines=None, lines_chunk: int | None = None, attrs: bool = False,
             capture_slots: int | None = None, density=None, layer: int | None = None, diffusivity: float = 0.0,
-            seed: int = 0, epochs=None):
+            seed: int = 0, epochs=None, integrals=None):
         """Run all pairs; returns device tensors {points, velocity, temperature,
         salinity, lastPoint, death_step (of the last pair)} when ``keep_lines``,
         else only lastPoint/death_step.  ``on_pair(p, last, ps)`` is called after pair p
@@ -216,7 +218,14 @@ class PathlineChain:
         in mops_traj.h) in every pair, keyed by ``seed``, the particle's index in ``seeds`` and the pair's global
         step, with the epoch word set to the pair index so that no two pairs draw the same deviates (``epochs``: a
         list of one word per pair instead).  Works in every mode above except ``attrs`` (ValueError before any
-        launch).  0: no kick code runs, unchanged."""
+        launch).  0: no kick code runs, unchanged.
+        ``integrals``: a dict {attribute name: engine.PathIntegral}.  Where the density maps are binned -- after
+        each pair's last launch, on the compute stream, before any slab swap -- every integral adds that pair's
+        slots [0, n_records) of its attribute times that pair's |record_t| seconds onto its accumulator at the
+        particles' ids (the rectangle rule of "path integrals and LAVD", include/mops_traj.h): the whole chain's
+        path integral, one ascending sum per particle, with no line leaving the device.  Needs ``attrs`` and a
+        sampled name (ValueError before any trajectory launch, as ``density``); works in every mode ``density``
+        works in.  The integrals are not reset here; None changes nothing."""
         import torch
         if not (float(diffusivity) >= 0.0) or not np.isfinite(float(diffusivity)):
             raise ValueError(f"diffusivity must be finite and >= 0, not {diffusivity!r}")
@@ -240,6 +249,17 @@ class PathlineChain:
                 given = getattr(self.make_attrs, "names", None)
                 if given and m.attribute not in sorted(given)[:MAX_SAMPLE_ATTRS]:
                     raise ValueError(f"density: the chain samples no attribute {m.attribute!r}")
+        if integrals is not None and not isinstance(integrals, dict):
+            raise ValueError("integrals: a dict {attribute name: PathIntegral}")
+        ints = dict(integrals or {})
+        for k, it in ints.items():
+            if not isinstance(k, str) or not isinstance(it, PathIntegral):
+                raise ValueError("integrals: a dict {attribute name: PathIntegral}")
+            if not attrs:
+                raise ValueError(f"integrals: the integral of the attribute {k!r} needs attrs=True")
+            given = getattr(self.make_attrs, "names", None)
+            if given and k not in sorted(given)[:MAX_SAMPLE_ATTRS]:
+                raise ValueError(f"integrals: the chain samples no attribute {k!r}")
         if attrs and int(method) == L.MOPS_RK4_RELOCATE:
             raise ValueError("attrs: attributes are not sampled with MOPS_RK4_RELOCATE")
         if attrs and self.make_attrs is None:
@@ -293,7 +313,10 @@ class PathlineChain:
             """Snapshot i's vertex attributes, inside ``with torch.cuda.stream(stream)``."""
             if not attrs:
                 return
-            t = self.make_attrs(i, stream.cuda_stream)
+            if getattr(self.make_attrs, "wants_field", False):
+                t = self.make_attrs(i, stream.cuda_stream, field=fields[i])
+            else:
+                t = self.make_attrs(i, stream.cuda_stream)
             missing = [k for k in names if k not in t]
             if missing:
                 raise ValueError(f"snapshot {i} carries no attribute {missing[0]!r}")
@@ -326,6 +349,9 @@ class PathlineChain:
                 for m in maps:
                     if m.attribute is not None and m.attribute not in names:
                         raise ValueError(f"density: the chain samples no attribute {m.attribute!r}")
+                for k in ints:
+                    if k not in names:
+                        raise ValueError(f"integrals: the chain samples no attribute {k!r}")
             if overlap and self.n_snapshots > 2 and len(self.make_field.pool) < 1:
                 raise ValueError("overlap_stream needs a third field buffer in make_field.pool (seed the "
                                  "recycler with three fields and release them before the run)")
@@ -333,6 +359,9 @@ class PathlineChain:
                 capture_slots = cfg.n_records if DEFAULT_CAPTURE else 0
             ps = ParticleSet(self.mesh, seeds0, cfg.depth, cfg, device=dev, record_stride=record_stride,
                              n_attr=len(names), capture_slots=int(capture_slots) if attrs else 0)
+            for k, it in ints.items():
+                if it.n != ps.n:
+                    raise ValueError(f"integrals: the integral of {k!r} holds {it.n} particles, the chain {ps.n}")
         period = ps.record_period(pathline=True)
         pts_acc, vel_acc, tmp_acc, sal_acc, att_acc = [], [], [], [], []
         last = None
@@ -418,6 +447,8 @@ class PathlineChain:
                 lists = None  # (the attribute tensors live as long as their fields, not until the next pair)
                 for m in maps:  # this pair's samples, from the slab the launches just wrote
                     m.accumulate(ps, n_records=cfg.n_records, seeds=(p == 0), names=names, stream=cs.cuda_stream)
+                for k, it in ints.items():  # ... and this pair's share of every path integral
+                    it.accumulate(ps, k, names=names, n_records=cfg.n_records, stream=cs.cuda_stream)
                 if defer_lines:
                     last = ps.last_points(stream=cs.cuda_stream)
                     done_ev = torch.cuda.Event()
@@ -743,6 +774,45 @@ def snapshot_attr_factory(mesh: DeviceMesh, make_snapshot, names=None):
         a = make_snapshot(i).attributes
         return {k: cell_to_vertex_attr(mesh, a[k]) for k in (sorted(a) if names is None else names)}
     make.names = None if names is None else list(names)
+    return make
+
+
+def derived_attr_factory(mesh: DeviceMesh, fn, names):
+    """``make_attrs`` for PathlineChain whose attributes are derived from each snapshot's FIELD and not read from
+    its files: ``fn(field, i) -> {name: vertex tensor [V, L]}`` is run wherever snapshot i's field is built or
+    refilled, with torch's current stream set to that build stream (so ``fn`` passes no ``stream=`` on: the
+    engine's entries take torch's current one).  ``names`` are the attributes ``fn`` returns.  ``make.seen``
+    lists the snapshots it was called for, in order."""
+    names = list(names)
+
+    def make(i, stream, field=None):
+        if field is None:
+            raise ValueError("a derived make_attrs is called with the snapshot's field (wants_field)")
+        out = fn(field, i)
+        missing = [k for k in names if k not in out]
+        if missing:
+            raise ValueError(f"derived_attr_factory: fn returned no attribute {missing[0]!r}")
+        make.seen.append(i)
+        return {k: out[k] for k in names}
+    make.names = names
+    make.wants_field = True
+    make.seen = []
+    return make
+
+
+def vorticity_deviation_factory(mesh: DeviceMesh, weight=None, name: str = "vorticity_deviation"):
+    """``make_attrs`` that gives every snapshot the vertex array of its vorticity deviation
+    (``engine.vorticity_deviation``: the vorticity minus its ``weight``-ed horizontal mean per level; None =
+    the cell areas) under ``name``: what ``run(attrs=True, integrals={name: PathIntegral})`` integrates into a
+    LAVD map.  ``make.means[i]`` keeps snapshot i's mean [nVertLevels]."""
+    means = {}
+
+    def fn(field, i):
+        dev_v, mean = vorticity_deviation(mesh, field, weight=weight, vertex=True)
+        means[i] = mean
+        return {name: dev_v}
+    make = derived_attr_factory(mesh, fn, [name])
+    make.means = means
     return make
 
 

@@ -1899,3 +1899,169 @@ mops_status mops_ftle_image(const mops_remap_cfg* cfg, const double* d_seeds, co
 }
 
 }  // extern "C"
+
+// ===========================================================================
+// path integrals and LAVD (mops_traj.h): the weighted mean of a cell field per level,
+// the sum of |sample| * weight along a particle's record slots, and the sum as an image.
+//
+// mops_level_mean.  The order of the sum is part of the ABI: groups of MOPS_MEAN_GROUP consecutive cells, each
+// summed in ascending cell order, then the groups in ascending order.  Lanes run over the levels, as in
+// velocity_gradient_kernel: a row of [C][L] is one run of consecutive doubles, and the weight of the row's cell is
+// one wave-uniform word.  Stage 1: one wave per group (and per chunk of 64 levels where L > 64) leaves the group's
+// {num, den} per level in the partials [L][G]; stage 2: one block per level adds that level's partials in
+// ascending g.  No atomics and no hand-off between workgroups: two launches.
+// Self-contained on purpose, as the density and FTLE kernels: no dev:: helper is instantiated here.
+// ===========================================================================
+namespace {
+
+constexpr int kMeanBlock = 64;  // one wave: 64 consecutive levels of one group
+
+static_assert(MOPS_MEAN_GROUP >= 1, "a group holds at least one cell");
+
+__global__ void __launch_bounds__(kMeanBlock) level_mean_group_kernel(int64_t C, int L,
+                                                                      const double* __restrict__ field,
+                                                                      const double* __restrict__ weight,
+                                                                      double* __restrict__ pnum,
+                                                                      double* __restrict__ pden) {
+    const int l = (int)blockIdx.y * kMeanBlock + (int)threadIdx.x;
+    if (l >= L) return;
+    const int64_t g = blockIdx.x;
+    const int64_t c0 = g * MOPS_MEAN_GROUP;
+    const int64_t c1 = c0 + MOPS_MEAN_GROUP < C ? c0 + MOPS_MEAN_GROUP : C;
+    double num = 0.0, den = 0.0;
+#pragma unroll 8
+    for (int64_t c = c0; c < c1; ++c) {
+        const double w = weight[c];
+        const double x = field[c * L + l];
+        if (isfinite(x) && isfinite(w) && w > 0.0) {
+            num = num + (w * x);
+            den = den + w;
+        }
+    }
+    pnum[(int64_t)l * gridDim.x + g] = num;  // [L][G]: a level's partials are one run for the second stage
+    pden[(int64_t)l * gridDim.x + g] = den;
+}
+
+// One block per level: its G partials (a contiguous run of [L][G]) go through LDS a tile at a time, loaded by the
+// whole block so that a tile's loads are in flight together, and thread 0 adds a tile in ascending g -- the order
+// is the ABI's, only the loads are spread.  (One lane per level reading [G][L] rows in a loop was measured first:
+// a chain of dependent-latency loads, most of the entry's 0.68 ms at 235 567 x 60)
+constexpr int kMeanTotalBlock = 256;
+constexpr int kMeanTile = 2048;  // partials of one level per tile: 2 x 16 KB of LDS
+
+__global__ void __launch_bounds__(kMeanTotalBlock) level_mean_total_kernel(int64_t G, const double* __restrict__ pnum,
+                                                                           const double* __restrict__ pden,
+                                                                           double* __restrict__ mean,
+                                                                           double* __restrict__ wsum) {
+    __shared__ double sn[kMeanTile], sd[kMeanTile];
+    const int l = (int)blockIdx.x;
+    const double* rn = pnum + (int64_t)l * G;
+    const double* rd = pden + (int64_t)l * G;
+    double num = 0.0, den = 0.0;
+    for (int64_t g0 = 0; g0 < G; g0 += kMeanTile) {
+        const int cnt = (int)(G - g0 < kMeanTile ? G - g0 : kMeanTile);
+        for (int k = (int)threadIdx.x; k < cnt; k += kMeanTotalBlock) {
+            sn[k] = rn[g0 + k];
+            sd[k] = rd[g0 + k];
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+#pragma unroll 8
+            for (int k = 0; k < cnt; ++k) {
+                num = num + sn[k];
+                den = den + sd[k];
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        mean[l] = den == 0.0 ? std::numeric_limits<double>::quiet_NaN() : num / den;
+        wsum[l] = den;
+    }
+}
+
+// one lane per slot; ids are a permutation, so every accumulator element has one writer
+__global__ void __launch_bounds__(256) path_integral_abs_kernel(int64_t n, int64_t k_begin, int64_t k_end,
+                                                                const double* __restrict__ values, int64_t vk,
+                                                                int64_t vi, const int32_t* __restrict__ ids,
+                                                                double weight, double* __restrict__ accum) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t id = ids ? (int64_t)ids[i] : i;
+    const double* v = values + i * vi;
+    double s = accum[id];
+    for (int64_t k = k_begin; k < k_end; ++k) s = s + (fabs(v[k * vk]) * weight);
+    accum[id] = s;
+}
+
+__global__ void __launch_bounds__(256) path_integral_image_kernel(int64_t n, const double* __restrict__ accum,
+                                                                  const int32_t* __restrict__ death, double horizon,
+                                                                  double2* __restrict__ img) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    const double s = accum[g];
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    double2 xy, za;
+    za.y = 1.0;
+    if ((death && death[g] >= 0) || !isfinite(s)) {
+        xy.x = nan; xy.y = nan; za.x = nan;
+    } else {
+        xy.x = s; xy.y = s / horizon; za.x = 0.0;
+    }
+    img[2 * g] = xy;
+    img[2 * g + 1] = za;
+}
+
+}  // namespace
+
+extern "C" {
+
+mops_status mops_level_mean(int64_t n_cells, int32_t n_levels, const double* d_field, const double* d_weight,
+                            double* d_mean, double* d_wsum, void* stream) {
+    if (!d_field || !d_weight || !d_mean || !d_wsum) return fail(MOPS_ERR_INVALID, "mops_level_mean: null argument");
+    if (n_cells < 1 || n_levels < 1) return fail(MOPS_ERR_INVALID, "mops_level_mean: n_cells or n_levels below 1");
+    const int64_t G = (n_cells + MOPS_MEAN_GROUP - 1) / MOPS_MEAN_GROUP;
+    const int64_t chunks = ((int64_t)n_levels + kMeanBlock - 1) / kMeanBlock;
+    if (G > 0x7fffffffLL || chunks > 65535)
+        return fail(MOPS_ERR_INVALID, "mops_level_mean: too many cells or levels for one launch");
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf part;  // pnum [L][G] | pden [L][G]
+    HIP_TRY(part.alloc((size_t)G * (size_t)n_levels * 2 * sizeof(double)));
+    double* pnum = part.as<double>();
+    double* pden = pnum + (size_t)G * (size_t)n_levels;
+    level_mean_group_kernel<<<dim3((unsigned)G, (unsigned)chunks), kMeanBlock, 0, s>>>(n_cells, n_levels, d_field,
+                                                                                       d_weight, pnum, pden);
+    level_mean_total_kernel<<<(unsigned)n_levels, kMeanTotalBlock, 0, s>>>(G, pnum, pden, d_mean, d_wsum);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // the partials are freed on return
+    if (e != hipSuccess) return fail(MOPS_ERR_HIP, std::string("mops_level_mean: ") + hipGetErrorString(e));
+    return MOPS_OK;
+}
+
+mops_status mops_path_integral_abs(int64_t n, int64_t k_begin, int64_t k_end, const double* d_values, int64_t vk,
+                                   int64_t vi, const int32_t* d_ids, double weight, double* d_accum, void* stream) {
+    if (!d_values || !d_accum) return fail(MOPS_ERR_INVALID, "mops_path_integral_abs: null argument");
+    if (n < 1 || n > (int64_t)0x7fffffff * 256) return fail(MOPS_ERR_INVALID, "mops_path_integral_abs: invalid n");
+    if (k_begin < 0 || k_end < k_begin) return fail(MOPS_ERR_INVALID, "mops_path_integral_abs: invalid slot range");
+    if (!std::isfinite(weight) || weight < 0.0)
+        return fail(MOPS_ERR_INVALID, "mops_path_integral_abs: the weight must be finite and not negative");
+    if (k_begin == k_end) return MOPS_OK;
+    path_integral_abs_kernel<<<grid_for(n), 256, 0, (hipStream_t)stream>>>(n, k_begin, k_end, d_values, vk, vi, d_ids,
+                                                                           weight, d_accum);
+    HIP_TRY(hipGetLastError());
+    return MOPS_OK;
+}
+
+mops_status mops_path_integral_image(int64_t n, const double* d_accum, const int32_t* d_death, double horizon,
+                                     double* d_image, void* stream) {
+    if (!d_accum || !d_image) return fail(MOPS_ERR_INVALID, "mops_path_integral_image: null argument");
+    if (n < 1 || n > (int64_t)0x7fffffff * 256) return fail(MOPS_ERR_INVALID, "mops_path_integral_image: invalid n");
+    if (!std::isfinite(horizon) || !(horizon > 0.0))
+        return fail(MOPS_ERR_INVALID, "mops_path_integral_image: the horizon must be finite and positive");
+    path_integral_image_kernel<<<grid_for(n), 256, 0, (hipStream_t)stream>>>(n, d_accum, d_death, horizon,
+                                                                             (double2*)d_image);
+    HIP_TRY(hipGetLastError());
+    return MOPS_OK;
+}
+
+}  // extern "C"

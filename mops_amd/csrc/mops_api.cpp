@@ -66,10 +66,13 @@ struct App {
     int front_id = 0;  // the solution behind `front` (its attributes feed the remapping)
     int back_id = 0;   // the solution behind `back` (attribute sampling along pathlines)
     std::map<int, double*> eddy;  // solID -> vorticity | okubo_weiss vertex arrays [2][V*L] (MOPS_RunEddyMap)
+    std::map<int, double*> lavd;  // solID -> the vorticity deviation's vertex array [V*L] (MOPS_RunLAVD)
 
     void release() {
         for (auto& kv : eddy) (void)hipFree(kv.second);
         eddy.clear();
+        for (auto& kv : lavd) (void)hipFree(kv.second);
+        lavd.clear();
         for (auto& kv : fields) mops_field_destroy(kv.second);
         fields.clear();
         if (mesh) mops_mesh_destroy(mesh);
@@ -831,6 +834,122 @@ ImageBuffer<double> MOPS_RunFTLE(const std::vector<TrajectoryLine>& lines, Visua
     check(mops_ftle_image(&cfg, d_seeds, d_seeds + 3 * n, nullptr, horizon, wrap, d_img, nullptr), "mops_ftle_image");
     ImageBuffer<double> img(W, H);
     hip(hipMemcpy(img.mPixels.data(), d_img, px * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy image");
+    return img;
+}
+
+namespace {
+
+// The vorticity deviation of solution `id` as a signed vertex array [V*L] on the device, once per solution id:
+// mops_velocity_gradient's vorticity, minus mops_level_mean of it under mops_cell_area's weights (one IEEE
+// subtraction per element, on the host), through mops_cell_to_vertex_signed.
+const double* lavd_vertex_attr(int id, mops_field* field) {
+    auto cached = g_app.lavd.find(id);
+    if (cached != g_app.lavd.end()) return cached->second;
+    auto hip = [](hipError_t e, const char* what) {
+        if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+    };
+    struct DevBuf {
+        void* p = nullptr;
+        ~DevBuf() { (void)hipFree(p); }
+    } cell, vert;  // vorticity [C*L] | area [C] | mean [L] | wsum [L]; the vertex array
+    const size_t C = g_app.grid->mCellsSize, L = g_app.grid->mVertLevels, CL = C * L,
+                 VL = (size_t)g_app.grid->mVertexSize * L;
+    hip(hipMalloc(&cell.p, (CL + C + 2 * L) * sizeof(double)), "MOPS_RunLAVD: hipMalloc");
+    hip(hipMalloc(&vert.p, VL * sizeof(double)), "MOPS_RunLAVD: hipMalloc");
+    double* d_vort = static_cast<double*>(cell.p);
+    double* d_area = d_vort + CL;
+    double* d_mean = d_area + C;
+    check(mops_velocity_gradient(g_app.mesh, field, d_vort, nullptr, nullptr, nullptr, nullptr), "mops_velocity_gradient");
+    check(mops_cell_area(g_app.mesh, d_area, nullptr), "mops_cell_area");
+    check(mops_level_mean((int64_t)C, (int32_t)L, d_vort, d_area, d_mean, d_mean + L, nullptr), "mops_level_mean");
+    std::vector<double> vort(CL), mean(L);
+    hip(hipMemcpy(vort.data(), d_vort, CL * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy vorticity");
+    hip(hipMemcpy(mean.data(), d_mean, L * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy mean");
+    for (size_t c = 0; c < C; ++c)
+        for (size_t l = 0; l < L; ++l) vort[c * L + l] = vort[c * L + l] - mean[l];
+    hip(hipMemcpy(d_vort, vort.data(), CL * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy deviation");
+    check(mops_cell_to_vertex_signed(g_app.mesh, d_vort, static_cast<double*>(vert.p), nullptr),
+          "mops_cell_to_vertex_signed");
+    hip(hipDeviceSynchronize(), "MOPS_RunLAVD");
+    double* out = static_cast<double*>(vert.p);
+    g_app.lavd.emplace(id, out);
+    vert.p = nullptr;
+    return out;
+}
+
+}  // namespace
+
+ImageBuffer<double> MOPS_RunLAVD(VisualizationSettings* config, TrajectorySettings* traj) {
+    ScopedTimer t("GPUKernel::LAVD", "GPUKernel");
+    if (config == nullptr || traj == nullptr || g_app.mesh == nullptr || g_app.front == nullptr ||
+        g_app.back == nullptr) {
+        Error("[MI355X::LAVD] invalid inputs: it needs both settings and an active front / back pair");
+        return ImageBuffer<double>();
+    }
+    if (traj->fixedLayer >= 0) {
+        Error("[MI355X::LAVD] attributes are not sampled with fixedLayer");
+        return ImageBuffer<double>();
+    }
+    if (traj->relocateStages) {
+        Error("[MI355X::LAVD] attributes are not sampled with relocateStages");
+        return ImageBuffer<double>();
+    }
+    if (!(traj->diffusivity == 0.0)) {
+        Error("[MI355X::LAVD] attributes are not sampled with diffusivity > 0");
+        return ImageBuffer<double>();
+    }
+    mops_traj_cfg cfg{(int64_t)traj->deltaT, (int64_t)traj->simulationDuration, (int64_t)traj->recordT,
+                      traj->directionType == CalcDirection::kForward ? MOPS_FORWARD : MOPS_BACKWARD,
+                      traj->methodType == CalcMethodType::kEuler ? MOPS_EULER : MOPS_RK4};
+    const int64_t K = mops_traj_num_records(&cfg), steps = mops_traj_num_steps(&cfg);
+    if (K <= 0 || steps <= 0) {
+        Error("[MI355X::LAVD] invalid trajectory settings");
+        return ImageBuffer<double>();
+    }
+    const int W = (int)config->imageSize.x, H = (int)config->imageSize.y;
+    if (W <= 0 || H <= 0 || (int64_t)W * H >= (1LL << 31)) {
+        Error("[MI355X::LAVD] invalid inputs");
+        return ImageBuffer<double>();
+    }
+    mops_remap_cfg rc{};
+    rc.width = W; rc.height = H;
+    rc.min_lat = config->LatRange.x; rc.max_lat = config->LatRange.y;
+    rc.min_lon = config->LonRange.x; rc.max_lon = config->LonRange.y;
+    auto hip = [](hipError_t e, const char* what) {
+        if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+    };
+    struct DevBuf {
+        void* p = nullptr;
+        ~DevBuf() { (void)hipFree(p); }
+    } buf;  // image [n][4] | seeds [n][3] | attribute lines [n][K+1] | sums [n] | death steps [n] (int32)
+    const size_t n = (size_t)W * H, P = (size_t)K + 1;
+    hip(hipMalloc(&buf.p, (n * 4 + n * 3 + n * P + n) * sizeof(double) + n * sizeof(int32_t)), "MOPS_RunLAVD: hipMalloc");
+    double* d_img = static_cast<double*>(buf.p);
+    double* d_seeds = d_img + n * 4;
+    double* d_lines = d_seeds + n * 3;
+    double* d_sum = d_lines + n * P;
+    int32_t* d_death = reinterpret_cast<int32_t*>(d_sum + n);
+    check(mops_flowmap_lattice(&rc, d_seeds, nullptr), "mops_flowmap_lattice");
+    std::vector<double> seeds(n * 3);
+    hip(hipMemcpy(seeds.data(), d_seeds, seeds.size() * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy seeds");
+    const double* d_fa[1] = {lavd_vertex_attr(g_app.front_id, g_app.front)};
+    const double* d_ba[1] = {lavd_vertex_attr(g_app.back_id, g_app.back)};
+    std::vector<double> hp(n * P * 3), lines(n * P);
+    std::vector<int32_t> death(n);
+    check(mops_run_pathline_attrs(g_app.mesh, g_app.front, g_app.back, &cfg, (int64_t)n, seeds.data(), nullptr,
+                                  (float)config->FixedDepth, nullptr, hp.data(), nullptr, nullptr, nullptr, nullptr,
+                                  nullptr, nullptr, death.data(), 1, d_fa, d_ba, lines.data(), nullptr),
+          "mops_run_pathline_attrs");
+    hip(hipMemcpy(d_lines, lines.data(), lines.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy lines");
+    hip(hipMemcpy(d_death, death.data(), n * sizeof(int32_t), hipMemcpyHostToDevice), "hipMemcpy death steps");
+    hip(hipMemset(d_sum, 0, n * sizeof(double)), "hipMemset");
+    const double record_s = std::fabs((double)cfg.record_t);
+    check(mops_path_integral_abs((int64_t)n, 0, K, d_lines, 1, (int64_t)P, nullptr, record_s, d_sum, nullptr),
+          "mops_path_integral_abs");
+    check(mops_path_integral_image((int64_t)n, d_sum, d_death, (double)K * record_s, d_img, nullptr),
+          "mops_path_integral_image");
+    ImageBuffer<double> img(W, H);
+    hip(hipMemcpy(img.mPixels.data(), d_img, n * 4 * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy image");
     return img;
 }
 

@@ -1157,6 +1157,66 @@ def cell_area(mesh: DeviceMesh, stream=None):
     return out
 
 
+def level_mean(field, weight, stream=None):
+    """The weighted mean of a cell field per level (mops_level_mean; the order of its sum is stated in
+    include/mops_traj.h): ``field`` a float64 CUDA tensor [C, L], ``weight`` a float64 CUDA tensor [C].  A term
+    counts where the field value and the weight are finite and the weight is positive, so a caller confines the
+    mean to a window or basin by zeroing weights.  Returns ``(mean [L], wsum [L])`` as float64 CUDA tensors; the
+    mean of a level without a counting cell is NaN and its ``wsum`` 0.  Mesh-free: any [C, L].  The library call
+    runs on ``stream`` (default torch's current one) and synchronises it (the group partials are a temporary
+    allocation of the call)."""
+    import torch
+    for t, name, nd in ((field, "field", 2), (weight, "weight", 1)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+                and t.dim() == nd):
+            raise ValueError(f"level_mean: {name} must be a contiguous float64 CUDA tensor "
+                             f"{'[C, L]' if nd == 2 else '[C]'}")
+    C_, L_ = int(field.shape[0]), int(field.shape[1])
+    if C_ < 1 or L_ < 1 or int(weight.shape[0]) != C_ or weight.device != field.device:
+        raise ValueError("level_mean: field [C, L] and weight [C] with C, L >= 1 on one device")
+    with torch.cuda.device(field.device):
+        mean = torch.empty((L_,), dtype=torch.float64, device=field.device)
+        wsum = torch.empty((L_,), dtype=torch.float64, device=field.device)
+        L.check(L.load().mops_level_mean(C_, L_, _tensor_ptr(field), _tensor_ptr(weight), _tensor_ptr(mean),
+                                         _tensor_ptr(wsum), _stream_or_current(stream, field.device)),
+                "mops_level_mean")
+    return mean, wsum
+
+
+def vorticity_deviation(mesh: DeviceMesh, field: DeviceField, weight=None, vertex: bool = True, stream=None):
+    """``(deviation, mean)``: the relative vorticity of ``velocity_gradient`` minus its weighted horizontal mean
+    per level (``level_mean``), the integrand of the Lagrangian-averaged vorticity deviation; ``mean`` is the
+    float64 CUDA tensor [nVertLevels] that was subtracted.  ``weight`` [nCells]: None = ``cell_area(mesh)``; a
+    caller confines the mean to a window or basin by zeroing weights.  ``vertex`` (the default): the deviation as
+    [nVertices, nVertLevels] through ``cell_to_vertex_attr(signed=True)``'s interpolation, ready for the
+    samplers; else [nCells, nVertLevels].  All of it runs on ``stream`` (default torch's current one); the
+    subtraction is one IEEE operation per element, a torch broadcast under that stream."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    h = _current_or(stream, dev)
+    vort = velocity_gradient(mesh, field, "vorticity", stream=h)["vorticity"]
+    own_weight = weight is None
+    if own_weight:
+        weight = cell_area(mesh, stream=h)
+    elif not (isinstance(weight, torch.Tensor) and weight.is_cuda and weight.dtype == torch.float64
+              and weight.is_contiguous() and weight.numel() == mesh.nCells):
+        raise ValueError("vorticity_deviation: weight must be a contiguous float64 CUDA tensor [nCells]")
+    mean, _ = level_mean(vort, weight.reshape(-1), stream=h)
+    dev_c = torch.empty_like(vort)
+    with _on_stream(h):
+        torch.sub(vort, mean[None, :], out=dev_c)
+    _release_on(vort, stream)
+    if own_weight:
+        _release_on(weight, stream)
+    if not vertex:
+        return dev_c, mean
+    vt = torch.empty((mesh.nVertices, mesh.nVertLevels), dtype=torch.float64, device=dev)
+    L.check(L.load().mops_cell_to_vertex_signed(mesh.handle, _tensor_ptr(dev_c), _tensor_ptr(vt), _stream_handle(h)),
+            "mops_cell_to_vertex_signed")
+    _release_on(dev_c, stream)
+    return vt, mean
+
+
 def eddy_classify(mesh: DeviceMesh, okubo_weiss, vorticity, layer: int, threshold: float, stream=None):
     """+1 / -1 / 0 per cell at ``layer`` (mops_eddy_classify): Okubo-Weiss below ``threshold`` and vorticity
     positive / negative / anything else (NaN is class 0).  The arrays are ``velocity_gradient``'s
@@ -1606,6 +1666,85 @@ class DensityMap:
         return img
 
 
+class PathIntegral:
+    """The integral of |a sampled attribute| along each particle's path (mops_path_integral_abs,
+    include/mops_traj.h "path integrals and LAVD"): ``accum`` is a float64 CUDA tensor [n] indexed by particle
+    id (seed order), whatever order the particle set keeps its slots in.
+
+    The rule is a rectangle rule: slot j of a pair's attribute slab is sampled at the start of step
+    (j+1)*ri - 1 (ri = recordT / deltaT steps) and stands for one record interval, so a pair adds
+    sum_j |sample_j| * |recordT| seconds, in ascending j, onto what the accumulator holds: a chain that
+    accumulates pair by pair equals one long ascending sum.  A particle's slots after its death hold the
+    reference's zeros and add nothing; a consumer masks such a particle (``FlowMapLattice.lavd(death=)``).  A
+    non-finite sample makes the sum non-finite."""
+
+    def __init__(self, n: int, device=None):
+        import torch
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"PathIntegral: n {n} < 1")
+        self.torch = torch
+        self.n = n
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.accum = torch.zeros((n,), dtype=torch.float64, device=self.device)
+
+    def reset(self):
+        """Zero the accumulator: a torch fill on torch's *current* stream (there is no ``stream=``), as
+        ``DensityMap.reset``."""
+        self.accum.zero_()
+
+    @staticmethod
+    def _weight(weight):
+        weight = float(weight)
+        if not (np.isfinite(weight) and weight >= 0.0):
+            raise ValueError(f"PathIntegral: the weight must be finite and >= 0, not {weight!r}")
+        return weight
+
+    def _call(self, n, k0, k1, values_ptr, vk, vi, ids_ptr, weight, stream):
+        with self.torch.cuda.device(self.device):
+            L.check(L.load().mops_path_integral_abs(
+                int(n), int(k0), int(k1), C.c_void_p(values_ptr), int(vk), int(vi),
+                None if ids_ptr is None else C.c_void_p(ids_ptr), weight, _tensor_ptr(self.accum),
+                _stream_or_current(stream, self.device)), "mops_path_integral_abs")
+
+    def accumulate(self, ps: "ParticleSet", name: str, names=None, n_records: int | None = None, weight=None,
+                   stream=None):
+        """Add slots [0, n_records) (default ``ps.K``) of the attribute ``name`` from ``ps.attr_records``, each
+        times ``weight`` (default |recordT| seconds of ``ps.cfg``: the rectangle rule above), onto ``accum`` at
+        ``ps.ids``, on ``stream`` (default torch's current one), without a host synchronisation.  ``names`` lists
+        the sampled attributes in slab order, exactly as ``DensityMap.accumulate`` finds its row.  ValueError
+        where the set samples no such attribute."""
+        if ps.n != self.n:
+            raise ValueError("PathIntegral: the particle set has another particle count")
+        k1 = ps.K if n_records is None else int(n_records)
+        names = list(names) if names is not None else ["salinity", "temperature"][:ps.n_attr]
+        if ps.attr_records is None or name not in names or names.index(name) >= ps.n_attr:
+            raise ValueError(f"PathIntegral: the particle set samples no attribute {name!r}")
+        if k1 < 0 or k1 > ps.attr_records.shape[0]:
+            raise ValueError(f"record range [0, {k1}) outside the slab's {ps.attr_records.shape[0]} slots")
+        weight = self._weight(abs(int(ps.cfg.recordT)) if weight is None else weight)
+        self._call(ps.n, 0, k1, ps.attr_records.data_ptr() + 8 * names.index(name) * ps.rec_stride,
+                   ps.n_attr * ps.rec_stride, 1, ps.ids.data_ptr(), weight, stream)
+
+    def accumulate_lines(self, values, weight, skip_last: bool = True):
+        """Add the samples of finished attribute lines ``values`` [n, P] (seed order; CUDA tensor or host array)
+        of a SINGLE pair, each times ``weight``, on torch's current stream.  ``skip_last`` (the default) drops
+        entry K = P - 1, the 0 the reference appends to an attribute line (mops_traj_finalize_attrs), so the
+        sum runs over the pair's K slots as ``accumulate`` does.  Lines concatenated over a chain do not
+        qualify: later pairs drop their slot 0 there (the reference's caller removes each later pair's first
+        sample), so the concatenation no longer holds every slot; accumulate a chain pair by pair
+        (``PathlineChain.run(integrals=)``)."""
+        torch = self.torch
+        val = torch.as_tensor(values, dtype=torch.float64).to(self.device).contiguous()
+        if val.dim() != 2 or int(val.shape[0]) != self.n:
+            raise ValueError(f"accumulate_lines: values must be [{self.n}, P]")
+        P = int(val.shape[1])
+        k1 = P - 1 if skip_last else P
+        if k1 < 0:
+            raise ValueError("accumulate_lines: no samples")
+        self._call(self.n, 0, k1, val.data_ptr(), 1, P, None, self._weight(weight), None)
+
+
 class FlowMapLattice:
     """One particle per pixel of a ``width`` x ``height`` lat / lon window, and the FTLE image of their flow map
     ("flow-map lattices and FTLE", include/mops_traj.h).
@@ -1678,3 +1817,33 @@ class FlowMapLattice:
         last = ps.last_points(stream=h)
         _release_on(last, stream)
         return self.ftle(last, ps.original(ps.death, stream=h), horizon, stream=h)
+
+    def lavd(self, integral, death=None, horizon: float = 1.0, stream=None):
+        """The LAVD image (mops_path_integral_image) of a ``PathIntegral`` of this lattice's particles (or its
+        ``accum``-like float64 tensor [height * width] in seed order): a float64 CUDA image [height, width, 4] =
+        {LAVD, LAVD / horizon, 0, 1}, NaN in channels 0-2 where ``death`` [height * width] is >= 0 or the sum is
+        not finite.  ``horizon`` > 0 is in SECONDS here (``ftle`` takes days): with the integral of the
+        vorticity deviation under ``PathIntegral``'s rectangle rule -- one record interval of |recordT| seconds
+        per slot -- channel 1 is the mean |deviation| along the path in 1/s.  The stream contract is ``ftle``'s:
+        the kernel and the torch copies that bring an input into its form run on ``stream`` (default torch's
+        current one); CUDA inputs are ordered on that stream by the caller; the image is allocated under torch's
+        current stream."""
+        torch = self.torch
+        horizon = float(horizon)
+        if not (np.isfinite(horizon) and horizon > 0.0):
+            raise ValueError("lavd: the horizon must be finite and positive")
+        acc = integral.accum if isinstance(integral, PathIntegral) else integral
+        with _on_stream(stream):
+            acc = torch.as_tensor(acc, dtype=torch.float64).to(self.device).contiguous()
+            if death is not None:
+                death = torch.as_tensor(death).to(device=self.device, dtype=torch.int32).contiguous()
+        if acc.numel() != self.n:
+            raise ValueError(f"lavd: the integral must be [{self.n}]")
+        if death is not None and death.numel() != self.n:
+            raise ValueError(f"lavd: death must be [{self.n}]")
+        with torch.cuda.device(self.device):
+            img = torch.empty((self.height, self.width, 4), dtype=torch.float64, device=self.device)
+            L.check(L.load().mops_path_integral_image(self.n, _tensor_ptr(acc), _tensor_ptr(death), horizon,
+                                                      _tensor_ptr(img), _stream_or_current(stream, self.device)),
+                    "mops_path_integral_image")
+        return img

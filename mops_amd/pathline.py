@@ -132,9 +132,11 @@ class MOPSPathline:
             raise RuntimeError("follow_last=True but last_pts is None")
         return self._last_pt.copy()
 
-    def _make_chain(self, sample_attributes: bool = False):
+    def _make_chain(self, sample_attributes: bool = False, derived_attrs=None):
         """The PathlineChain over the month pairs' snapshots: timestamps read ahead, the mesh uploaded at the
-        first call, each snapshot read from its file and derived on the device when its pair needs it."""
+        first call, each snapshot read from its file and derived on the device when its pair needs it.
+        ``derived_attrs(mesh) -> make_attrs``: attributes derived from each snapshot's field instead of read from
+        its file (chain.derived_attr_factory; the mesh exists only here)."""
         from .chain import PathlineChain
         from .engine import DeviceField, DeviceMesh, cell_to_vertex_attr
         from .mpas import MPASOReader, mesh_from_reader, snapshot_from_reader
@@ -159,8 +161,10 @@ class MOPSPathline:
         def make_attrs(i, stream):  # (called right after make_field(i), on the same stream)
             return {k: cell_to_vertex_attr(self._mesh, v) for k, v in cell_attrs.pop(i).items()}
 
+        if derived_attrs is not None:
+            make_attrs = derived_attrs(self._mesh)
         return PathlineChain(self._mesh, make_field, len(dates), timestamps=stamps, device=self.device,
-                             make_attrs=make_attrs if sample_attributes else None)
+                             make_attrs=make_attrs if (sample_attributes or derived_attrs is not None) else None)
 
     def run(self, method: str = "rk4", delta_minutes: int = 1, record_every_minutes: int = 6,
             sample_attributes: bool = False, density=None, layer: int | None = None, diffusivity: float = 0.0,
@@ -252,3 +256,40 @@ class MOPSPathline:
                         follow_last=True, keep_lines=False, on_pair=ever, layer=layer, diffusivity=diffusivity,
                         seed=seed)
         return lattice.ftle(res["lastPoint"], ever.death(), horizon=float(horizon_days))
+
+    def lavd(self, width: int, height: int, lat_range, lon_range, depth: float, method: str = "euler",
+             delta_minutes: int = 1, record_every_minutes: int = 60, horizon_days: float | None = None,
+             mean_weight=None):
+        """The LAVD image of the month pairs set by ``set_time``: the Lagrangian-averaged vorticity deviation, the
+        integral of |vorticity - its horizontal mean| along the pathline of one particle per pixel of the
+        ``width`` x ``height`` window (engine.FlowMapLattice: the pixel positions of a ``MOPS_RunRemapping`` image
+        and of ``ftle`` of the same window), seeded at ``depth`` and integrated through every pair as one
+        device-resident chain that keeps no lines.  FTLE shows the transport barriers, LAVD the coherent cores
+        they enclose.  Every snapshot's vorticity deviation (engine.vorticity_deviation) is derived from its field
+        on the device and sampled inside the trajectory launches; the integral is engine.PathIntegral's
+        rectangle rule: slot j of a pair is sampled at the start of step (j+1)*ri - 1 (ri =
+        record_every_minutes / delta_minutes) and stands for one record interval.  Returns a float64 CUDA
+        tensor [height, width, 4] = {LAVD (dimensionless), mean |deviation| in 1/s, 0, 1}, NaN for a particle
+        that died in any pair (chain.EverDead; land included): its later slots hold zeros and would dilute the
+        integral.  ``horizon_days``: the time channel 1 is divided by (default: the sum of the pair gaps).
+        ``mean_weight``: the float64 CUDA tensor [nCells] the horizontal mean is weighted with (default: the cell
+        areas); zero weights confine the mean to a window or basin.  ``method``: "euler" (the default) or
+        "rk4" -- the reference's RK4 kills a particle at its first cell crossing (quirk Q1), which leaves a
+        mostly-NaN map; "rk4_relocate" is refused with the chain's own message, because the samplers refuse
+        it.  Does not touch the state ``run`` keeps between calls (seeds, last points)."""
+        from .chain import EverDead, vorticity_deviation_factory
+        from .engine import FlowMapLattice, PathIntegral
+        meth = {"rk4": L.MOPS_RK4, "rk4_relocate": L.MOPS_RK4_RELOCATE}.get(method.lower(), L.MOPS_EULER)
+        name = "vorticity_deviation"
+        chain = self._make_chain(False, derived_attrs=lambda mesh: vorticity_deviation_factory(mesh, mean_weight, name))
+        if horizon_days is None:
+            horizon_days = sum(chain.gaps) / 86400.0
+        lattice = FlowMapLattice(width, height, lat_range, lon_range, device=self.device)
+        integral = PathIntegral(lattice.n, device=self.device)
+        ever = EverDead()
+        chain.run(lattice.seeds, depth=float(depth), method=meth,
+                  delta_t=int(delta_minutes) * self._one_min,
+                  record_t=int(record_every_minutes) * self._one_min,
+                  direction=L.MOPS_FORWARD if self.direction == "forward" else L.MOPS_BACKWARD,
+                  follow_last=True, keep_lines=False, on_pair=ever, attrs=True, integrals={name: integral})
+        return lattice.lavd(integral, ever.death(), horizon=float(horizon_days) * 86400.0)

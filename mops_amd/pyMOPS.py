@@ -27,6 +27,8 @@ and, beyond the pybind module, the image output of the reference's C++ side:
     MOPS_LatticeSeeds(config)                  extension: one seed per pixel of the window, (H*W, 3)
     MOPS_RunFTLE(lines, config, horizon)       extension: the FTLE image of lines seeded on that lattice,
                                                (H, W, 4) float64 {ftle, lambda_max, lambda_min, 1}
+    MOPS_RunLAVD(config, traj)                 extension: the Lagrangian-averaged vorticity deviation over the active
+                                               pair on that lattice, (H, W, 4) float64 {LAVD, mean, 0, 1}
     MOPS_RunRemappingSection(config)           extension: a vertical section along config.SectionPath,
                                                [ (H, W, 4) float64 ] {zonal, meridional, across, 1} and
                                                {attr0, attr1, 0, 1}
@@ -435,6 +437,7 @@ class _App:
         self.back_id = None
         self.vertex_attrs = {}  # solID -> {name: the attribute's vertex array (device)}, built on first use
         self.eddy_attrs = {}    # solID -> (vorticity, okubo_weiss) vertex arrays (device), built on first use
+        self.lavd_attrs = {}    # solID -> the vorticity deviation's vertex array (device), built on first use
 
 
 _app = _App()
@@ -955,6 +958,61 @@ def MOPS_RunFTLE(lines, config: VisualizationSettings, horizon: float):
                 last[i] = np.asarray(ln["lastPoint"], dtype=np.float64).reshape(3)
         lat.seeds.copy_(lat.torch.as_tensor(seeds))  # points[0] of each line (the lattice seed itself, from a run)
         return lat.ftle(last, None, hz).cpu().numpy()
+
+
+def _lavd_vertex_attr(sol_id):
+    """The vorticity deviation of one solution as a signed vertex array on the device
+    (``engine.vorticity_deviation``: area-weighted mean), built once per solution id, like ``_eddy_vertex_attrs``."""
+    if sol_id not in _app.lavd_attrs:
+        _app.lavd_attrs[sol_id] = _E.vorticity_deviation(_app.mesh, _app.fields[sol_id], vertex=True)[0]
+    return _app.lavd_attrs[sol_id]
+
+
+LAVD_ATTRIBUTE = "vorticity_deviation"
+
+
+def MOPS_RunLAVD(config: VisualizationSettings, traj: TrajectorySettings):
+    """Extension ("path integrals and LAVD", include/mops_traj.h): the Lagrangian-averaged vorticity deviation
+    over the active front / back pair.  One particle per pixel of ``config``'s window (MOPS_LatticeSeeds) at
+    ``config.FixedDepth`` runs one pathline with ``traj``'s deltaT, simulationDuration, recordT, direction and
+    method; each solution's vorticity deviation (its vorticity minus the area-weighted mean of its level) is the
+    single sampled attribute, and the sampled line is summed with the rectangle rule -- slot j, sampled at the
+    start of step (j+1)*ri - 1, times recordT seconds (engine.PathIntegral.accumulate_lines).  One [H, W, 4]
+    float64 array {LAVD, mean |deviation| in 1/s over K * recordT seconds, 0, 1}, NaN where the particle died
+    (land included), usable with SaveToPNG and SaveVTI; it overlays the velocity, density, FTLE and eddy images
+    of the same window.  kRK4 evaluates its stages in the step's start cell (quirk Q1) and leaves a mostly-NaN
+    map.  Invalid inputs -- no back solution, ``fixedLayer`` >= 0, ``relocateStages``, ``diffusivity`` > 0, bad
+    sizes or trajectory settings -- answer Error() and return an empty image."""
+    with _Timer("GPUKernel::LAVD", "GPUKernel"):
+        empty = np.zeros((0, 0, 4))
+        if traj is None or _app.mesh is None or _app.front is None or _app.back is None:
+            _error("[MI355X::LAVD] invalid inputs: it needs a TrajectorySettings and an active front / back pair")
+            return empty
+        if int(getattr(traj, "fixedLayer", -1)) >= 0:
+            _error("[MI355X::LAVD] attributes are not sampled with fixedLayer")
+            return empty
+        if getattr(traj, "relocateStages", False):
+            _error("[MI355X::LAVD] attributes are not sampled with relocateStages")
+            return empty
+        kh = float(getattr(traj, "diffusivity", 0.0))
+        if not kh == 0.0:
+            _error("[MI355X::LAVD] attributes are not sampled with diffusivity > 0")
+            return empty
+        cfg = _E.TrajectoryConfig(deltaT=int(traj.deltaT), simulationDuration=int(traj.simulationDuration),
+                                  recordT=int(traj.recordT), depth=float(np.float32(config.FixedDepth))
+                                  if config is not None else 0.0, direction=int(traj.directionType),
+                                  method=int(traj.methodType))
+        if cfg.n_records <= 0 or cfg.n_steps <= 0:
+            _error("[MI355X::LAVD] invalid trajectory settings")
+            return empty
+        lat = _lattice(config, "LAVD")
+        if lat is None:
+            return empty
+        attrs = {LAVD_ATTRIBUTE: (_lavd_vertex_attr(_app.front_id), _lavd_vertex_attr(_app.back_id))}
+        r = _E.run_trajectories(_app.mesh, _app.front, _app.back, cfg, lat.seeds.cpu().numpy(), attrs=attrs)
+        integral = _E.PathIntegral(lat.n)
+        integral.accumulate_lines(r["attributes"][LAVD_ATTRIBUTE], float(abs(cfg.recordT)))
+        return lat.lavd(integral, r["death_step"], horizon=float(cfg.n_records * abs(cfg.recordT))).cpu().numpy()
 
 
 def SaveToPNG(image, filename: str, channel: int = 3) -> bool:
