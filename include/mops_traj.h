@@ -100,8 +100,12 @@ typedef struct {
     int32_t* d_cell;                     /* in: seed cell (default_cell_id), then current cell */
     int32_t* d_death_step;               /* out: -1 alive, else the step it died at */
     const int32_t* d_order;              /* optional processing order (slot -> particle index),
-                                            from mops_order_particles; NULL = identity.  Only
-                                            affects speed, never results. */
+                                            from mops_order_particles; NULL = identity.  Never
+                                            changes results, but it decides the kernel family as
+                                            well as the speed: a pathline launch with d_order runs
+                                            the plain per-lane kernels and never the cooperative
+                                            tile kernels, which need the state itself in slot
+                                            order (see mops_traj_selection). */
     const int32_t* d_n_live;             /* optional device count: only slots [0, *d_n_live) hold
                                             live particles (after mops_order_particles_live); the
                                             launch spreads just those over the XCDs.  NULL = all n. */
@@ -304,6 +308,25 @@ mops_status mops_traj_advance(const mops_mesh* mesh, const mops_field* front, co
                               const mops_traj_cfg* cfg, const mops_particles* particles,
                               int64_t step_begin, int64_t step_end, double* d_records,
                               int64_t record_stride, void* stream);
+
+/* Which kernel family the pathline launches of `stream` on this mesh ran: a
+ * blocking test / diagnostic entry, not part of any hot path (no reference
+ * counterpart).  A pathline launch of mops_traj_advance (and of the sampled and
+ * captured entries over it) on a maxEdges <= 7 mesh with d_order == NULL and a
+ * method other than MOPS_RK4_RELOCATE first runs the selection kernel, which
+ * counts the runs of equal cells per 64-slot wave and sets the stream's device
+ * flag: 1 = the cooperative tile kernels run (Euler: the tile step; RK4: the
+ * hand-off kernel and the resumed one), 0 = the plain kernel.  Every other
+ * launch -- streamlines, d_order set, MOPS_RK4_RELOCATE, the layer and the
+ * diffusive entries, a wider mesh -- makes no selection and runs per-lane
+ * kernels.
+ * *count: the number of launches so far on this (mesh, stream) that made a
+ * selection, a host counter (0 if none).  *flag: the device flag after
+ * hipStreamSynchronize(stream), i.e. how the stream's last selection fell;
+ * -1 when *count == 0.  A caller reads *count before and after a launch: the
+ * difference says a selection was made, *flag how it fell.
+ * MOPS_ERR_INVALID for a null argument. */
+mops_status mops_traj_selection(const mops_mesh* mesh, void* stream, int32_t* flag, int64_t* count);
 
 /* ---- fixed-layer streamlines and pathlines -------------------------------- */
 

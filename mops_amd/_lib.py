@@ -22,7 +22,7 @@ EXPORTED = (
     "mops_order_particles_live", "mops_permute_arrays", "mops_records_clear_dead",
     "mops_traj_num_records", "mops_traj_num_steps", "mops_traj_advance", "mops_traj_finalize", "mops_traj_last_points",
     "mops_layer_velocity_bytes", "mops_field_layer_velocity", "mops_traj_advance_layer", "mops_run_trajectories_layer",
-    "mops_traj_alpha_table",
+    "mops_traj_alpha_table", "mops_traj_selection",
     "mops_diffusion_scale", "mops_traj_advance_diffuse", "mops_traj_advance_layer_diffuse", "mops_selftest_philox",
     "mops_run_trajectories_diffuse", "mops_run_trajectories_layer_diffuse",
     "mops_traj_sample_attrs", "mops_traj_advance_sampled", "mops_traj_finalize_attrs", "mops_run_pathline_attrs",
@@ -176,6 +176,8 @@ def load(path: str | None = None):
     lib.mops_traj_num_records.argtypes = [P]; lib.mops_traj_num_records.restype = I64
     lib.mops_traj_num_steps.argtypes = [P]; lib.mops_traj_num_steps.restype = I64
     lib.mops_traj_advance.argtypes = [P, P, P, P, P, I64, I64, P, I64, P]; lib.mops_traj_advance.restype = st
+    if hasattr(lib, "mops_traj_selection"):  # (older engine builds timed as variants lack the witness)
+        lib.mops_traj_selection.argtypes = [P, P, P, P]; lib.mops_traj_selection.restype = st
     lib.mops_layer_velocity_bytes.argtypes = [P]; lib.mops_layer_velocity_bytes.restype = I64
     lib.mops_field_layer_velocity.argtypes = [P, P, I32, P, P]; lib.mops_field_layer_velocity.restype = st
     lib.mops_traj_advance_layer.argtypes = [P, P, P, P, P, I64, I64, P, I64, P]

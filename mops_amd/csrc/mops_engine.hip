@@ -3915,7 +3915,7 @@ void free_mesh(mops_mesh* m) {
     (void)hipFree(m->d_scratch);
     (void)hipFree(m->d_eoc); (void)hipFree(m->d_coe); (void)hipFree(m->d_exyz); (void)hipFree(m->d_rbf_coef);
     (void)hipFree(m->d_rbf_slot);
-    for (auto& f : m->coop_flags) (void)hipFree(f.second);
+    for (auto& f : m->coop_flags) (void)hipFree(f.d_flag);
     for (auto& t : m->alpha_tabs) (void)hipFree(t.second);
     (void)hipFree(m->d_vold);
     delete m;
@@ -3976,14 +3976,15 @@ __global__ void __launch_bounds__(256) coop_select_kernel(int64_t n, const int* 
     if (threadIdx.x == 0) *flag = (S > 0 && runs[0] <= (unsigned long long)MOPS_COOP_CELLS * (unsigned long long)S) ? 1 : 0;
 }
 
-// The stream's instantiation flag (mops_mesh::coop_flags), allocated on the stream's first pathline launch.
+// The stream's instantiation flag (mops_mesh::coop_flags), allocated on the stream's first pathline launch.  Its
+// caller launches coop_select_kernel next: the entry's count of such launches advances here.
 static mops_status coop_flag(const mops_mesh* mesh, hipStream_t s, int** out) {
     std::lock_guard<std::mutex> lk(mesh->coop_mu);
-    for (const auto& f : mesh->coop_flags)
-        if (f.first == s) { *out = f.second; return MOPS_OK; }
+    for (auto& f : mesh->coop_flags)
+        if (f.stream == s) { f.launches += 1; *out = f.d_flag; return MOPS_OK; }
     int* d = nullptr;
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), sizeof(int)));
-    mesh->coop_flags.emplace_back(s, d);
+    mesh->coop_flags.push_back({s, d, 1});
     *out = d;
     return MOPS_OK;
 }
@@ -5071,6 +5072,26 @@ mops_status mops_traj_advance(const mops_mesh* mesh, const mops_field* front, co
                               const mops_traj_cfg* cfg, const mops_particles* p, int64_t step_begin,
                               int64_t step_end, double* d_records, int64_t record_stride, void* stream) {
     return traj_advance_impl(mesh, front, back, cfg, p, step_begin, step_end, d_records, record_stride, stream, nullptr);
+}
+
+mops_status mops_traj_selection(const mops_mesh* mesh, void* stream, int32_t* flag, int64_t* count) {
+    if (!mesh || !flag || !count) return fail(MOPS_ERR_INVALID, "mops_traj_selection: invalid inputs");
+    hipStream_t s = (hipStream_t)stream;
+    const int* d = nullptr;
+    int64_t launches = 0;
+    {
+        std::lock_guard<std::mutex> lk(mesh->coop_mu);
+        for (const auto& f : mesh->coop_flags)
+            if (f.stream == s) { d = f.d_flag; launches = f.launches; }
+    }
+    *count = launches;
+    *flag = -1;
+    if (launches == 0) return MOPS_OK;
+    HIP_TRY(hipStreamSynchronize(s));  // (the stream's last selection has written the flag)
+    int h = -1;
+    HIP_TRY(hipMemcpy(&h, d, sizeof(int), hipMemcpyDeviceToHost));
+    *flag = h;
+    return MOPS_OK;
 }
 
 // ---- fixed-layer trajectories ------------------------------------------------

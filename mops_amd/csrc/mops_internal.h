@@ -100,9 +100,15 @@ struct mops_mesh {
     int* d_vold = nullptr;
     // the pathline launches' instantiation flag (coop_select_kernel), one per HIP stream: launches on
     // one stream run in order, so the next launch's selection never overwrites a flag a running
-    // trajectory kernel still reads; allocated once per stream (no per-launch allocation)
+    // trajectory kernel still reads; allocated once per stream (no per-launch allocation).  `launches` counts, on
+    // the host, the stream's launches that ran the selection (mops_traj_selection's witness)
+    struct CoopFlag {
+        hipStream_t stream;
+        int* d_flag;
+        int64_t launches;
+    };
     mutable std::mutex coop_mu;
-    mutable std::vector<std::pair<hipStream_t, int*>> coop_flags;
+    mutable std::vector<CoopFlag> coop_flags;
     // the pathline launches' time-fraction tables (alpha_table), one per distinct number of steps: a run's
     // n_steps comes from its settings, so a mesh sees one or a few; built on the first launch that needs it
     mutable std::vector<std::pair<int64_t, double*>> alpha_tabs;

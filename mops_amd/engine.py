@@ -177,6 +177,17 @@ class DeviceMesh:
                                                       C.c_void_p(d_cells), _stream_handle(stream)),
                     "mops_locate_cells_hinted")
 
+    def tile_selection(self, stream=None):
+        """``(flag, count)`` of the pathline launches on ``stream`` (None: stream 0) -- a blocking test / diagnostic
+        entry (mops_traj_selection).  ``count``: how many launches on this mesh and stream ran the cooperative-tile
+        selection so far; ``flag``: how the last of them fell once the stream has drained, 1 = the tile kernels,
+        0 = the plain kernel, -1 while ``count`` is 0.  A launch with a processing order (``run_trajectories``), a
+        streamline, MOPS_RK4_RELOCATE, the layer and diffusive entries and a mesh past maxEdges 7 never select."""
+        flag, count = C.c_int32(-1), C.c_int64(0)
+        L.check(L.load().mops_traj_selection(self.handle, _stream_handle(stream), C.byref(flag), C.byref(count)),
+                "mops_traj_selection")
+        return int(flag.value), int(count.value)
+
     def close(self):
         if getattr(self, "handle", None):
             L.load().mops_mesh_destroy(self.handle)

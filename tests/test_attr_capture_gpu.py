@@ -68,15 +68,20 @@ def _snapshot(ps):
     return out
 
 
-def _run(c, cfg, seeds, depths, cells, W, names=NAMES, ranges=None, reorder=False):
+def _run(c, cfg, seeds, depths, cells, W, names=NAMES, ranges=None, reorder=False, expect_tile=False):
     """One run over the step ranges (default: one call).  W None: the plain advance without a slab; W 0: the
-    split path; W > 0: the capture path with a window of W slots."""
+    split path; W > 0: the capture path with a window of W slots.  ``expect_tile``: every trajectory launch of
+    every call must have selected the tile kernels (DeviceMesh.tile_selection)."""
     from mops_amd.engine import ParticleSet
     ps = ParticleSet(c.dm, seeds, depths, cfg, cells=cells, n_attr=0 if W is None else len(names),
                      capture_slots=W or 0)
     lists = None if W is None else c.lists(names)
     for b, e in ranges or [(0, cfg.n_steps)]:
+        _, count = c.dm.tile_selection()
         ps.advance(c.f0, c.f1, b, e, attrs=lists)
+        if expect_tile:
+            flag, after = c.dm.tile_selection()
+            assert after > count and flag == 1, (W, flag, after - count)
         if reorder:
             ps.reorder()
     return _snapshot(ps)
@@ -129,19 +134,20 @@ def _dense_seeds(mesh):
 
 @pytest.mark.parametrize("euler", [True, False], ids=["euler", "rk4"])
 def test_dense_seeds_tile_kernels(case, euler):
-    """The only case whose waves take the cooperative tile, the RK4 hand-off and the resumed kernel: the split
-    path is the reference (the Python restatement is too slow at 360 steps x 800 particles)."""
+    """The case of this file whose waves take the cooperative tile, the RK4 hand-off and the resumed kernel, in their
+    plain and their capture instantiations (every launch is asserted to have selected the tile): the split path is
+    the reference (the Python restatement is too slow at 360 steps x 800 particles)."""
     seeds, depths = _dense_seeds(case.mesh)
     assert len(seeds) % 64 != 0
     cfg = _cfg(euler, delta_t=120, duration=43200, record_t=3600)
     assert cfg.n_records == 12
     args = (case, cfg, seeds, depths, None)
-    split = _run(*args, 0)
+    split = _run(*args, 0, expect_tile=True)
     assert (split["death"] >= 0).any() and (split["death"] < 0).any()
     alive = split["death"] < 0
     assert np.all(split["slab"][:, 1, alive] != 0.0)  # every slot of a live particle was sampled
     for W in (12, 3):
-        _same(_run(*args, W), split, ("slab", "records") + STATE, f"W={W}")
+        _same(_run(*args, W, expect_tile=True), split, ("slab", "records") + STATE, f"W={W}")
 
 
 @pytest.mark.parametrize("euler", [True, False], ids=["euler", "rk4"])

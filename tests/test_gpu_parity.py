@@ -278,14 +278,17 @@ def test_pathline_parity(dev_small, ref_small, small_case, oracle_lib, method):
 @pytest.mark.parametrize("method", ["euler", "rk4"])
 @pytest.mark.parametrize("variant", ["forward", "backward", "zlevel"])
 def test_pathline_cooperative_waves(gpu, engine_lib, dev_small, ref_small, small_case, oracle_lib, variant, method):
-    """Pathline waves that share cells (config 3's density: ~40 particles per cell) take the
-    cooperative path -- each group's polygon, edge normals and hinted-layer records loaded once into the
-    wave's LDS tile and kept until a lane's cell or layer changes (traj_kernel, MOPS_COOP_PE / _PR); waves
-    with more than MOPS_COOP_G groups switch to per-lane normals, and in RK4 (MOPS_RK4_HANDOFF) a wave
-    leaves the hexagon-tile kernel at its first step outside a hexagon or the tile and finishes in the
-    cooperative one.  Dense cells with one or two depth groups, seeds on land (dead at step 0), particles
-    dying later, a partial last wave; forward, backward (dt < 0), and MPAS z-level columns (partial
-    bottom cells: hint misses change the groups) -- bit-exact against the oracle."""
+    """Pathline waves that share cells (config 3's density: ~40 particles per cell), run twice against one oracle
+    result.  run_trajectories launches with a processing order, which never selects the tile: it runs the plain
+    kernels (traj_kernel<7, true, EULER>) on these dense waves.  The slot-ordered run (tile_case.run_slot_ordered,
+    selection flag 1 asserted) takes the cooperative path -- each group's polygon, edge normals and hinted-layer
+    records loaded once into the wave's LDS tile and kept until a lane's cell or layer changes (traj_kernel,
+    MOPS_COOP_PE / _PR); waves with more than MOPS_COOP_G groups switch to per-lane normals, and in RK4
+    (MOPS_RK4_HANDOFF) a wave leaves the hexagon-tile kernel at its first step outside a hexagon or the tile and
+    finishes in the cooperative one.  Dense cells with one or two depth groups, seeds on land (dead at step 0),
+    particles dying later, a partial last wave; forward, backward (dt < 0), and MPAS z-level columns (partial
+    bottom cells: hint misses change the groups) -- both runs bit-exact against the oracle."""
+    import tile_case
     from mops_amd import synth
     from mops_amd.engine import DeviceField, TrajectoryConfig, run_trajectories
     mesh, _, _ = small_case
@@ -322,6 +325,8 @@ def test_pathline_cooperative_waves(gpu, engine_lib, dev_small, ref_small, small
                          euler=euler, backward=back, cells=got["cells"])
     assert len(seeds) % 64 != 0
     assert_lines_match(got, ref, f"pathline cooperative waves ({variant}, {method})")
+    tiled = tile_case.run_slot_ordered(dm, f0, f1, cfg, seeds, depths, got["cells"], expect_flag=1)
+    assert_lines_match(tiled, ref, f"pathline cooperative waves ({variant}, {method}), tile kernels")
     assert (ref["death"] >= 0).any() and (ref["death"] < 0).any()
     if euler:
         assert (ref["death"] < 0).sum() > len(seeds) // 2

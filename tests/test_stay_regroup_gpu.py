@@ -1,6 +1,11 @@
 """Cooperative pathline waves whose lanes change cell and layer often: the tile kernel's wave-synchronous
 stay-ball re-anchoring and its regroups against the CPU oracle, bit for bit.
 
+Every oracle case runs twice against one oracle result: through run_trajectories, which launches with a
+processing order and therefore runs the plain kernel, and slot-ordered through a ParticleSet
+(tile_case.run_slot_ordered), where the launch's selection is asserted to have picked the tile kernels -- the
+re-anchoring is compiled into the tile Euler kernel only.
+
 The stay ball and the tile are speed-only state, so every comparison is tests/test_gpu_parity.py's
 assert_lines_match (np.array_equal on points, velocity, lastPoint, depth and death steps).  The seeds are those
 of test_pathline_cooperative_waves (14 random cells x 45..58 particles jittered by 20 km), here on the 41k-cell
@@ -96,6 +101,17 @@ def _run_both(case, oracle_lib, topo, euler, back, seeds, depths, dt=DT, duratio
     return got, ref
 
 
+def _run_tiled(case, topo, euler, back, seeds, depths, cells, dt=DT, duration=DAYS * 86400, rec=REC):
+    """The same run slot-ordered, its launch asserted to have selected the tile kernels."""
+    import tile_case
+    from mops_amd.engine import TrajectoryConfig
+    _, dm, get = case
+    f0, f1, _, _ = get(topo)
+    cfg = TrajectoryConfig(deltaT=dt, simulationDuration=duration, recordT=rec, depth=0.0, method=1 if euler else 0,
+                           direction=1 if back else 0)
+    return tile_case.run_slot_ordered(dm, f0, f1, cfg, seeds, depths, cells, expect_flag=1)
+
+
 def _assert_crossing_heavy(mesh, oracle_lib, ref, cells0):
     """On the oracle's output: more than half of the particles stay alive and at least half of the live ones
     end in another cell than they started in (so the case cannot pass without cell changes)."""
@@ -114,6 +130,8 @@ def test_crossing_heavy_cooperative_waves(case, oracle_lib, direction):
     seeds, depths = _seeds(mesh)
     got, ref = _run_both(case, oracle_lib, "sigma", True, direction == "backward", seeds, depths)
     assert_lines_match(got, ref, f"crossing-heavy cooperative waves ({direction})")
+    tiled = _run_tiled(case, "sigma", True, direction == "backward", seeds, depths, got["cells"])
+    assert_lines_match(tiled, ref, f"crossing-heavy cooperative waves ({direction}), tile kernel")
     _assert_crossing_heavy(mesh, oracle_lib, ref, got["cells"])
 
 
@@ -125,13 +143,21 @@ def test_crossing_heavy_zlevel(case, oracle_lib, direction):
     seeds, depths = _seeds(mesh, zlevel=True)
     got, ref = _run_both(case, oracle_lib, "zlevel", True, direction == "backward", seeds, depths)
     assert_lines_match(got, ref, f"crossing-heavy z-level waves ({direction})")
+    tiled = _run_tiled(case, "zlevel", True, direction == "backward", seeds, depths, got["cells"])
+    assert_lines_match(tiled, ref, f"crossing-heavy z-level waves ({direction}), tile kernel")
     _assert_crossing_heavy(mesh, oracle_lib, ref, got["cells"])
 
 
 def test_launch_boundaries(gpu, case):
     """Case 3: one launch against launches of one record period -- every launch starts with cell-centred stay
     balls and an empty tile, a long launch carries re-anchored balls and its tile across the same steps; records
-    and final state must be identical."""
+    and final state must be identical.  The one launch selects the tile kernel (asserted).  Of the launches per
+    record period only the first does when the slots stay where they are: these seeds are crossing-heavy, so from
+    step 48 on a wave's 64 slots hold far more than six runs of cells (each launch's flag is asserted to be the
+    restatement's on the cells it saw).  A third set is therefore compacted before every launch, as
+    advance_pipelined(compact=True) does; there every launch selects the tile kernel (asserted), and its lines and
+    state are the one launch's in seed order."""
+    import tile_case
     import torch
     from mops_amd.engine import ParticleSet, TrajectoryConfig
     mesh, dm, get = case
@@ -139,23 +165,46 @@ def test_launch_boundaries(gpu, case):
     seeds, depths = _seeds(mesh)
     cfg = TrajectoryConfig(deltaT=DT, simulationDuration=DAYS * 86400, recordT=REC, depth=0.0, method=1)
     a = ParticleSet(dm, seeds, depths, cfg)
+    _, count = dm.tile_selection()
     a.advance(f0, f1, 0, cfg.n_steps)
+    count = tile_case.assert_selected(dm, count, 1, what="the one launch")
     b = ParticleSet(dm, seeds, depths, cfg)
     per = REC // DT
     assert cfg.n_steps == DAYS * per
+    flags = []
     for s in range(0, cfg.n_steps, per):
+        torch.cuda.synchronize()
+        flags.append(tile_case.select_rule(b.cell.cpu().numpy()))
         b.advance(f0, f1, s, s + per)
+        count = tile_case.assert_selected(dm, count, flags[-1], what=f"the launch from step {s}")
+    assert flags[0] == 1
     torch.cuda.synchronize()
     assert torch.equal(a.records, b.records)
     for k in ("x", "y", "z", "depth", "cell", "death"):
         assert torch.equal(getattr(a, k), getattr(b, k)), k
     assert int((a.death < 0).sum()) > a.n // 2
+    c = ParticleSet(dm, seeds, depths, cfg)
+    st = torch.cuda.current_stream()
+    live = None
+    for s in range(0, cfg.n_steps, per):
+        if s > 0:
+            live = c.compact(0, c.n, st, records_written=min(cfg.n_records, s // per + 1))
+        c.advance(f0, f1, s, s + per, stream=st, live_count=live)
+        count = tile_case.assert_selected(dm, count, 1, stream=st, what=f"the compacted launch from step {s}")
+    la, lc = a.finalize(pathline=True), c.finalize(pathline=True)
+    torch.cuda.synchronize()
+    for k in ("points", "velocity", "lastPoint"):
+        assert torch.equal(la[k], lc[k]), k
+    for k in ("x", "y", "z", "depth", "cell", "death"):
+        assert torch.equal(a.original(getattr(a, k)), c.original(getattr(c, k))), k
 
 
 def test_fallback_and_return(case, oracle_lib):
     """Case 4: 64 particles in 64 distinct neighbouring cells (more than MOPS_COOP_G groups: lane-normal mode,
     which retries the tile every 64 steps) beside twenty dense waves that keep the launch on the tile kernel;
-    200 steps."""
+    200 steps.  run_trajectories runs the plain kernel; the slot-ordered runs (selection flag 1 asserted) run the
+    tile Euler kernel and, in RK4, the hand-off kernel, which the wave of 64 cells -- more than MOPS_COOP_G_PR = 9
+    groups -- leaves at its first step for the resumed kernel."""
     mesh = case[0]
     cc = np.asarray(mesh.cellCoord, dtype=np.float64).reshape(-1, 3)
     coc = np.asarray(mesh.cellsOnCell, dtype=np.int64).reshape(mesh.nCells, -1) - 1
@@ -183,12 +232,30 @@ def test_fallback_and_return(case, oracle_lib):
     assert_lines_match(got, ref, "lane-normal wave beside cooperative waves")
     assert len(np.unique(got["cells"][:64])) == 64
     assert (ref["death"][:64] < 0).sum() > 32 and (ref["death"][64:] < 0).sum() > 640
+    tiled = _run_tiled(case, "sigma", True, False, seeds, depths, got["cells"], duration=200 * DT, rec=50 * DT)
+    assert_lines_match(tiled, ref, "lane-normal wave beside cooperative waves, tile kernel")
+    # the patch's cells are spread over the waves of the slot-ordered launch by the locality order: the waves
+    # that hold them, and how many of the 64 the fullest of them holds, read off the launch's slot ids
+    in_wave = np.bincount(np.flatnonzero(np.isin(tiled["slot_ids"], np.arange(64))) // 64)
+    print(f"the 64 distinct-cell particles sit in {int((in_wave > 0).sum())} waves, at most {int(in_wave.max())} in one")
+    assert in_wave.max() > 9, "no wave of the slot-ordered launch holds more than MOPS_COOP_G_PR distinct cells"
+    # RK4: the hand-off kernel and the resumed kernel on the same seeds
+    _, _, get = case
+    _, _, r0, r1 = get("sigma")
+    ref4 = oracle_lib.run(mesh, r0, r1, seeds, depths=depths, delta_t=DT, duration=200 * DT, record_t=50 * DT,
+                          euler=False, backward=False, cells=got["cells"])
+    tiled4 = _run_tiled(case, "sigma", False, False, seeds, depths, got["cells"], duration=200 * DT, rec=50 * DT)
+    assert_lines_match(tiled4, ref4, "lane-normal wave beside cooperative waves, rk4 hand-off")
+    assert (ref4["death"] > 50).any(), "no RK4 particle lived to the first record"
 
 
 def test_rk4_unchanged(case, oracle_lib):
-    """Case 5: case 1 with RK4 -- the hand-off kernel and the resumed tile kernel, which share the step loop and
-    the regroup code with the Euler kernel and keep the per-lane stay test."""
+    """Case 5: case 1 with RK4.  run_trajectories runs the plain RK4 kernel; the slot-ordered run (selection flag
+    1 asserted) runs the hand-off kernel and the resumed tile kernel, which share the step loop and the regroup
+    code with the Euler kernel and keep the per-lane stay test."""
     mesh = case[0]
     seeds, depths = _seeds(mesh)
     got, ref = _run_both(case, oracle_lib, "sigma", False, False, seeds, depths)
     assert_lines_match(got, ref, "crossing-heavy cooperative waves (rk4)")
+    tiled = _run_tiled(case, "sigma", False, False, seeds, depths, got["cells"])
+    assert_lines_match(tiled, ref, "crossing-heavy cooperative waves (rk4), hand-off and resumed kernels")

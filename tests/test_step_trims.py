@@ -230,24 +230,27 @@ def trim_seeds(small_case):
     special = np.concatenate([verts, mids, centres, cc[cells]])
     seeds += [special, land]
     depths += [np.full(len(special), 300.0), np.full(len(land), 500.0)]
+    # The 149 special and land seeds sit one or two to a cell: with them alone the set has 86 runs of equal cells in
+    # 14 waves, over the 6 per wave at which a slot-ordered launch still selects the tile kernels.  30 more
+    # particles in each dense cell (after the seeds above, from a generator of their own, so those are unchanged)
+    # bring it to 21 waves, and every launch of _run_segments selects the tile (asserted there).
+    rng2 = np.random.default_rng(4141)
+    for j, c in enumerate(cells):
+        u = cc[c] / np.linalg.norm(cc[c])
+        jit = rng2.normal(size=(30, 3)) * 2.0e4
+        p = u + (jit - np.outer(jit @ u, u)) / 6.371e6
+        seeds.append(p / np.linalg.norm(p, axis=1, keepdims=True) * 6.37101e6)
+        depths.append(np.full(30, 300.0) if j < 7 else np.where(np.arange(30) % 2 == 0, 300.0, 1100.0))
     seeds = np.concatenate(seeds)
     assert len(seeds) % 64 != 0
     return seeds, np.concatenate(depths).astype(np.float32)
 
 
 def _run_segments(dm, f0, f1, cfg, seeds, depths, cells, bounds):
-    """The run as launches over [bounds[i], bounds[i+1]), assembled like run_trajectories' result."""
-    import torch
-    from mops_amd.engine import ParticleSet
-    ps = ParticleSet(dm, seeds, depths, cfg, cells=cells)
-    for lo, hi in zip(bounds[:-1], bounds[1:]):
-        ps.advance(f0, f1, lo, hi)
-    lines = ps.finalize(pathline=True)
-    torch.cuda.synchronize()
-    out = {k: v.cpu().numpy() for k, v in lines.items()}
-    out["death_step"] = ps.original(ps.death).cpu().numpy()
-    out["final_depth"] = ps.original(ps.depth).cpu().numpy()
-    return out
+    """The run as slot-ordered launches over [bounds[i], bounds[i+1]), assembled like run_trajectories' result;
+    every launch is asserted to have selected the tile kernels (tests/tile_case.py)."""
+    import tile_case
+    return tile_case.run_slot_ordered(dm, f0, f1, cfg, seeds, depths, cells, expect_flag=1, bounds=bounds)
 
 
 # RK4 runs with a time step at which particles die during the run on this 2.4k-cell mesh (a stage leaves the
@@ -268,9 +271,10 @@ RECORD_T = {"every5": lambda dt: 5 * dt, "odd4": lambda dt: 4 * dt + dt // 6, "o
 @pytest.mark.parametrize("method", ["euler", "rk4"])
 def test_pathline_trims_parity(dev_small, ref_small, small_case, oracle_lib, trim_seeds, method, direction, rec):
     """Pathlines through the table-fed time fraction and the guarded quotient block, bit-exact against the
-    oracle: as one launch and as three launches whose boundaries fall between record steps.  Some particles
-    are dead at step 0 and some survive; in the RK4 cases some die on a record step and some between record steps
-    (see DELTA_T)."""
+    oracle: through run_trajectories (a processing order: the plain kernels), and slot-ordered on the tile kernels
+    (selection flag 1 asserted per launch) as one launch and as three launches whose boundaries fall between
+    record steps.  Some particles are dead at step 0 and some survive; in the RK4 cases some die on a record step
+    and some between record steps (see DELTA_T)."""
     from mops_amd.engine import TrajectoryConfig, run_trajectories
     mesh, _, _ = small_case
     dm, f0, f1 = dev_small
@@ -287,6 +291,8 @@ def test_pathline_trims_parity(dev_small, ref_small, small_case, oracle_lib, tri
                          euler=euler, backward=back, cells=got["cells"])
     label = f"pathline {method} {direction} {rec}"
     _assert_lines_match(got, ref, label + " (one launch)")
+    one = _run_segments(dm, f0, f1, cfg, seeds, depths, got["cells"], [0, cfg.n_steps])
+    _assert_lines_match(one, ref, label + " (one launch, tile kernels)")
     period = record_t // dt
     bounds = [0, 101, 233, cfg.n_steps]
     assert all((b % period) not in (0, period - 1) for b in bounds[1:-1])

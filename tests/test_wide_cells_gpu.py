@@ -171,8 +171,13 @@ def test_waves_of_every_kind_in_seed_order(device, key, mode):
 @pytest.mark.parametrize("euler", [True, False], ids=["euler", "rk4"])
 def test_dense_waves_on_heptagons(device, oracle_lib, capsys, euler, backward):
     """test_pathline_cooperative_waves' density (45..58 particles per cell, one or two depth groups) with five of
-    the 14 cells heptagons and the other nine hexagons upstream of one: the cooperative tile and, in RK4, the
-    hand-off kernel on live heptagons and on a wave's first step out of a hexagon into one."""
+    the 14 cells heptagons and the other nine hexagons upstream of one, run twice against one oracle result:
+    through run_trajectories, which launches with a processing order and so runs the plain kernels on live
+    heptagons, and slot-ordered (tile_case.run_slot_ordered, selection flag 1 asserted), which runs the cooperative
+    tile and, in RK4, the hand-off kernel and the resumed one: waves with a lane in a heptagon are handed over at
+    step 0, and the particles seeded towards a heptagon die at its edge there (quirk Q1) or, in Euler, cross
+    into it on the tile."""
+    import tile_case
     from mops_amd.engine import run_trajectories
     d = device("me7")
     seeds, depths, cells = WC.dense_seeds("me7")
@@ -188,6 +193,9 @@ def test_dense_waves_on_heptagons(device, oracle_lib, capsys, euler, backward):
     assert len(seeds) % 64 != 0 and (nv[cells] == 7).sum() >= 4 and live7 >= 200
     assert (ref["death"] >= 0).any() and (ref["death"] < 0).any()
     assert_lines_match(got, ref, "dense waves on heptagons")
+    tiled = tile_case.run_slot_ordered(d.dm, d.f0, d.f1, _cfg(WC.DENSE_TIMES, euler, backward), seeds, depths,
+                                       got["cells"], expect_flag=1)
+    assert_lines_match(tiled, ref, "dense waves on heptagons, tile kernels")
 
 
 @pytest.mark.parametrize("key", WC.KEYS)
